@@ -9,9 +9,15 @@ A "step" is one pass of the hot path over one batch with inputs already resident
 (device graph construction, bases, 6x(global+local) message passing, fusion, pooling) -> L1 loss -> backward -> RCCL
 all-reduce of the flat gradient (N>1) -> clip -> Adam -> EMA, i.e. the reference loop main_qm9.py:103-118.
 Workload (config.workload): BASELINE.json configs[1] -- 128 molecules per GPU (weak scaling: global batch 128*N).
-One JSON line on rank 0: whole-job molecules/s + `roofline` (the scatter-add kernel, HIP-event timed, PMC traffic from
-profiles/) + `step_kernels` (rooflines of the step's dominant kernels at the workload shapes) + `cpu_baseline` (the
-oracle = port of the reference CPU forward+backward, bounded sample, N=1 only).
+One JSON line on rank 0: whole-job molecules/s and ms_per_step of the --steps timed steps.  A plain run does nothing else.
+
+--full adds the side measurements: forward-only rates, the zero-host-sync store path, the reference loop unchanged, the
+graph-construction bound, the exposed all-reduce (N>1), `roofline` (the scatter-add kernel, HIP-event timed, PMC traffic
+from profiles/), `step_kernels` (rooflines of the step's dominant kernels at the workload shapes), `other_configs` and
+`cpu_baseline` (the oracle = port of the reference CPU forward+backward, bounded sample, N=1 only).
+
+--dump-outputs DIR writes what the last timed step left to its caller as DIR/<name>.npy (rank 0): the step's loss, the
+pre-clip gradient norm, the flat parameters and their EMA shadow after the update.
 """
 import argparse
 import json
@@ -42,9 +48,14 @@ def parse():
     ap.add_argument('--dim', type=int, default=128)
     ap.add_argument('--n-layer', type=int, default=6)
     ap.add_argument('--n-batches', type=int, default=4, help='distinct resident batches cycled through')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-rooflines', action='store_true', help='skip the kernel roofline probes (profiling runs)')
-    ap.add_argument('--no-other-configs', action='store_true', help='skip the PDBbind / RNA side measurements')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the side measurements (forward-only, store path, reference loop, graph cost, exposed '
+                         'all-reduce, rooflines, other configurations, CPU baseline); a plain run times the steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the last timed step\'s outputs (loss, gradient norm, parameters, EMA shadow) as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-rooflines', action='store_true', help='with --full: skip the kernel roofline probes (profiling runs)')
+    ap.add_argument('--no-other-configs', action='store_true', help='with --full: skip the PDBbind / RNA side measurements')
     ap.add_argument('--force-comm', action='store_true',
                     help='N=1 only: run the bucketed gradient all-reduce through a 1-rank RCCL group (overhead check)')
     ap.add_argument('--cpu-seconds', type=float, default=20.0)
@@ -58,7 +69,10 @@ def parse():
     ap.add_argument('--cpu-dry-run', action='store_true',
                     help='NOT a measurement: exercise the multi-rank control flow (sharding, barriers, max-over-ranks '
                          'timing, gradient all-reduce) on CPU with the gloo backend and a stand-in module (tests/standin.py)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def event_time_ms(fn, reps, groups=1):
@@ -725,6 +739,29 @@ def describe_ranks(args, world, rank, dev, dry):
             'devices': [{k: e.get(k) for k in ('rank', 'host', 'pid', 'device', 'pci', 'name')} for e in everyone]}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """Write each array as dirname/<name>.npy in float32 (float64 stays float64).  Past DUMP_BUDGET_BYTES in all, every
+    array keeps a fixed, seeded sample of its elements in proportion to its size (name suffix `_sample`), so that two runs
+    of the same command are compared element for element."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32).reshape(-1)
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, int(a.size * (DUMP_BUDGET_BYTES / float(total)) * 0.99))
+            if keep < a.size:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+                a, name = a[idx], name + '_sample'
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 def guarded(fn, *a):
     """A side leg of the line: its failure is reported in its field, the line is still printed."""
     try:
@@ -823,7 +860,7 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         k = args.warmup + i
-        trainer.step(batches[k % nb], global_graphs=gB, next_data=batches[(k + 1) % nb])
+        loss = trainer.step(batches[k % nb], global_graphs=gB, next_data=batches[(k + 1) % nb])
         if marks is not None:
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()
@@ -848,10 +885,16 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = gB * args.steps / dt
 
-    # Exposed all-reduce time (N > 1, or N = 1 with --force-comm): the same loop with the gradient exchange skipped; the
-    # ranks' parameters drift apart from here on, which nothing below depends on (timings only).
+    # What the last timed step handed back, before anything below runs more steps on the same trainer.  The parameters
+    # are identical on every rank (one all-reduced update), so rank 0's copy stands for the job.
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'loss': loss, 'grad_norm': trainer.last_grad_norm, 'params': trainer.fp.flat,
+                                         'ema_params': trainer.shadow})
+
+    # Exposed all-reduce time (N > 1 with --full, or N = 1 with --force-comm): the same loop with the gradient exchange
+    # skipped; the ranks' parameters drift apart from here on, which nothing below depends on (timings only).
     exposed = None
-    if (world > 1 or args.force_comm) and not dry:
+    if ((world > 1 and args.full) or args.force_comm) and not dry:
         ksteps = min(args.steps, 100)
         orig_sync = trainer.sync_gradients
         trainer.sync_gradients = lambda: None
@@ -904,30 +947,32 @@ def main():
     # calls, each stalling on its own graph's size round trip, is reported beside it.
     from pamnet_amd.train import predict
     fsteps = min(args.steps, 200)
-    with torch.no_grad():
-        for i in range(2):
-            model(batches[i % nb])
-        sync()
-        t0 = time.perf_counter()
-        for i in range(fsteps):
-            model(batches[i % nb])
-        sync()
-        fwd_plain_ms = (time.perf_counter() - t0) / fsteps * 1e3
-        for _ in predict(model, (batches[i % nb] for i in range(4))):
-            pass
-        sync()
-        t0 = time.perf_counter()
-        for _ in predict(model, (batches[i % nb] for i in range(fsteps))):
-            pass
-        sync()
-        fwd_ms = (time.perf_counter() - t0) / fsteps * 1e3
+    fwd_ms = fwd_plain_ms = None
+    if args.full:
+        with torch.no_grad():
+            for i in range(2):
+                model(batches[i % nb])
+            sync()
+            t0 = time.perf_counter()
+            for i in range(fsteps):
+                model(batches[i % nb])
+            sync()
+            fwd_plain_ms = (time.perf_counter() - t0) / fsteps * 1e3
+            for _ in predict(model, (batches[i % nb] for i in range(4))):
+                pass
+            sync()
+            t0 = time.perf_counter()
+            for _ in predict(model, (batches[i % nb] for i in range(fsteps))):
+                pass
+            sync()
+            fwd_ms = (time.perf_counter() - t0) / fsteps * 1e3
 
     # Zero-host-sync path (pamnet_amd/store.py): the same molecules resident on the device as one
     # concatenated dataset, every batch collated by one gather launch INSIDE the timed loops and carrying its data-dependent
     # sizes as host integers (per-molecule counts taken once per dataset) -- graph construction reads nothing back.
     # Reported beside the classic numbers, never as `value`.
     zero_sync = None
-    if not args.cpu_dry_run and world == 1:       # a side measurement: single-GPU runs only (nothing the scaling runs need)
+    if args.full and not args.cpu_dry_run and world == 1:   # a side measurement: single-GPU runs only (nothing the scaling runs need)
         try:                                      # (a side leg must never cost the run its result line)
             from pamnet_amd.store import MoleculeStore
             lo, hi = shard_range(gB, rank, world)
@@ -970,14 +1015,14 @@ def main():
     # pipeline -- what "drops into main_qm9.py unchanged" delivers before anything of pamnet_amd.train is adopted.  A side
     # field on a model of its own (same architecture, same batches); never `value`.
     ref_loop = None
-    if not args.cpu_dry_run and world == 1:
+    if args.full and not args.cpu_dry_run and world == 1:
         ref_loop = guarded(reference_loop_unchanged, dev, args, batches)
 
     # What graph construction costs the step although it runs beside it (a side-stream launch displaces a workgroup
     # of the model's full-chip launches): the same steps on graphs prepared once and reused.  A bound, never `value` -- the
     # timed region above rebuilds the graph of every batch.
     graph_cost = None
-    if not args.cpu_dry_run and world == 1:
+    if args.full and not args.cpu_dry_run and world == 1:
         try:
             keep = {}
             for b in batches:
@@ -1023,16 +1068,17 @@ def main():
                        'nodes_per_batch': int(g.n), 'global_edges': int(g.glob.m), 'local_edges': int(g.loc.m),
                        'triplets': int(g.n_trip), 'pairs': int(g.n_pair)},
             'timed_region_s': dt, 'step_ms_spread': spread, 'comm': comm,
-            'forward_only_molecules_per_s': gB / (fwd_ms / 1e3), 'forward_ms': fwd_ms,
-            'forward_ms_unpipelined': fwd_plain_ms,
-            'zero_host_sync': zero_sync,
-            'graph_construction_cost': graph_cost,
-            'reference_loop_unchanged': ref_loop,
             'mfma': mfma_summary(args, g, ms_per_step),
         }
+        if args.full:
+            line.update({'forward_only_molecules_per_s': gB / (fwd_ms / 1e3), 'forward_ms': fwd_ms,
+                         'forward_ms_unpipelined': fwd_plain_ms,
+                         'zero_host_sync': zero_sync,
+                         'graph_construction_cost': graph_cost,
+                         'reference_loop_unchanged': ref_loop})
         if args.share_gpu:
             line['shared_gpu'] = 'all %d ranks on one device, gloo transport: a flow check, NOT a measurement' % world
-        if not args.no_rooflines:
+        if args.full and not args.no_rooflines:
             roof = scatter_add_roofline(dev, g, args.dim, args.stream_gb)
             s = roof['streamed']
             pmc = pmc_record('r06_scatter_add_pmc') or pmc_record('r05_scatter_add_pmc') or pmc_record('r04_scatter_add_pmc')
@@ -1060,7 +1106,7 @@ def main():
                                'us_per_launch': roof['workload']['ms'] * 1e3, 'gbs': roof['workload']['gbs'],
                                'frac': roof['workload']['gbs'] / HBM_PEAK_GBS}]}
             line['step_kernels'] = guarded(step_kernel_rooflines, dev, g, args.dim, args.n_layer)
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             line['other_configs'] = guarded(other_configs, dev)
             try:                                            # the scatter-add at the shape a configuration streams from HBM
                 k0 = line['other_configs']['pdbbind_b32_d128_l3']['kernels'][0]
@@ -1072,7 +1118,7 @@ def main():
                     'us_per_launch_warm': k0['us_per_launch'], 'frac_warm': k0['frac']})
             except Exception:                               # noqa: BLE001 -- a side field
                 pass
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(args, args.cpu_seconds)
             line['cpu_baseline']['parity'] = guarded(parity_beside_baseline, dev, args)
             line['speedup_vs_cpu'] = value / line['cpu_baseline']['value']

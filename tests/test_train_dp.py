@@ -472,6 +472,61 @@ def test_bench_plain_invocation_launches_its_own_ranks_on_cpu():
     assert r.returncode != 0 and 'WORLD_SIZE=3' in r.stderr and 'Traceback' not in r.stderr
 
 
+def _bench_dump(repo, out_dir, extra, env=None, timeout=600):
+    import json
+    import subprocess
+    import sys
+    cmd = [sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '1', '--dump-outputs', str(out_dir)] + extra
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=repo, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith('{'), r.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_repeat_on_cpu(tmp_path):
+    """--dump-outputs writes the last timed step's loss, gradient norm, parameters and EMA shadow as float32 .npy files;
+    the same command twice gives the same inputs and so the same arrays.  --steps sets the timed steps."""
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR')}
+    extra = ['--steps', '4', '--warmup', '1', '--batch-per-gpu', '8', '--n-layer', '3', '--cpu-dry-run']
+    runs = []
+    for k in range(2):
+        j = _bench_dump(repo, tmp_path / str(k), extra, env=env)
+        assert j['steps'] == 4 and j['ms_per_step'] > 0
+        assert abs(j['value'] - 8 * 4 / (j['ms_per_step'] * 4e-3)) < 1e-6 * j['value']
+        runs.append({n: np.load(str(tmp_path / str(k) / (n + '.npy'))) for n in ('loss', 'grad_norm', 'params', 'ema_params')})
+    for n, a in runs[0].items():
+        assert a.dtype == np.float32 and a.size > 0 and np.all(np.isfinite(a)), n
+        assert np.array_equal(a, runs[1][n]), n
+    assert not np.array_equal(runs[0]['params'], runs[0]['ema_params'])      # the update and the shadow are both there
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` times its steps and prints the headline only (the side measurements are --full's); with
+    --dump-outputs the real step's loss, gradient norm, parameters and EMA shadow land as float32 .npy files within 64 MB."""
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    j = _bench_dump(repo, tmp_path, ['--steps', '5', '--warmup', '2', '--batch-per-gpu', '32', '--n-layer', '2'], timeout=900)
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in j, k
+    assert j['steps'] == 5 and j['unit'] == 'molecules/s' and j['higher_is_better'] is True and j['dtype'] == 'f32'
+    assert abs(j['value'] - 32 * 5 / (j['ms_per_step'] * 5e-3)) < 1e-6 * j['value']
+    for k in ('roofline', 'step_kernels', 'other_configs', 'cpu_baseline', 'forward_ms', 'zero_host_sync',
+              'reference_loop_unchanged', 'graph_construction_cost'):
+        assert k not in j, k
+    files = sorted(os.listdir(str(tmp_path)))
+    assert files == ['ema_params.npy', 'grad_norm.npy', 'loss.npy', 'params.npy'], files
+    total = 0
+    for f in files:
+        a = np.load(str(tmp_path / f))
+        total += a.nbytes
+        assert a.dtype == np.float32 and a.size > 0 and np.all(np.isfinite(a)), f
+    assert total <= 64 << 20
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('kind', ['qm9_d128', 'rna_d16'])
 def test_direct_tape_backward_equals_autograd(kind):
@@ -639,7 +694,7 @@ def test_bench_eight_ranks_on_one_gpu_prints_one_line():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR')}
     cmd = [sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '8', '--share-gpu', '--steps', '3', '--warmup', '1',
-           '--batch-per-gpu', '16', '--n-layer', '2', '--no-rooflines', '--no-cpu-baseline', '--no-other-configs']
+           '--batch-per-gpu', '16', '--n-layer', '2', '--no-rooflines', '--no-cpu-baseline', '--no-other-configs', '--full']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=repo, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -667,7 +722,7 @@ def test_bench_two_ranks_on_one_gpu_runs_the_multi_rank_flow():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR')}
     cmd = [sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '2', '--share-gpu', '--steps', '6', '--warmup', '2',
-           '--batch-per-gpu', '32', '--n-layer', '2', '--no-rooflines', '--no-cpu-baseline', '--no-other-configs']
+           '--batch-per-gpu', '32', '--n-layer', '2', '--no-rooflines', '--no-cpu-baseline', '--no-other-configs', '--full']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=repo, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

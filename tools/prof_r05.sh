@@ -27,7 +27,7 @@ for k in rna pdbbind; do
 done
 (python $R/tools/fwd_store_pipe.py qm9 2>/dev/null; python $R/tools/fwd_store_pipe.py rna 2>/dev/null; python $R/tools/store_steps.py qm9 300 2>/dev/null; python $R/tools/store_steps.py rna 200 2>/dev/null; python $R/tools/store_steps.py pdbbind 60 2>/dev/null) | grep -v amdgpu.ids > $O/r05_forward_and_store_steps.txt
 cd $R && python -m pytest tests/test_hip_model.py tests/test_store.py -m gpu -q -s -k "baseline or trainer_step_path or large_batch or configs1" 2>/dev/null | grep -E "vs the reference|vs oracle|12 targets|Trainer.forward_backward|through the store|passed|failed" > $O/r05_parity_figures.txt
-cd $R && python bench.py 2>/dev/null | tail -1 > $O/r05_bench_line.json
+cd $R && python bench.py --full 2>/dev/null | tail -1 > $O/r05_bench_line.json
 ls -la $O | grep r05_
 # round 5: the fused global-edge backward + weight gradients against what it replaces, its phase timestamps, same-box A/B of the
 # PDBbind step with the old route (PAMNET_EDGE_WGRAD=0), the upper bound of "edge-embedding pieces once per step" (split probe)
