@@ -41,7 +41,7 @@ typedef void* pamnet_stream_t; /* hipStream_t */
 
 /* Library / ABI version (bumped on any signature change).  pamnet_abi_version() returns the PAMNET_ABI_VERSION the library
  * was built against; a binding compares it with this header's (pamnet_amd/lib.py load(): a stale .so fails loudly). */
-#define PAMNET_ABI_VERSION 14
+#define PAMNET_ABI_VERSION 15
 int pamnet_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------------
@@ -706,20 +706,27 @@ int pamnet_embed_multi_bwd_f32(const pamnet_embed_job* jobs, int32_t n_jobs, con
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Layer-stack engine: the n_layer x (global, local) loop of PAMNet.forward (models.py:196-204) in ONE call per
- * direction (dim = 128).  Host-side C++ enqueues ~10 (fwd) / ~20 (bwd) fused launches per layer pair on `stream`.
+ * direction.  Host-side C++ enqueues ~10 (fwd) / ~20 (bwd) fused launches per layer pair on `stream`.
+ *   d          : model width.  128: csrc/engine.hip; 16 / 32 / 64: csrc/narrow_engine.hip (node-side chains as single
+ *                launches); any other width -> PAMNET_EINVAL
  *   sizes      : {n, e_g, e_l, tp}
  *   graph_idx  : 18 device index arrays {g_ptr, g_row, g_col, gT_ptr, gT_perm, l_ptr, l_row, l_col, lT_ptr, lT_perm,
  *                tp_ptr, tp_row, tp_col, tpT_ptr, tpT_perm, cuts, tpT_edge, tpT_node}  (the *T_* entries are only read by
  *                the backward; cuts: nullable -- the work split of pamnet_seg_cuts_i32 made with the graph, else computed per
  *                call; tpT_edge / tpT_node: nullable pair -- pamnet_triplet_transpose_aux_i32; the narrow-width engine reads
  *                the first 15)
- *   gparams    : n_layer x 28 device pointers  {mlp_x1.W, .b, mlp_m.W [128,384], .b, W_edge_attr.W, tail W[10], b[10],
+ *   gparams    : n_layer x 28 device pointers  {mlp_x1.W, .b, mlp_m.W [d,3d], .b, W_edge_attr.W, tail W[10], b[10],
  *                W_out.weight, W_out.bias, W}
  *   lparams    : n_layer x 35 device pointers  {mlp_x1.W, .b, mlp_m_ji.W, .b, mlp_m_kj.W, .b, mlp_sbf.0.W, .b,
  *                mlp_sbf.1.W, .b, lin_rbf.W, lin_rbf_out.W, tail ...}
  *   saved/temp : caller-owned arenas sized by pamnet_stack_workspace (floats); `saved` must survive until the backward
  *   outs/atts  : [2*n_layer, n] rows ordered (global_0, local_0, global_1, ...)
- * wpack (nullable, both directions): scratch of pamnet_stack_pack_floats(n_layer) floats; when given, the call first
+ * pamnet_stack_layout: layout[0] = floats per layer pair in `saved`, layout[1] / [2] = offset of the global / local
+ * layer's node output [n, d] within a pair.
+ * At d = 16 / 32 / 64, save_for_backward, wpack, aux_stream and aux_events are ignored (every save is written, the
+ * weight images are packed inside `temp`, no fork; pamnet_stack_pack_floats reports 0), and the backward needs
+ * n, e_g, e_l, tp > 0.
+ * wpack (nullable, both directions): scratch of pamnet_stack_pack_floats(n_layer, d) floats; when given, the call first
  * re-packs the node chains' weight matrices into fragment-ordered images (pamnet_pack_weights_f32, one launch) and the
  * chains read those.  Contents need not survive the call.
  * Forward, save_for_backward = 0 (inference): tensors only the backward reads are not written (the single kernels take
@@ -734,20 +741,21 @@ int pamnet_embed_multi_bwd_f32(const pamnet_embed_job* jobs, int32_t n_jobs, con
  * k = n_layer-1 .. 0, so a data-parallel caller can start reducing the last layers' gradients on another stream while
  * the earlier layers are still being differentiated.
  * ------------------------------------------------------------------------------------------------------------------ */
-int pamnet_stack_workspace(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t n_layer, int64_t* saved_floats,
-                           int64_t* temp_floats_out);
-int pamnet_stack_pack_floats(int64_t n_layer, int64_t* floats);
-int pamnet_stack_layout(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t* layout);
-int pamnet_stack_fwd_f32(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer, const float* x0,
-                         const float* e_g, const float* rbf_e, const float* e_sbf, const float* const* gparams,
-                         const float* const* lparams, float* saved, float* temp, float* outs, float* atts,
-                         int32_t save_for_backward, float* wpack, pamnet_stream_t aux_stream, void* const* aux_events,
+int pamnet_stack_workspace(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t n_layer, int64_t d,
+                           int64_t* saved_floats, int64_t* temp_floats);
+int pamnet_stack_pack_floats(int64_t n_layer, int64_t d, int64_t* floats);
+int pamnet_stack_layout(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t d, int64_t* layout);
+int pamnet_stack_fwd_f32(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer, int64_t d,
+                         const float* x0, const float* e_g, const float* rbf_e, const float* e_sbf,
+                         const float* const* gparams, const float* const* lparams, float* saved, float* temp, float* outs,
+                         float* atts, int32_t save_for_backward, float* wpack, pamnet_stream_t aux_stream,
+                         void* const* aux_events, pamnet_stream_t stream);
+int pamnet_stack_bwd_f32(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer, int64_t d,
+                         const float* x0, const float* e_g, const float* rbf_e, const float* e_sbf,
+                         const float* const* gparams, const float* const* lparams, const float* saved, float* temp,
+                         const float* d_outs, const float* d_atts, float* const* ggrads, float* const* lgrads,
+                         float* d_x0, float* d_eg, float* d_rbf, float* d_sbf, float* wpack, void* const* layer_done,
                          pamnet_stream_t stream);
-int pamnet_stack_bwd_f32(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer, const float* x0,
-                         const float* e_g, const float* rbf_e, const float* e_sbf, const float* const* gparams,
-                         const float* const* lparams, const float* saved, float* temp, const float* d_outs,
-                         const float* d_atts, float* const* ggrads, float* const* lgrads, float* d_x0, float* d_eg,
-                         float* d_rbf, float* d_sbf, float* wpack, void* const* layer_done, pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Small whole-buffer reductions of the training step (csrc/reduce.hip), fixed summation order.
@@ -874,31 +882,6 @@ int pamnet_narrow_embed_rbf_fwd_f32(const float* dist, const float* freq, float 
 int pamnet_narrow_embed_rbf_bwd_f32(const float* dist, const float* freq, float cutoff, int64_t m, int64_t d,
                                     const float* Wa, const float* ba, const float* dy, float* partial, float* dW,
                                     float* db_dfreq, pamnet_stream_t stream);
-
-/* ------------------------------------------------------------------------------------------------------------------
- * Narrow-width layer-stack engine (csrc/narrow_engine.hip): the n_layer x (global, local) loop of PAMNet.forward
- * (models.py:196-204) at d = 16 / 32 / 64 in ONE call per direction -- the counterpart of pamnet_stack_*_f32.
- * sizes, graph_idx, gparams / lparams (n_layer x 28 / 35 device pointers; mlp_m etc. are [d, 3d]), ggrads / lgrads,
- * outs / atts ([2 n_layer, n]), saved / temp (caller-owned arenas sized by pamnet_narrow_stack_workspace; `saved` must
- * survive until the backward) and layer_done (nullable hipEvent_t handles) exactly as documented for pamnet_stack_*_f32.
- * The node-side chains of a layer are single launches (pre: mlp_x1 + projections; tail: mlp_x2 .. heads); weight
- * gradients are written (not accumulated) in fixed summation order; d_x0, d_eg, d_rbf, d_sbf are written.
- * The backward needs n, e_g, e_l, tp > 0.  pamnet_narrow_stack_layout: layout[0] = floats per layer pair in `saved`,
- * layout[1] / [2] = offset of the global / local layer's node output [n, d] within a pair.
- * ------------------------------------------------------------------------------------------------------------------ */
-int pamnet_narrow_stack_workspace(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t n_layer, int64_t d,
-                                  int64_t* saved_floats, int64_t* temp_floats);
-int pamnet_narrow_stack_layout(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t d, int64_t* layout);
-int pamnet_narrow_stack_fwd_f32(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer, int64_t d,
-                                const float* x0, const float* e_g, const float* rbf_e, const float* e_sbf,
-                                const float* const* gparams, const float* const* lparams, float* saved, float* temp,
-                                float* outs, float* atts, pamnet_stream_t stream);
-int pamnet_narrow_stack_bwd_f32(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer, int64_t d,
-                                const float* x0, const float* e_g, const float* rbf_e, const float* e_sbf,
-                                const float* const* gparams, const float* const* lparams, const float* saved, float* temp,
-                                const float* d_outs, const float* d_atts, float* const* ggrads, float* const* lgrads,
-                                float* d_x0, float* d_eg, float* d_rbf, float* d_sbf, void* const* layer_done,
-                                pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Dense layers of any width (csrc/dense.hip): Sequential(Linear, SiLU) of layers/basic.py:19-22 and the bare F.linear

@@ -362,15 +362,20 @@ inline int run_jobs(Jobs& j, float* partial, const Graph& g, const HeadGrads& h,
 
 }  // namespace
 
+// The entry points serve every model width: d = 128 runs the loops below, d = 16 / 32 / 64 the narrow engine's
+// (narrow_engine.hip), which checks d itself.
+
 // floats of the optional weight-image arena (`wpack`) of pamnet_stack_fwd_f32 / pamnet_stack_bwd_f32
-extern "C" int pamnet_stack_pack_floats(int64_t n_layer, int64_t* floats) {
+extern "C" int pamnet_stack_pack_floats(int64_t n_layer, int64_t d, int64_t* floats) {
+    if (d != D) return narrow_stack::pack_floats(n_layer, d, floats);
     if (n_layer < 1 || !floats) return PAMNET_EINVAL;
     *floats = n_layer * (PACK_FLOATS_PER_PAIR + EDGE_PACK_PER_PAIR * EDGE_IMG);
     return PAMNET_OK;
 }
 
-extern "C" int pamnet_stack_workspace(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t n_layer,
+extern "C" int pamnet_stack_workspace(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t n_layer, int64_t d,
                                       int64_t* saved_floats, int64_t* temp_floats_out) {
+    if (d != D) return narrow_stack::workspace(n, eg, el, tp, n_layer, d, saved_floats, temp_floats_out);
     if (n < 0 || eg < 0 || el < 0 || tp < 0 || n_layer < 1 || !saved_floats || !temp_floats_out) return PAMNET_EINVAL;
     Graph g{};
     g.n = n; g.eg = eg; g.el = el; g.tp = tp;
@@ -381,7 +386,8 @@ extern "C" int pamnet_stack_workspace(int64_t n, int64_t eg, int64_t el, int64_t
 
 // layout[0] = floats per layer pair in `saved`; layout[1] / layout[2] = offset of the global / local layer's output
 // node features x_out inside a pair's slab (for inspection: x after every layer).
-extern "C" int pamnet_stack_layout(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t* layout) {
+extern "C" int pamnet_stack_layout(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t d, int64_t* layout) {
+    if (d != D) return narrow_stack::layout(n, eg, el, tp, d, layout);
     if (n < 0 || eg < 0 || el < 0 || tp < 0 || !layout) return PAMNET_EINVAL;
     Graph g{};
     g.n = n; g.eg = eg; g.el = el; g.tp = tp;
@@ -405,11 +411,14 @@ static int fill_graph(Graph& g, const int64_t* sizes, const int32_t* const* idx)
     return PAMNET_OK;
 }
 
-extern "C" int pamnet_stack_fwd_f32(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer,
+extern "C" int pamnet_stack_fwd_f32(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer, int64_t d,
                                     const float* x0, const float* e_g, const float* rbf_e, const float* e_sbf,
                                     const float* const* gparams, const float* const* lparams, float* saved, float* temp,
                                     float* outs, float* atts, int32_t save_for_backward, float* wpack,
                                     pamnet_stream_t aux, void* const* aux_events, pamnet_stream_t st) {
+    if (d != D)
+        return narrow_stack::fwd(sizes, graph_idx, n_layer, d, x0, e_g, rbf_e, e_sbf, gparams, lparams, saved, temp, outs,
+                                 atts, st);
     Graph g;
     CK(fill_graph(g, sizes, graph_idx));
     if (n_layer < 1) return PAMNET_EINVAL;
@@ -638,12 +647,15 @@ extern "C" int pamnet_stack_fwd_f32(const int64_t* sizes, const int32_t* const* 
 
 // d_outs / d_atts: [2L][n].  ggrads / lgrads: gradient buffers in the same tables as the parameters (written, not
 // accumulated).  d_x0 [n,128] written; d_eg, d_rbf, d_sbf written (first layer processed) then accumulated.
-extern "C" int pamnet_stack_bwd_f32(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer,
+extern "C" int pamnet_stack_bwd_f32(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer, int64_t d,
                                     const float* x0, const float* e_g, const float* rbf_e, const float* e_sbf,
                                     const float* const* gparams, const float* const* lparams, const float* saved,
                                     float* temp, const float* d_outs, const float* d_atts, float* const* ggrads,
                                     float* const* lgrads, float* d_x0, float* d_eg, float* d_rbf, float* d_sbf,
                                     float* wpack, void* const* layer_done, pamnet_stream_t st) {
+    if (d != D)
+        return narrow_stack::bwd(sizes, graph_idx, n_layer, d, x0, e_g, rbf_e, e_sbf, gparams, lparams, saved, temp, d_outs,
+                                 d_atts, ggrads, lgrads, d_x0, d_eg, d_rbf, d_sbf, layer_done, st);
     Graph g;
     CK(fill_graph(g, sizes, graph_idx));
     if (n_layer < 1) return PAMNET_EINVAL;

@@ -1,6 +1,7 @@
 // Layer-stack engine for the narrow widths (dim = 16 / 32 / 64: the reference's RNA configurations,
 // inference_rna_puzzles.py:29-30, main_rna_puzzles.py:52-53): the n_layer x (global, local) loop of PAMNet.forward
-// (models.py:196-204) as ONE call per direction, the counterpart of engine.hip for dim = 128.
+// (models.py:196-204) as ONE call per direction, the counterpart of engine.hip for dim = 128: pamnet_stack_* (engine.hip)
+// dispatches here on d.
 //
 // Per layer the node-side chains are single launches (narrow_chain.h), the edge / triplet-row work uses the row kernels
 // of narrow_core.h, every weight gradient goes from the kernels' partial rows straight into the caller's gradient
@@ -381,8 +382,17 @@ inline void tail_fwd_params(NTailFwd& t, const float* const* tp, const Images& i
 
 }  // namespace
 
-extern "C" int pamnet_narrow_stack_workspace(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t n_layer, int64_t d,
-                                             int64_t* saved_floats, int64_t* temp_floats) {
+// ---- the narrow-width half of the pamnet_stack_* entry points (engine.hip dispatches here for d != 128) --------------
+
+// the weight images live inside `temp`: no `wpack` arena
+int narrow_stack::pack_floats(int64_t n_layer, int64_t d, int64_t* floats) {
+    if (n_layer < 1 || !floats || !width_ok(d)) return PAMNET_EINVAL;
+    *floats = 0;
+    return PAMNET_OK;
+}
+
+int narrow_stack::workspace(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t n_layer, int64_t d,
+                            int64_t* saved_floats, int64_t* temp_floats) {
     if (n < 0 || eg < 0 || el < 0 || tp < 0 || n_layer < 1 || !width_ok(d)) return PAMNET_EINVAL;
     if (!saved_floats || !temp_floats) return PAMNET_ENULL;
     const Lay L = make_layout(n, eg, el, tp, d, n_layer);
@@ -392,7 +402,7 @@ extern "C" int pamnet_narrow_stack_workspace(int64_t n, int64_t eg, int64_t el, 
 }
 
 // layout[0] = floats per layer pair in `saved`; [1], [2] = offsets of the global / local layer's node output in a pair
-extern "C" int pamnet_narrow_stack_layout(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t d, int64_t* layout) {
+int narrow_stack::layout(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t d, int64_t* layout) {
     if (!width_ok(d)) return PAMNET_EINVAL;
     if (!layout) return PAMNET_ENULL;
     const Lay L = make_layout(n, eg, el, tp, d);
@@ -400,10 +410,10 @@ extern "C" int pamnet_narrow_stack_layout(int64_t n, int64_t eg, int64_t el, int
     return PAMNET_OK;
 }
 
-extern "C" int pamnet_narrow_stack_fwd_f32(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer, int64_t d,
-                                           const float* x0, const float* e_g, const float* rbf_e, const float* e_sbf,
-                                           const float* const* gparams, const float* const* lparams, float* saved,
-                                           float* temp, float* outs, float* atts, pamnet_stream_t stream) {
+int narrow_stack::fwd(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer, int64_t d, const float* x0,
+                      const float* e_g, const float* rbf_e, const float* e_sbf, const float* const* gparams,
+                      const float* const* lparams, float* saved, float* temp, float* outs, float* atts,
+                      pamnet_stream_t stream) {
     if (!sizes || !graph_idx || !gparams || !lparams) return PAMNET_ENULL;
     const int64_t n = sizes[0], eg = sizes[1], el = sizes[2], tp = sizes[3];
     if (n < 0 || eg < 0 || el < 0 || tp < 0 || n_layer < 1 || !width_ok(d)) return PAMNET_EINVAL;
@@ -470,12 +480,11 @@ extern "C" int pamnet_narrow_stack_fwd_f32(const int64_t* sizes, const int32_t* 
     return PAMNET_OK;
 }
 
-extern "C" int pamnet_narrow_stack_bwd_f32(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer, int64_t d,
-                                           const float* x0, const float* e_g, const float* rbf_e, const float* e_sbf,
-                                           const float* const* gparams, const float* const* lparams, const float* saved,
-                                           float* temp, const float* d_outs, const float* d_atts, float* const* ggrads,
-                                           float* const* lgrads, float* d_x0, float* d_eg, float* d_rbf, float* d_sbf,
-                                           void* const* layer_done, pamnet_stream_t stream) {
+int narrow_stack::bwd(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer, int64_t d, const float* x0,
+                      const float* e_g, const float* rbf_e, const float* e_sbf, const float* const* gparams,
+                      const float* const* lparams, const float* saved, float* temp, const float* d_outs,
+                      const float* d_atts, float* const* ggrads, float* const* lgrads, float* d_x0, float* d_eg,
+                      float* d_rbf, float* d_sbf, void* const* layer_done, pamnet_stream_t stream) {
     if (!sizes || !graph_idx || !gparams || !lparams || !ggrads || !lgrads) return PAMNET_ENULL;
     const int64_t n = sizes[0], eg = sizes[1], el = sizes[2], tp = sizes[3];
     if (n <= 0 || eg <= 0 || el <= 0 || tp <= 0 || n_layer < 1 || !width_ok(d)) return PAMNET_EINVAL;   // (empty parts: the

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from pamnet_amd import fused, modules, narrow
+from pamnet_amd import fused, narrow, stack
 from pamnet_amd import graph as G
 from pamnet_amd import ops
 from pamnet_amd.modules import MLP, BesselBasis, GlobalMP, LocalMP, mlp_apply
@@ -133,14 +133,11 @@ class SphericalBasis(nn.Module):
 class _LazyLayers(object):
     """x after every layer, materialised from the engine's saved-activation arena only when somebody looks."""
 
-    def __init__(self, saved, graph, n_layer, dim=None):
-        self._args = (saved, graph, n_layer)
-        self._dim = dim
+    def __init__(self, *args):
+        self._args = args                   # stack.stack_x_layers(saved, graph, n_layer, d)
 
     def _views(self):
-        if self._dim is not None:
-            return narrow.stack_x_layers(*self._args, self._dim)
-        return fused.stack_x_layers(*self._args)
+        return stack.stack_x_layers(*self._args)
 
     def __iter__(self):
         return iter(self._views())
@@ -596,13 +593,9 @@ class _PAMNetBase(nn.Module):
         return len(seq) == 1 and fused.embed_supported(x, seq[0][0])
 
     def _run_layers(self, x, e_l, e_g, e_sbf, g, tape=None):
-        if modules._fused(x):                      # dim = 128 on an MI355X: the whole loop is one engine call
-            outs, atts, saved = fused.layer_stack(self.global_layer, self.local_layer, x, e_g, e_l, e_sbf, g, tape=tape)
-            self._x_layers = _LazyLayers(saved, g, self.n_layer)
-            return outs, atts
-        if modules._narrow(x) and narrow.engine_supported(x, g):       # dim 16 / 32 / 64: one engine call as well
-            outs, atts, saved = narrow.layer_stack(self.global_layer, self.local_layer, x, e_g, e_l, e_sbf, g, tape=tape)
-            self._x_layers = _LazyLayers(saved, g, self.n_layer, self.dim)
+        if stack.engine_supported(x, g):           # dim 128 / 16 / 32 / 64 on an MI355X: the whole loop is one engine call
+            outs, atts, saved = stack.layer_stack(self.global_layer, self.local_layer, x, e_g, e_l, e_sbf, g, tape=tape)
+            self._x_layers = _LazyLayers(saved, g, self.n_layer, x.size(1))
             return outs, atts
         outs, atts = [], []
         self._x_layers = []
@@ -624,15 +617,13 @@ class _PAMNetBase(nn.Module):
         row kernels: the whole forward is recorded on the model's own tape and handed to autograd as ONE node (ops.Tape)."""
         if not (ops.TAPE and torch.is_grad_enabled() and self.rbf_g.freq.is_cuda):
             return False
-        if self.dim == fused.D:
-            if not all(getattr(p, '_pamnet_direct', False) and p.grad is not None for p in self._top_params()):
-                return False
-            return fused.stack_plan(self.global_layer, self.local_layer).direct()
-        if self.dim in narrow.WIDTHS and narrow.ENABLED:
-            if not all(getattr(p, '_pamnet_direct', False) and p.grad is not None for p in self._all_params()):
-                return False
-            return fused.stack_plan(self.global_layer, self.local_layer).direct()      # (the engine's gradient tables)
-        return False
+        if not (self.dim == fused.D or (self.dim in narrow.WIDTHS and narrow.ENABLED)):
+            return False
+        # dim 128: the parameters outside the layer stack (the plan checks its own); narrow widths: all of them
+        params = self._top_params() if self.dim == fused.D else self._all_params()
+        if not all(getattr(p, '_pamnet_direct', False) and p.grad is not None for p in params):
+            return False
+        return stack.stack_plan(self.global_layer, self.local_layer).direct()
 
     def _checked_forward(self, data):
         """The dtype check just walked the cache against the live tree (~0.05 ms of host time); nothing re-hangs parameters

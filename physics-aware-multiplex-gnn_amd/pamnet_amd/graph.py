@@ -619,7 +619,7 @@ def _engine_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos, edge_ind
     else:
         g.glob_T = g.loc_T = g.tp_T = _NoTranspose
     g.__dict__['_lazy'] = lazy
-    # pointer tables of the layer-stack engines (fused._graph_tables): raw addresses, no tensors
+    # pointer tables of the layer-stack engine (stack._graph_tables): raw addresses, no tensors
     order = ('G_PTR', 'G_ROW', 'G_COL', 'GT_PTR', 'GT_PERM', 'L_PTR', 'L_ROW', 'L_COL', 'LT_PTR', 'LT_PERM',
              'T_PTR', 'T_ROW', 'T_COL', 'TT_PTR', 'TT_PERM', 'CUTS', 'TT_EDGE', 'TT_NODE')
     idx = (ctypes.c_void_p * 18)()

@@ -305,7 +305,7 @@ class Trainer(object):
     # -- gradient all-reduce -------------------------------------------------------------------------------------------
     def _setup_buckets(self, n_buckets):
         """Split the flat gradient into contiguous slices by layer pair, last layers first (plan_buckets).  On the GPU
-        the layer-stack backward records one event per layer pair (handed to it through the model's fused.StackCtx) and
+        the layer-stack backward records one event per layer pair (handed to it through the model's stack.StackCtx) and
         the slices are reduced on a side stream behind those events; on CPU (gloo tests) the same slices are reduced
         one after the other."""
         plan = plan_buckets(self.fp.layer_ranges, self.fp.grad.numel(), n_buckets)
@@ -314,7 +314,7 @@ class Trainer(object):
         self._buckets, self._tail_range = plan
         if not self.fp.flat.is_cuda:
             return
-        from . import fused
+        from . import stack
         dev = self.fp.flat.device
         L = len(self.fp.layer_ranges)
         events = [torch.cuda.Event() for _ in range(L)]
@@ -324,7 +324,7 @@ class Trainer(object):
         self._comm = torch.cuda.Stream(device=dev)
         layers = getattr(self.model, 'global_layer', None)
         if layers is not None:
-            self._stack_ctx = fused.stack_ctx(layers)
+            self._stack_ctx = stack.stack_ctx(layers)
             self._stack_ctx.events = events
 
     def sync_gradients(self):

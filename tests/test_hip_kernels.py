@@ -533,6 +533,7 @@ def test_fuse_pool_fwd_bwd(dev):
 def test_cabi_argument_errors(dev):
     """Every entry point validates its arguments before launching: negative sizes / unsupported widths -> PAMNET_EINVAL,
     missing required pointers -> PAMNET_ENULL (surfaced as RuntimeError by the binding); zero rows are a no-op."""
+    import ctypes
     from pamnet_amd import lib
     x = torch.randn(8, 128, device=dev)
     ptr = torch.tensor([0, 3, 8], dtype=torch.int32, device=dev)
@@ -549,6 +550,12 @@ def test_cabi_argument_errors(dev):
     with pytest.raises(RuntimeError, match='EINVAL'):
         lib.call('pamnet_adam_ema_f32', lib.ptr(x), lib.ptr(x), lib.ptr(x), lib.ptr(x), lib.ptr(x), 1023, 1e-3, 0.9, 0.999,
                  1e-8, 0.0, 1, 0.999, None, 1000.0, 0, st)
+    # the layer-stack entry points dispatch on the width: 128 and 16 / 32 / 64 have an engine, other widths are refused
+    need = (ctypes.c_int64 * 2)()
+    with pytest.raises(RuntimeError, match='EINVAL'):
+        lib.call('pamnet_stack_workspace', 8, 4, 4, 4, 1, 48, ctypes.addressof(need), ctypes.addressof(need) + 8)
+    for d in (16, 128):
+        lib.call('pamnet_stack_workspace', 8, 4, 4, 4, 1, d, ctypes.addressof(need), ctypes.addressof(need) + 8)
     # zero rows: nothing is launched, nothing is touched
     out.fill_(7.0)
     lib.call('pamnet_segment_sum_f32', lib.ptr(out), None, lib.ptr(x), None, None, None, None, lib.ptr(ptr), 0, 128, st)

@@ -11,7 +11,7 @@ for p in (REPO, os.path.join(REPO, 'physics-aware-multiplex-gnn_amd')):
 import torch  # noqa: E402
 
 import models  # noqa: E402
-from pamnet_amd import fused, graph as G, narrow, ops, store as S, synth  # noqa: E402
+from pamnet_amd import graph as G, ops, stack, store as S, synth  # noqa: E402
 from pamnet_amd.train import Trainer  # noqa: E402
 
 kind = sys.argv[1] if len(sys.argv) > 1 else 'rna'
@@ -55,8 +55,7 @@ wrap(G, 'spherical_basis', 'sbf')
 wrap(model, '_input_stage', 'input_stage')
 wrap(model, '_embed', 'embed_x')
 wrap(model, '_edge_embeddings', 'edge_embed')
-wrap(fused, 'layer_stack', 'stack_fwd')
-wrap(narrow, 'layer_stack', 'stack_fwd')
+wrap(stack, 'layer_stack', 'stack_fwd')
 wrap(ops, 'fuse_pool', 'fuse_pool')
 wrap(ops, 'l1_loss_with_grad', 'loss')
 wrap(ops, 'backward_whole', 'backward')
