@@ -451,13 +451,16 @@ def test_local_backward_pair_equals_the_two_launches(dev, rows, edges, acc):
 @pytest.mark.parametrize('nblk', [0, 2, 4])
 @pytest.mark.parametrize('save', [True, False])
 def test_lean_forward_chain_equals_the_parked_one(dev, nblk, save):
-    """Batches of more than 512 row tiles run the forward chain with three workgroups per CU and the saves written straight
-    from the accumulators (node_tail_fwd_lean_kernel); same arithmetic per row, so a launch over 8 200 rows (lean) must
-    reproduce, bit for bit, the first 8 000 rows as a launch of their own (500 tiles: the parked form) computes them."""
+    """Launches of more than LEAN_FROM_TILES = 256 row tiles run the forward chain with three workgroups per CU and the saves
+    written straight from the accumulators (node_tail_fwd_lean_kernel); 256 tiles or fewer park a tile's state in LDS
+    (node_tail_fwd_kernel<true, false>).  Same arithmetic per row, so a launch over 4 103 rows (257 tiles: lean) must
+    reproduce, bit for bit, what a launch over its first 4 090 rows (256 tiles, the last one partial: parked) computes."""
     from pamnet_amd import lib
     from pamnet_amd.fused import _parr, _iarr
     torch.manual_seed(5 + nblk)
-    n_big, n_small = 8200 + 7, 8000
+    LEAN_FROM_TILES = 256                                        # node_tail.hip: the lean kernel above this many row tiles
+    n_big, n_small = 4096 + 7, 4096 - 6
+    assert (n_small + 15) // 16 <= LEAN_FROM_TILES < (n_big + 15) // 16
     NW = 15
     W = [(torch.randn(D, D, device=dev) * 0.08) for _ in range(NW)]
     b = [torch.randn(D, device=dev) * 0.1 for _ in range(11)]

@@ -64,15 +64,17 @@ def grad_tol(dataset):
 GRAD_TOL = 1e-5          # gradients within 1e-5 of the reference's fp64 autograd (measured worst: 4e-7) ...
 
 
-def _check_gradients(model, p64, fwd, sd, cfg, b, report=None, head_bias_terms=None):
+def _check_gradients(model, p64, fwd, sd, cfg, b, report=None, head_bias_terms=None, p32=None):
     """Every parameter gradient of the HIP backward against the oracle's fp64 autograd (p64[k].grad already filled):
         err(hip, fp64) <= max(GRAD_TOL, 2 * err(oracle_fp32, fp64))
     -- the 1e-5 of DESIGN.md (round 6: tightened from 1e-4), never tighter than what the reference's OWN fp32 backward achieves on the same inputs
     (its sympy closed forms and the signed PDBbind pooling cancel catastrophically for a few tensors; the fp32 oracle
-    is run here to measure exactly that floor instead of hard-coding a looser bound)."""
-    p32 = {k: v.detach().clone().requires_grad_(v.is_floating_point()) for k, v in sd.items()}
-    pos, ei = getattr(b, 'pos', None), getattr(b, 'edge_index', None)
-    torch.nn.functional.l1_loss(fwd(p32, cfg, b.x, b.batch, pos, ei), b.y).backward()
+    is run here to measure exactly that floor instead of hard-coding a looser bound).  p32: that fp32 run's parameters,
+    gradients filled, when the caller has made it already (one oracle run for several runs of the model)."""
+    if p32 is None:
+        p32 = {k: v.detach().clone().requires_grad_(v.is_floating_point()) for k, v in sd.items()}
+        pos, ei = getattr(b, 'pos', None), getattr(b, 'edge_index', None)
+        torch.nn.functional.l1_loss(fwd(p32, cfg, b.x, b.batch, pos, ei), b.y).backward()
     gn = float(torch.sqrt(sum((p.grad.double() ** 2).sum() for p in model.parameters() if p.grad is not None)))
     gn64 = float(torch.sqrt(sum((p.grad ** 2).sum() for p in p64.values() if p.grad is not None)))
     gn32 = float(torch.sqrt(sum((p.grad.double() ** 2).sum() for p in p32.values() if p.grad is not None)))
@@ -674,6 +676,140 @@ def test_fused_engine_fresh_inputs_vs_oracle(dev, case):
                    inter['x_layers'].detach().numpy())
     assert ok, ('x_layers', info)
     _check_gradients(model, p64, fwd, sd, cfg, b)
+
+
+# The d = 128 layer-stack engine picks its launch plan from the batch: from its row tiles, ceil(n / 16), and its global
+# edges E_g.  The bounds, each with the function it comes from:
+PLAN_BOUNDS = {
+    'rider_tiles': 256 - 80,        # engine.hip riders_fit(): the chain launches carry riders up to RIDER_MAX_SLOTS - 80 tiles
+    'bf16_tiles': 256,              # engine.hip chain_bf16_tiles(), fuse_local_agg(): bf16x6 chains, fused local aggregation
+    'lean_from_tiles': 256,         # node_tail.hip LEAN_FROM_TILES: the lean fp32 chains above this many tiles
+    'edge_wgrad_edges': 256 * 512,  # engine.hip edge_wgrad(), edge_agg.hip agg_pp(): from this many global edges on, the
+}                                   # ping-pong edge forward and the edge backward that forms its own weight gradients
+
+
+def _launch_plan(gc):
+    """(plan, row tiles, E_g) of the batch whose graph is `gc` (model._graph_cache)."""
+    tiles, eg = (gc.n + 15) // 16, gc.glob.m
+    if tiles <= PLAN_BOUNDS['rider_tiles'] and gc.tp.m > 0:
+        plan = 'riders'
+    elif tiles > PLAN_BOUNDS['lean_from_tiles']:
+        plan = 'lean'
+    else:
+        assert tiles <= PLAN_BOUNDS['bf16_tiles']
+        plan = 'bf16x6'
+    return plan + ('+edge_wgrad' if eg >= PLAN_BOUNDS['edge_wgrad_edges'] else ''), tiles, eg
+
+
+def _qm9_batch_of(n_nodes, seed=4):
+    """A QM9-schema batch of exactly `n_nodes` atoms: whole synth.qm9_molecule(seed, i) molecules while the next one fits,
+    the rest single atoms (no bond, no edge of either kind, as in synth.ragged_qm9_batch) spread between them."""
+    from pamnet_amd import synth
+    mols, n = [], 0
+    while True:
+        m = synth.qm9_molecule(seed, len(mols))
+        if n + m['x'].shape[0] > n_nodes:
+            break
+        mols.append(m)
+        n += m['x'].shape[0]
+    singles = n_nodes - n
+    every = len(mols) // max(singles, 1)
+    graphs = []
+    for i, m in enumerate(mols):
+        if singles and i % every == 0 and i // every < singles:
+            k = i // every
+            graphs.append(dict(x=np.array([k % 5], np.float32), pos=np.zeros((1, 3), np.float32),
+                               edge_index=np.zeros((2, 0), np.int64), y=np.float32(0.25 * (k % 7) - 0.75)))
+        graphs.append(m)
+    b = synth.collate(graphs)
+    assert b.x.numel() == n_nodes and b.num_graphs == len(mols) + singles
+    return b
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case,plan', [('qm9_d128_l3_n2816', 'riders'), ('qm9_d128_l3_n2817', 'bf16x6'),
+                                       ('qm9_d128_l3_n4096', 'bf16x6'), ('qm9_d128_l3_n4097', 'lean'),
+                                       ('qm9_d128_l1_n4097', 'lean'), ('qm9s_d128_l2_n4097', 'lean'),
+                                       ('pdbbind_d128_l3_b8', 'lean+edge_wgrad')])
+def test_engine_launch_plans_vs_oracle(dev, case, plan):
+    """Every launch plan of the d = 128 layer-stack engine (PLAN_BOUNDS) against the CPU oracle, at the batches on both sides
+    of its bounds: the last batch with riders (2 816 nodes) and the first without (2 817: one row in the last tile), the
+    last batch of the bf16x6 chains and fused local aggregation (4 096) and the first of the lean chains (4 097), the
+    single-pair backward (L = 1) and PAMNet_s (pairs only) in the lean plan, and an 8-complex PDBbind batch in the plan of
+    the B = 32 step bench.py --full times (lean chains, the ping-pong edge forward, the edge backward that forms its own
+    weight gradients, init_linear, the +-1 pooling).  One oracle run (fp64 autograd; fp32 for the error floor) judges three runs of the model on the batch:
+    plain autograd (outputs, node features after every layer, every parameter gradient), train.Trainer.forward_backward
+    (the direct-gradient tape path bench.py times: every parameter gradient, none left at zero that the oracle's is not) and
+    the inference forward under no_grad, which skips the saves (outputs)."""
+    import re
+    import models
+    from oracle import pamnet_oracle as O
+    from pamnet_amd import synth, train
+    _oracle_threads()
+    small = case.startswith('qm9s')
+    n_layer = int(re.search(r'_l(\d+)_', case).group(1))
+    if case.startswith('pdbbind'):
+        cfg = models.Config(dataset='PDBbind', dim=128, n_layer=n_layer, cutoff_l=2.0, cutoff_g=6.0)
+        b = synth.collate([synth.pdbbind_complex(1, i) for i in range(8)])
+    else:
+        cfg = models.Config(dataset='QM9', dim=128, n_layer=n_layer, cutoff_l=5.0, cutoff_g=5.0)
+        b = _qm9_batch_of(int(case.rsplit('_n', 1)[1]))
+    fwd = O.pamnet_s_forward if small else O.pamnet_forward
+    sd = O.init_state_dict(cfg, seed=31, small=small)
+    pos, ei = getattr(b, 'pos', None), getattr(b, 'edge_index', None)
+    p64 = O.as_params({k: v.double() for k, v in sd.items()})
+    x64 = b.x.double() if cfg.dataset == 'PDBbind' else b.x
+    inter = {}
+    ref64 = fwd(p64, cfg, x64, b.batch, pos, ei, dtype=torch.float64, intermediates=inter)
+    torch.nn.functional.l1_loss(ref64, b.y.double()).backward()
+    p32 = O.as_params(sd)
+    ref32 = fwd(p32, cfg, b.x, b.batch, pos, ei)
+    torch.nn.functional.l1_loss(ref32, b.y).backward()
+    ref32, ref64, xl64 = ref32.detach().numpy(), ref64.detach().numpy(), inter['x_layers'].detach()
+    scale = None
+    if cfg.dataset == 'PDBbind':
+        pin = inter['pool_in'].detach().abs()
+        scale = max(float(pin[b.batch == g].sum()) for g in range(int(b.batch.max()) + 1))
+    model = (models.PAMNet_s if small else models.PAMNet)(cfg)
+    model.load_state_dict(sd, strict=True)
+    model = model.to(dev)
+    data = b.to(dev)
+    # plain autograd
+    out = model(data)
+    torch.nn.functional.l1_loss(out, data.y).backward()
+    ran, tiles, eg = _launch_plan(model._graph_cache)
+    print('%s: n = %d (%d row tiles), E_g = %d: plan %s' % (case, b.x.size(0), tiles, eg, ran))
+    assert ran == plan, (ran, tiles, eg)
+    ok, info = _ok(out.detach().cpu().numpy(), ref32, ref64, scale)
+    assert ok, ('out', info)
+    ok, info_x = _ok(torch.stack(list(model._x_layers)).detach().cpu().numpy(), xl64.float().numpy(), xl64.numpy())
+    assert ok, ('x_layers', info_x)
+    rep = {}
+    _check_gradients(model, p64, fwd, sd, cfg, b, rep, p32=p32)
+    # inference
+    with torch.no_grad():
+        out_inf = model(data).cpu().numpy()
+    assert _launch_plan(model._graph_cache)[0] == plan
+    ok, info_i = _ok(out_inf, ref32, ref64, scale)
+    assert ok, ('inference out', info_i)
+    # the trainer's tape path
+    tr = train.Trainer(model, lr=1e-4)
+    assert model._one_node()
+    tr.forward_backward(data)
+    assert _launch_plan(model._graph_cache)[0] == plan
+    used = 0
+    for k, p in model.named_parameters():
+        if p64[k].grad is None or float(p64[k].grad.abs().max()) == 0.0:
+            assert float(p.grad.abs().max()) == 0.0, k              # a parameter this branch of the model never reads
+        else:
+            assert float(p.grad.abs().max()) > 0.0, 'no gradient reached %s' % k
+            used += 1
+    assert used >= len(p64) - 2 and (cfg.dataset != 'PDBbind' or float(model.init_linear.weight.grad.abs().max()) > 0.0)
+    rep_t = {}
+    _check_gradients(model, p64, fwd, sd, cfg, b, rep_t, p32=p32)
+    print('  out %.2e (ref fp32 %.2e), x_layers %.2e (%.2e), inference out %.2e (%.2e); worst gradient: autograd %.2e '
+          '(ref fp32 %.2e, %s), trainer %.2e (ref fp32 %.2e, %s)'
+          % (info + info_x + info_i + rep['grad_worst'] + rep_t['grad_worst']))
 
 
 @pytest.mark.gpu

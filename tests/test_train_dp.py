@@ -566,11 +566,16 @@ def test_direct_tape_backward_equals_autograd(kind):
     assert torch.equal(direct, via_autograd)
 
 
+# (n_layer, n_mol, whether the batch takes the rider plan) of the test below: seed-9 QM9 batches on both sides of the rider
+# bound, engine.hip riders_fit(): ceil(n / 16) <= 256 - 80 row tiles
+_ENGINE_PLAN_CASES = [(1, 16, True), (2, 16, True), (3, 40, True), (4, 128, True), (2, 150, True), (3, 170, False)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize('n_layer,n_mol', [(1, 16), (2, 16), (3, 40), (4, 128), (2, 150), (3, 170)])
+@pytest.mark.parametrize('n_layer,n_mol', [c[:2] for c in _ENGINE_PLAN_CASES])
 def test_engine_gradients_direct_vs_plain_autograd_across_launch_plans(n_layer, n_mol):
     """The layer-stack backward picks its launch plan from the batch: riders in the chain launches and ONE weight-gradient launch
-    per layer pair when the chains leave CUs idle (ceil(n / 16) <= 176 tiles: up to ~140 QM9 molecules), per-layer launches
+    per layer pair when the chains leave CUs idle (ceil(n / 16) <= 176 tiles: up to ~155 QM9 molecules), per-layer launches
     with the tail jobs in them beyond; the last pair and n_layer = 1 have their own forms.  Whatever the plan, the gradients
     the Trainer's kernels write in place equal -- to fp32 summation order of the reductions -- those of a twin model under
     plain autograd, and both are repeatable bit for bit."""
@@ -580,6 +585,9 @@ def test_engine_gradients_direct_vs_plain_autograd_across_launch_plans(n_layer, 
     dev = torch.device('cuda:0')
     cfg = models.Config(dataset='QM9', dim=128, n_layer=n_layer, cutoff_l=5.0, cutoff_g=5.0)
     b = synth.qm9_batch(9, 0, n_mol).to(dev)
+    riders = {c[:2]: c[2] for c in _ENGINE_PLAN_CASES}
+    assert set(riders.values()) == {True, False}
+    assert ((b.x.numel() + 15) // 16 <= 256 - 80) == riders[(n_layer, n_mol)], b.x.numel()
     torch.manual_seed(n_layer * 100 + n_mol)
     model = models.PAMNet(cfg).to(dev)
     twin = models.PAMNet(cfg).to(dev)
