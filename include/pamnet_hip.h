@@ -41,7 +41,7 @@ typedef void* pamnet_stream_t; /* hipStream_t */
 
 /* Library / ABI version (bumped on any signature change).  pamnet_abi_version() returns the PAMNET_ABI_VERSION the library
  * was built against; a binding compares it with this header's (pamnet_amd/lib.py load(): a stale .so fails loudly). */
-#define PAMNET_ABI_VERSION 15
+#define PAMNET_ABI_VERSION 16
 int pamnet_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------------
@@ -360,6 +360,37 @@ int pamnet_sbf_radial_tab_f32(const float* dist, float cutoff, int64_t m, int32_
                               pamnet_stream_t stream);
 int pamnet_sbf_combine_tab_f32(const float* rad, const int32_t* idx, const float* angle, int64_t m, int32_t num_spherical,
                                int32_t num_radial, float* sbf, pamnet_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Geometric backward: d prediction / d positions (forces; the reference differentiates its geometry ops, models.py:62-66,
+ * 165-177, layers/basic.py).  Default basis only (7, 6, envelope exponent 5).  Derivatives in fp64, rounded once; zero
+ * beyond the cutoff (where the reference's envelope is cut to zero).  No atomics: fixed-order sums over CSR rows and
+ * transposed row lists, bitwise reproducible.  Every pointer is required: a null pointer or a negative count returns
+ * PAMNET_EINVAL.
+ *   pamnet_rbf_ddist_f32:  ddist[e] = sum_n grad[e, n] d/dd [env(d/c) sin(freq[n] d/c)]          (grad: [m, 16])
+ *   pamnet_sbf_bwd_f32:    gsbf [n_rows, 42] -> dangle[t] = sum_{l,n} gsbf[t, l, n] rad[idx[t], l, n] dY_l0/dtheta(angle[t]);
+ *                          ddist[e] = sum_{l,n} (sum_{t in tt row e} gsbf[t, l, n] Y_l0(angle[t])) d rad[e, l, n] / dd,
+ *                          with j_l' = j_{l-1} - (l+1)/u j_l.  tt_ptr [n_edges+1] / tt_perm [n_rows]: the rows that gather
+ *                          each edge (pamnet_triplet_transpose_*).  rad: [n_edges, 42] scratch (the forward's table).
+ *                          Rows gather edges: n_rows > 0 with n_edges == 0 returns PAMNET_EINVAL.
+ *   pamnet_pos_bwd_f32:    dpos [n, 3] from d dist_g [eg], d dist_l [el] and d angle [tp]: global CSR g_* (rows = targets,
+ *                          col = neighbour; dist = |p_row - p_col|) with its transposed list gt_*; local CSR l_* (rows = dst,
+ *                          col = src) with lt_*; triplet / pair rows t_* (row = target edge e, col = source edge e', kind 0 =
+ *                          triplet: theta = angle(p_j - p_i, p_k - p_j), kind 1 = pair: angle(p_i - p_j, p_j' - p_i)) with
+ *                          tt_*.  Where |a x b| = 0 (theta = 0 or pi) the cross-product term contributes exactly 0.
+ *                          bond_work: [el, 3] doubles of scratch.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int pamnet_rbf_ddist_f32(const float* dist, const float* freq, float cutoff, int64_t m, const float* grad, float* ddist,
+                         pamnet_stream_t stream);
+int pamnet_sbf_bwd_f32(const float* gsbf, const float* dist, float cutoff, int64_t n_edges, const int32_t* idx,
+                       const float* angle, int64_t n_rows, const int32_t* tt_ptr, const int32_t* tt_perm, float* rad,
+                       float* dangle, float* ddist, pamnet_stream_t stream);
+int pamnet_pos_bwd_f32(const float* pos, int64_t n, const int32_t* g_ptr, const int32_t* g_row, const int32_t* g_col,
+                       const int32_t* gt_ptr, const int32_t* gt_perm, const float* ddist_g, int64_t eg, const int32_t* l_ptr,
+                       const int32_t* l_row, const int32_t* l_col, const int32_t* lt_ptr, const int32_t* lt_perm,
+                       const float* ddist_l, int64_t el, const int32_t* t_ptr, const int32_t* t_row, const int32_t* t_col,
+                       const int32_t* t_kind, const int32_t* tt_ptr, const int32_t* tt_perm, const float* dangle, int64_t tp,
+                       double* bond_work, float* dpos, pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Attention fusion + per-graph pooling  (models.py:206-224)

@@ -1,0 +1,169 @@
+// Geometric backward of graph construction: gradients of the edge lengths and triplet / pair angles (models.py:65,
+// 165-177) with respect to the atom positions -- what d prediction / d pos (the negated forces) needs after the basis
+// backward (pamnet_rbf_ddist_f32, pamnet_sbf_bwd_f32) has turned the embedding input gradients into d dist / d angle.
+//
+// Every row t of the triplet / pair list angles two bond vectors.  With u_e = p[src e] - p[dst e] for local edge e, row t of
+// target edge e and source edge e' has a = u_e (triplet: p_j - p_i) or a = -u_e (pair: p_i - p_j), and b = u_e' (p_k - p_j,
+// resp. p_j' - p_i): the forward's own operands (graph.hip triplet_fill_kernel).  So the angle gradients fold into one
+// 3-vector per local edge, and the positions gather those per atom.  No atomics: every sum runs over a CSR row or a
+// transposed row list in a fixed order, so the result is bitwise the same from run to run.  Arithmetic in fp64.
+#include "common.h"
+
+namespace {
+
+struct V3 {
+    double x, y, z;
+};
+__device__ __forceinline__ V3 v3(double x, double y, double z) { return V3{x, y, z}; }
+__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
+__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
+__device__ __forceinline__ V3 operator*(double s, V3 a) { return v3(s * a.x, s * a.y, s * a.z); }
+__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+// every product rounded on its own (no fma contraction): for b = -a each component is then exactly 0, so |a x b| = 0
+// takes the exact-zero branch of angle_grads instead of a residue whose direction is noise
+__device__ __forceinline__ V3 cross(V3 a, V3 b) {
+    return v3(__dsub_rn(__dmul_rn(a.y, b.z), __dmul_rn(a.z, b.y)), __dsub_rn(__dmul_rn(a.z, b.x), __dmul_rn(a.x, b.z)),
+              __dsub_rn(__dmul_rn(a.x, b.y), __dmul_rn(a.y, b.x)));
+}
+__device__ __forceinline__ V3 load_pos(const float* __restrict__ pos, int64_t i) {
+    return v3((double)pos[3 * i], (double)pos[3 * i + 1], (double)pos[3 * i + 2]);
+}
+// u_e = p[src] - p[dst] of local edge e (loc: rows = dst, col = src)
+__device__ __forceinline__ V3 bond(const float* __restrict__ pos, const int32_t* __restrict__ l_row,
+                                   const int32_t* __restrict__ l_col, int64_t e) {
+    return load_pos(pos, l_col[e]) - load_pos(pos, l_row[e]);
+}
+
+// theta = atan2(|a x b|, a.b):  d theta / d a = (a.b (b x c) / |c| - |c| b) / s,  d theta / d b = (a.b (c x a) / |c| - |c| a) / s,
+// c = a x b, s = |c|^2 + (a.b)^2.  Where |c| = 0 (every pair row whose two bonds are the same edge: b = -a, theta = pi) the
+// cross-product term is exactly 0, as torch's norm backward makes it; s = 0 (a zero bond) gives 0 too.
+__device__ __forceinline__ void angle_grads(V3 a, V3 b, double g, V3* ga, V3* gb) {
+    const V3 c = cross(a, b);
+    const double cn = sqrt(dot(c, c)), d = dot(a, b);
+    const double s = cn * cn + d * d;
+    if (!(s > 0.0)) {
+        *ga = *gb = v3(0.0, 0.0, 0.0);
+        return;
+    }
+    const double k = g / s;
+    V3 ta = (-cn) * b, tb = (-cn) * a;
+    if (cn > 0.0) {
+        const double kc = d / cn;
+        ta = ta + kc * cross(b, c);
+        tb = tb + kc * cross(c, a);
+    }
+    *ga = k * ta;
+    *gb = k * tb;
+}
+
+// fixed-order butterfly over the 64 lanes of a wavefront (every lane ends with the same sum): deterministic
+__device__ __forceinline__ V3 wave_sum(V3 v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = v3(v.x + __shfl_xor(v.x, o, 64), v.y + __shfl_xor(v.y, o, 64), v.z + __shfl_xor(v.z, o, 64));
+    return v;
+}
+
+// One wavefront per local edge e: G_e = d/d u_e of everything that depends on u_e -- its length, the rows of e (operand a)
+// and the rows that gather e (operand b, transposed row list); the lanes stride over the rows.
+__global__ __launch_bounds__(256) void bond_grad_kernel(const float* __restrict__ pos, const int32_t* __restrict__ l_row,
+                                                        const int32_t* __restrict__ l_col, const float* __restrict__ ddist,
+                                                        int64_t el, const int32_t* __restrict__ t_ptr,
+                                                        const int32_t* __restrict__ t_row, const int32_t* __restrict__ t_col,
+                                                        const int32_t* __restrict__ t_kind, const int32_t* __restrict__ tt_ptr,
+                                                        const int32_t* __restrict__ tt_perm, const float* __restrict__ dangle,
+                                                        double* __restrict__ G) {
+    const int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (e >= el) return;                                          // (uniform over the wavefront)
+    const V3 u = bond(pos, l_row, l_col, e);
+    V3 acc = v3(0.0, 0.0, 0.0);
+    if (lane == 0) {
+        const double r = sqrt(dot(u, u));
+        if (r > 0.0) acc = ((double)ddist[e] / r) * u;
+    }
+    for (int t = t_ptr[e] + lane; t < t_ptr[e + 1]; t += 64) {   // rows of e: a = +-u_e
+        const double sg = t_kind[t] == 0 ? 1.0 : -1.0;
+        V3 ga, gb;
+        angle_grads(sg * u, bond(pos, l_row, l_col, t_col[t]), (double)dangle[t], &ga, &gb);
+        acc = acc + sg * ga;
+    }
+    for (int k = tt_ptr[e] + lane; k < tt_ptr[e + 1]; k += 64) { // rows gathering e: b = u_e
+        const int64_t t = tt_perm[k];
+        const double sg = t_kind[t] == 0 ? 1.0 : -1.0;
+        V3 ga, gb;
+        angle_grads(sg * bond(pos, l_row, l_col, t_row[t]), u, (double)dangle[t], &ga, &gb);
+        acc = acc + gb;
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) {
+        G[3 * e] = acc.x;
+        G[3 * e + 1] = acc.y;
+        G[3 * e + 2] = acc.z;
+    }
+}
+
+// One wavefront per atom a, the lanes striding over: the global edges of row a and of column a (transposed list), then the
+// bond gradients of the local edges leaving a (+G) and arriving at a (-G).
+__global__ __launch_bounds__(256) void pos_grad_kernel(const float* __restrict__ pos, int64_t n,
+                                                       const int32_t* __restrict__ g_ptr, const int32_t* __restrict__ g_row,
+                                                       const int32_t* __restrict__ g_col, const int32_t* __restrict__ gt_ptr,
+                                                       const int32_t* __restrict__ gt_perm, const float* __restrict__ ddist_g,
+                                                       const int32_t* __restrict__ l_ptr, const int32_t* __restrict__ lt_ptr,
+                                                       const int32_t* __restrict__ lt_perm, const double* __restrict__ G,
+                                                       float* __restrict__ dpos) {
+    const int64_t a = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (a >= n) return;                                           // (uniform over the wavefront)
+    const V3 pa = load_pos(pos, a);
+    V3 acc = v3(0.0, 0.0, 0.0);
+    for (int q = g_ptr[a] + lane; q < g_ptr[a + 1]; q += 64) {
+        const V3 w = pa - load_pos(pos, g_col[q]);
+        const double r = sqrt(dot(w, w));
+        if (r > 0.0) acc = acc + ((double)ddist_g[q] / r) * w;
+    }
+    for (int k = gt_ptr[a] + lane; k < gt_ptr[a + 1]; k += 64) {
+        const int64_t q = gt_perm[k];
+        const V3 w = pa - load_pos(pos, g_row[q]);
+        const double r = sqrt(dot(w, w));
+        if (r > 0.0) acc = acc + ((double)ddist_g[q] / r) * w;
+    }
+    for (int k = lt_ptr[a] + lane; k < lt_ptr[a + 1]; k += 64) {
+        const int64_t e = lt_perm[k];
+        acc = acc + v3(G[3 * e], G[3 * e + 1], G[3 * e + 2]);
+    }
+    for (int e = l_ptr[a] + lane; e < l_ptr[a + 1]; e += 64) acc = acc - v3(G[3 * e], G[3 * e + 1], G[3 * e + 2]);
+    acc = wave_sum(acc);
+    if (lane == 0) {
+        dpos[3 * a] = (float)acc.x;
+        dpos[3 * a + 1] = (float)acc.y;
+        dpos[3 * a + 2] = (float)acc.z;
+    }
+}
+
+inline unsigned blocks_for(int64_t n) { return (unsigned)(n > 0 ? ceil_div(n, 256) : 1); }
+
+}  // namespace
+
+extern "C" int pamnet_pos_bwd_f32(const float* pos, int64_t n, const int32_t* g_ptr, const int32_t* g_row,
+                                  const int32_t* g_col, const int32_t* gt_ptr, const int32_t* gt_perm, const float* ddist_g,
+                                  int64_t eg, const int32_t* l_ptr, const int32_t* l_row, const int32_t* l_col,
+                                  const int32_t* lt_ptr, const int32_t* lt_perm, const float* ddist_l, int64_t el,
+                                  const int32_t* t_ptr, const int32_t* t_row, const int32_t* t_col, const int32_t* t_kind,
+                                  const int32_t* tt_ptr, const int32_t* tt_perm, const float* dangle, int64_t tp,
+                                  double* bond_work, float* dpos, pamnet_stream_t stream) {
+    if (n < 0 || eg < 0 || el < 0 || tp < 0) return PAMNET_EINVAL;
+    if (!pos || !g_ptr || !g_row || !g_col || !gt_ptr || !gt_perm || !ddist_g || !l_ptr || !l_row || !l_col || !lt_ptr ||
+        !lt_perm || !ddist_l || !t_ptr || !t_row || !t_col || !t_kind || !tt_ptr || !tt_perm || !dangle || !bond_work || !dpos)
+        return PAMNET_EINVAL;
+    if (n == 0) return PAMNET_OK;
+    hipStream_t st = as_stream(stream);
+    if (el > 0) {
+        hipLaunchKernelGGL(bond_grad_kernel, dim3(blocks_for(el * 64)), dim3(256), 0, st, pos, l_row, l_col, ddist_l, el, t_ptr,
+                           t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, bond_work);
+        PAMNET_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(pos_grad_kernel, dim3(blocks_for(n * 64)), dim3(256), 0, st, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm,
+                       ddist_g, l_ptr, lt_ptr, lt_perm, bond_work, dpos);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}

@@ -530,14 +530,16 @@ class _PAMNetBase(nn.Module):
         idx = g.types if getattr(g, 'types', None) is not None else col.to(torch.int32).contiguous()
         if ops.type_rows_supported(self.embeddings):                                    # models.py:107,140
             direct = self.embeddings.grad if ((tape is not None or torch.is_grad_enabled()) and self.embeddings.grad is not None
-                                              and getattr(self.embeddings, '_pamnet_direct', False)) else None
+                                              and getattr(self.embeddings, '_pamnet_direct', False)
+                                              and ops.direct_allowed()) else None
             return ops.type_rows(self.embeddings, idx, direct, tape=tape)
         tr = G.Transpose(idx, self.embeddings.size(0)) if torch.is_grad_enabled() else None
         return ops.gather(self.embeddings, idx, tr.ptr if tr else None, tr.perm if tr else None)
 
     def _edge_embeddings(self, g, tape=None):
-        sbf = g.sbf                                                                          # [T+P, 42], no grad
-        if self._narrow(g.dist_g) and g.loc.m > 0 and g.glob.m > 0 and self.sbf.envelope_exponent == 5:
+        sbf = g.sbf                                           # [T+P, 42]; differentiable only with g.pos_grad
+        if (self._narrow(g.dist_g) and g.loc.m > 0 and g.glob.m > 0 and self.sbf.envelope_exponent == 5
+                and not g.pos_grad):
             # dim 16 / 32 / 64: the Bessel rows are formed inside the embedding kernels (no [E, 16] tensor either way)
             e_l = narrow.embed_rbf(g.dist_l, self.rbf_l.freq, self.cutoff_l, self.mlp_rbf_l[0][0])
             e_g = narrow.embed_rbf(g.dist_g, self.rbf_g.freq, self.cutoff_g, self.mlp_rbf_g[0][0])
@@ -562,8 +564,9 @@ class _PAMNetBase(nn.Module):
         """(x, e_l, e_g, e_sbf) of models.py:107/119/140 and 185-188 as ONE launch (two in the backward) on the dim = 128
         path: the Bessel rows are formed inside the embedding kernel from the edge lengths, the type-table rows ride along.
         lin_a (, lin_b): the sbf embedding(s) -- with lin_b, rows of g.tp_kind == 1 use lin_b.  None when not applicable."""
-        if not (self.dim == fused.D and g.sbf.is_cuda and self.sbf.default):
-            return None                               # (the one-launch input stage is built for the default basis)
+        if not (self.dim == fused.D and g.sbf.is_cuda and self.sbf.default) or g.pos_grad:
+            return None                               # (the one-launch input stage is built for the default basis and
+            #                                            computes no gradient of the edge lengths)
         lin_l, lin_g = self.mlp_rbf_l[0][0], self.mlp_rbf_g[0][0]
         layers = [(None, g.dist_l, self.cutoff_l, None, True, True), (None, g.dist_g, self.cutoff_g, None, True, True),
                   (g.sbf, None, None, g.tp_kind if lin_b is not None else None, True, True)]
@@ -611,6 +614,40 @@ class _PAMNetBase(nn.Module):
         out, node_out = ops.fuse_pool(outs, atts, g, mean=mean, tape=tape)                  # models.py:206-224
         self._graph_cache, self._node_out = g, node_out
         return out if tape is not None else out.view(-1)        # (ops._Whole hands autograd its own view)
+
+    def _positions_with_grad(self, data):
+        """The positions as fp32 [N, 3], still linked to the caller's tensor, when they require grad in grad mode (forces:
+        QM9 `data.pos`; PDBbind / RNA `data.x[:, :3]`, models.py:118,139); else None."""
+        if not torch.is_grad_enabled():
+            return None
+        if self.dataset == 'QM9':
+            src = getattr(data, 'pos', None)
+            if src is None or not src.requires_grad:
+                return None
+        else:
+            x = data.x
+            if not x.requires_grad or x.dim() != 2:
+                return None
+            src = x[:, :3]
+        if not self.sbf.default:
+            raise NotImplementedError('PAMNet: gradients with respect to the positions are implemented for the default basis '
+                                      '(num_spherical=7, num_radial=6, envelope_exponent=5) only; this model has (%d, %d, %d)'
+                                      % (self.sbf.num_spherical, self.sbf.num_radial, self.sbf.envelope_exponent))
+        return src.to(torch.float32).contiguous()
+
+    def _forward_geometry(self, data, g, pos):
+        """Forward with the geometry linked to `pos` (graph.differentiable_geometry): plain autograd, the unfused input
+        route (explicit Bessel rows, embeddings that return their input gradient), and no direct gradient writes -- so that
+        torch.autograd.grad(E, pos) leaves every p.grad as it was (ops.no_direct_writes)."""
+        with ops.no_direct_writes():
+            out = self._forward_on(data, G.differentiable_geometry(g, pos, self.cutoff_l), None)
+        # the inspection hooks keep the plain graph and detached layer outputs: a dropped E frees its autograd graph
+        self._graph_cache = g
+        if isinstance(self._x_layers, _LazyLayers):
+            self._x_layers = _LazyLayers(self._x_layers._args[0], g, *self._x_layers._args[2:])
+        else:
+            self._x_layers = [x.detach() for x in self._x_layers]
+        return out
 
     def _one_node(self):
         """Training forward with preallocated gradients (train.FlatParams) on the fused dim = 128 path or the narrow-width
@@ -735,6 +772,9 @@ class PAMNet(_PAMNetBase):
     def _forward(self, data):
         self._release_inspection()
         g = self._graph(data)
+        pos = self._positions_with_grad(data)
+        if pos is not None:
+            return self._forward_geometry(data, g, pos)
         if self._one_node():
             return self._run_one_node(lambda tape: self._forward_on(data, g, tape))
         return self._forward_on(data, g, None)
@@ -782,6 +822,9 @@ class PAMNet_s(_PAMNetBase):
     def _forward(self, data):
         self._release_inspection()
         g = self._graph(data)
+        pos = self._positions_with_grad(data)
+        if pos is not None:
+            return self._forward_geometry(data, g, pos)
         if self._one_node():
             return self._run_one_node(lambda tape: self._forward_on(data, g, tape))
         return self._forward_on(data, g, None)

@@ -11,7 +11,7 @@ import ctypes
 import torch
 
 from . import lib
-from .ops import apply as _apply, gather_mul_raw, segment_sum_raw
+from .ops import apply as _apply, direct_allowed, embed_input_grad, gather_mul_raw, segment_sum_raw
 
 D = 128
 
@@ -62,10 +62,19 @@ def alloc_like_grouped(params, groups=None):
     return out, ptrs
 
 
+class _NoDirect(list):
+    """Parameter list of a forward that ran under ops.no_direct_writes: its backward never writes in place."""
+
+
+def _plist(plist):
+    """The forward's decision (ctx.plist): direct writes allowed, or not (ops.no_direct_writes)."""
+    return plist if direct_allowed() else _NoDirect(plist)
+
+
 def _grad_buffers(params):
     """(direct, buffers): where the gradients of `params` (a list of Parameters / tensors) are written."""
-    if all(getattr(p, '_pamnet_direct', False) and getattr(p, 'grad', None) is not None
-           and p.grad.is_contiguous() for p in params):
+    if type(params) is not _NoDirect and all(getattr(p, '_pamnet_direct', False) and getattr(p, 'grad', None) is not None
+                                             and p.grad.is_contiguous() for p in params):
         return True, [p.grad for p in params]
     return False, alloc_like_grouped(params)[0]
 
@@ -190,7 +199,7 @@ class _NodeTail(torch.autograd.Function):
         x2, res_x = x2.contiguous(), res_x.contiguous()
         Z, R, x_out, out, att = k_tail_fwd(x2, res_x, tp)
         ctx.save_for_backward(x2, Z, R, x_out, *tp)
-        ctx.plist = plist
+        ctx.plist = _plist(plist)
         return x_out, out, att
 
     @staticmethod
@@ -225,7 +234,7 @@ class _Embed(torch.autograd.Function):
                  lib.ptr(b1), 1 if act else 0, lib.ptr(out), lib.stream_of(out))
         ctx.save_for_backward(x, kind, *[p for p in params if p is not None])
         ctx.layout = [p is not None for p in params]
-        ctx.act, ctx.plist, ctx.need_dx = act, plist, bool(ctx.needs_input_grad and ctx.needs_input_grad[0])
+        ctx.act, ctx.plist, ctx.need_dx = act, _plist(plist), bool(ctx.needs_input_grad and ctx.needs_input_grad[0])
         return out
 
     @staticmethod
@@ -243,13 +252,18 @@ class _Embed(torch.autograd.Function):
         need = ctypes.c_int64(0)
         lib.call('pamnet_embed_scratch_floats', rows, K, ctypes.addressof(need))
         partial = _empty(int(need.value), like=gout)
-        dx = _empty(rows, K, like=gout) if ctx.need_dx else None
+        dx_rows = None
+        if ctx.need_dx and (kind is not None or K != 16):
+            # the kernel forms the input gradient of the single-set K = 16 layer only: the 42-wide spherical-basis rows and
+            # the 18-wide PDBbind features (positions that require grad) take the any-width GEMM kernels
+            dx_rows = embed_input_grad(x, gout, kind, ((W0, b0), (W1, b1)) if W1 is not None else ((W0, b0),), ctx.act)
+        dx = _empty(rows, K, like=gout) if (ctx.need_dx and dx_rows is None) else None
         lib.call('pamnet_embed_bwd_f32', lib.ptr(x), rows, K, lib.ptr(kind), lib.ptr(W0), lib.ptr(b0), lib.ptr(W1),
                  lib.ptr(b1), 1 if ctx.act else 0, lib.ptr(gout), lib.ptr(gp[0]), lib.ptr(gp[1]),
                  lib.ptr(gp[2]) if len(gp) > 2 else None, lib.ptr(gp[3]) if len(gp) > 3 else None, lib.ptr(dx),
                  lib.ptr(partial), lib.stream_of(gout))
         grads = tuple(None if (direct or has is False) else gp[i] for i, has in enumerate(ctx.layout))
-        return (dx, None, None, None) + grads
+        return (dx if dx_rows is None else dx_rows, None, None, None) + grads
 
 
 def embed(x, lin0, lin1=None, kind=None, act=True, tape=None, need_dx=False):
@@ -317,7 +331,7 @@ class _InputStage(torch.autograd.Function):
         lib.call('pamnet_embed_multi_fwd_f32', ctypes.addressof(jobs), n, ctypes.addressof(tj) if tj is not None else None,
                  lib.stream_of(ref))
         ctx.save_for_backward(*params)
-        ctx.spec, ctx.plist = spec, plist
+        ctx.spec, ctx.plist = spec, _plist(plist)
         return tuple(outs)
 
     @staticmethod
@@ -391,7 +405,7 @@ class _GlobalLayer(torch.autograd.Function):
                  lib.ptr(z), lib.ptr(ea), lib.ptr(x2), st)
         Z, R, x_out, out, att = k_tail_fwd(x2, x, tp)
         ctx.save_for_backward(x, e, Zx1, z, ea, x2, Z, R, x_out, *params)
-        ctx.graph, ctx.plist = graph, plist
+        ctx.graph, ctx.plist = graph, _plist(plist)
         return x_out, out, att
 
     @staticmethod
@@ -462,7 +476,7 @@ class _LocalLayer(torch.autograd.Function):
                  lib.ptr(tpc.col), lib.ptr(loc.ptr), lib.ptr(x1), n, lib.ptr(m_t), lib.ptr(x2), st)
         Z, R, x_out, out, att = k_tail_fwd(x2, x, tp)
         ctx.save_for_backward(x, rbf, sbf, Zx1, z_ji, z_kj, q2, q3, m_nb, s, m_t, z1, z2, x2, Z, R, x_out, *params)
-        ctx.graph, ctx.plist = graph, plist
+        ctx.graph, ctx.plist = graph, _plist(plist)
         return x_out, out, att
 
     @staticmethod

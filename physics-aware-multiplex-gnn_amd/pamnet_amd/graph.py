@@ -192,6 +192,7 @@ class Graph(object):
     """All index / geometry tensors one forward needs (int32 / fp32 on the device)."""
 
     capped = False        # max_num_neighbors cut a row of the radius graph: not symmetric, general transposes (build_graph)
+    pos_grad = False      # geometry linked to positions that require grad (differentiable_geometry)
 
     # Row lists / counts per kind are only needed by the generic (non-fused) path and by tests: built on first use so
     # the fused path (which selects weights per row from `tp_kind` inside the kernel) pays no host sync for them.
@@ -1001,3 +1002,98 @@ def spherical_basis(g, cutoff_l):
     sbf = torch.empty((tot, 42), dtype=torch.float32, device=dev)
     lib.call('pamnet_sbf_combine_f32', lib.ptr(rad), lib.ptr(g.tp.col), lib.ptr(g.tp_angle), tot, lib.ptr(sbf), st)
     return sbf
+
+
+# ---- differentiable geometry: forces (d prediction / d positions) ------------------------------------------------------
+_SECOND_ORDER = ('PAMNet: second derivatives through the positions are not supported (the kernels\' backward passes are not '
+                 'themselves differentiable): torch.autograd.grad(..., create_graph=True) cannot give forces with a grad_fn')
+
+
+def _index_lists(g):
+    """The index tensors of `g` that pamnet_pos_bwd_f32 reads, with the sizes.  The geometry Functions keep these on ctx, not
+    the graph: the graph object is where their outputs end up, and ctx -> graph -> output -> node would be a cycle."""
+    glob, loc, tp = g.glob, g.loc, g.tp
+    return (g.n, glob.ptr, glob.row_of, glob.col, g.glob_T.ptr, g.glob_T.perm, glob.m, loc.ptr, loc.row_of, loc.col,
+            g.loc_T.ptr, g.loc_T.perm, loc.m, tp.ptr, tp.row_of, tp.col, g.tp_kind, g.tp_T.ptr, g.tp_T.perm, tp.m)
+
+
+class _Geometry(torch.autograd.Function):
+    """pos [N, 3] -> (dist_g, dist_l, tp_angle) of a graph built from these positions (models.py:62-66,165-177).  The
+    forward hands out the values graph construction already computed; the backward is pamnet_pos_bwd_f32.  Everything
+    the backward reads is kept (pos through save_for_backward, so an in-place change of it is caught): a graph that is
+    retained can be walked again."""
+
+    @staticmethod
+    def forward(ctx, pos, g):
+        ctx.save_for_backward(pos)
+        ctx.idx = _index_lists(g)
+        return g.dist_g.clone(), g.dist_l.clone(), g.tp_angle.clone()
+
+    @staticmethod
+    def backward(ctx, d_dg, d_dl, d_ang):
+        if torch.is_grad_enabled():
+            raise RuntimeError(_SECOND_ORDER)
+        pos, = ctx.saved_tensors
+        (n, g_ptr, g_row, g_col, gt_ptr, gt_perm, eg, l_ptr, l_row, l_col, lt_ptr, lt_perm, el, t_ptr, t_row, t_col, t_kind,
+         tt_ptr, tt_perm, tp) = ctx.idx
+        pos = pos.contiguous()
+        d_dg, d_dl, d_ang = d_dg.contiguous(), d_dl.contiguous(), d_ang.contiguous()
+        work = torch.empty(3 * max(el, 1), dtype=torch.float64, device=pos.device)
+        dpos = torch.empty((n, 3), dtype=torch.float32, device=pos.device)
+        lib.call('pamnet_pos_bwd_f32', lib.ptr(pos), n, lib.ptr(g_ptr), lib.ptr(g_row), lib.ptr(g_col), lib.ptr(gt_ptr),
+                 lib.ptr(gt_perm), lib.ptr(d_dg), eg, lib.ptr(l_ptr), lib.ptr(l_row), lib.ptr(l_col), lib.ptr(lt_ptr),
+                 lib.ptr(lt_perm), lib.ptr(d_dl), el, lib.ptr(t_ptr), lib.ptr(t_row), lib.ptr(t_col), lib.ptr(t_kind),
+                 lib.ptr(tt_ptr), lib.ptr(tt_perm), lib.ptr(d_ang), tp, lib.ptr(work), lib.ptr(dpos), lib.stream_of(pos))
+        return dpos, None
+
+
+class _SphericalBasis(torch.autograd.Function):
+    """(dist_l, tp_angle) -> the default spherical basis rows [T+P, 42] (layers/basic.py:107-116).  The forward hands out
+    the rows graph construction / spherical_basis already formed; the backward is pamnet_sbf_bwd_f32 (inputs through
+    save_for_backward, index lists on ctx: see _Geometry)."""
+
+    @staticmethod
+    def forward(ctx, dist_l, angle, g, cutoff_l, sbf):
+        ctx.save_for_backward(dist_l, angle)
+        ctx.idx = (g.tp.col, g.tp_T.ptr, g.tp_T.perm, g.loc.m, g.tp.m)
+        ctx.cutoff = float(cutoff_l)
+        return sbf.clone()
+
+    @staticmethod
+    def backward(ctx, gs):
+        if torch.is_grad_enabled():
+            raise RuntimeError(_SECOND_ORDER)
+        dist_l, angle = ctx.saved_tensors
+        t_col, tt_ptr, tt_perm, e_l, tot = ctx.idx
+        gs = gs.contiguous()
+        rad = torch.empty(max(e_l, 1) * 42, dtype=torch.float32, device=gs.device)
+        dangle, ddist = torch.empty_like(angle), torch.empty_like(dist_l)
+        lib.call('pamnet_sbf_bwd_f32', lib.ptr(gs), lib.ptr(dist_l), ctx.cutoff, e_l, lib.ptr(t_col), lib.ptr(angle), tot,
+                 lib.ptr(tt_ptr), lib.ptr(tt_perm), lib.ptr(rad), lib.ptr(dangle), lib.ptr(ddist), lib.stream_of(gs))
+        return ddist, dangle, None, None, None
+
+
+class _DiffGraph(object):
+    """Graph `g` seen with its geometry replaced by differentiable tensors (differentiable_geometry); every other attribute
+    is g's own.  g itself keeps the plain tensors, so what caches it (models: the inspection hooks) holds no autograd
+    graph."""
+
+    pos_grad = True
+
+    def __init__(self, g, **geometry):
+        self.__dict__.update(geometry)
+        self.__dict__['_plain'] = g
+
+    def __getattr__(self, name):
+        return getattr(self.__dict__['_plain'], name)
+
+
+def differentiable_geometry(g, pos, cutoff_l):
+    """Graph `g` (built from `pos`, fp32 [N, 3], with the backward index lists: need_grad) seen with its geometry linked to
+    `pos`: dist_g, dist_l, tp_angle and the default-basis rows sbf are outputs of autograd Functions whose backward passes
+    are HIP kernels.  Values are unchanged (the same tensors' contents); `g` itself is not modified."""
+    if g.glob_T is _NoTranspose or g.loc_T is _NoTranspose or g.tp_T is _NoTranspose:
+        raise RuntimeError('differentiable geometry needs a graph built with need_grad=True')
+    dist_g, dist_l, angle = _Geometry.apply(pos, g)
+    sbf = _SphericalBasis.apply(dist_l, angle, g, cutoff_l, g.sbf)
+    return _DiffGraph(g, dist_g=dist_g, dist_l=dist_l, tp_angle=angle, sbf=sbf)

@@ -373,8 +373,11 @@ class _Embed(torch.autograd.Function):
             z = [torch.zeros_like(wa), torch.zeros_like(ba)] + ([torch.zeros_like(wb), torch.zeros_like(bb)] if two else [None, None])
             return (torch.zeros_like(f) if ctx.needs_input_grad[0] else None), None, z[0], z[1], z[2], z[3]
         need_df = ctx.needs_input_grad[0]
+        df_rows = None
         if need_df and (k != 16 or two):
-            raise RuntimeError('narrow embed: input gradient only for the 16-wide single-set embedding')
+            # the spherical-basis rows' gradient (positions that require grad): the embed kernel writes df for the 16-wide
+            # single-set form only
+            df_rows, need_df = ops.embed_input_grad(f, g, kind, ((wa, ba), (wb, bb)) if two else ((wa, ba),)), False
         df = _empty(m, k, like=g) if need_df else None
         kp = 16 if k == 16 else 48
         partial = _empty(_blocks(m), sets * (d * kp + d), like=g)
@@ -382,7 +385,7 @@ class _Embed(torch.autograd.Function):
         lib.call('pamnet_narrow_embed_bwd_f32', lib.ptr(f), m, k, d, lib.ptr(kind) if two else None, lib.ptr(wa),
                  lib.ptr(ba), lib.ptr(wb) if two else None, lib.ptr(bb) if two else None, lib.ptr(g), lib.ptr(df),
                  lib.ptr(partial), lib.ptr(dw), lib.ptr(db), lib.stream_of(g))
-        return df, None, dw[0], db[0], (dw[1] if two else None), (db[1] if two else None)
+        return (df if df_rows is None else df_rows), None, dw[0], db[0], (dw[1] if two else None), (db[1] if two else None)
 
 
 class _EmbedRbf(torch.autograd.Function):

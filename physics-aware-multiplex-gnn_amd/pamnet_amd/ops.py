@@ -50,6 +50,22 @@ def current_tape():
     return st[-1] if st else None
 
 
+class no_direct_writes(object):
+    """Context of a forward whose geometry is differentiable (forces): its Functions decide, at forward time, that their
+    backward returns parameter gradients to autograd instead of writing them into `_pamnet_direct` buffers -- so that
+    torch.autograd.grad(E, pos) leaves every p.grad untouched (fused._grad_buffers, stack.layer_stack, models._embed)."""
+
+    def __enter__(self):
+        _tls.no_direct = getattr(_tls, 'no_direct', 0) + 1
+
+    def __exit__(self, *exc):
+        _tls.no_direct -= 1
+
+
+def direct_allowed():
+    return not getattr(_tls, 'no_direct', 0)
+
+
 def apply(fn, *args, tape=None):
     """fn.apply(*args) under autograd; straight fn.forward without a tape in no-grad mode; or -- inside a forward that is
     being recorded as ONE autograd node (see Tape) -- a call on that tape."""
@@ -350,7 +366,8 @@ def sumsq_partials(flat):
 
 
 class _RBF(torch.autograd.Function):
-    """BesselBasisLayer (layers/basic.py:59-76); freq is trainable, dist is not differentiated (pos has no grad)."""
+    """BesselBasisLayer (layers/basic.py:59-76); freq is trainable; dist is differentiated when it requires grad (positions
+    that require grad: graph.differentiable_geometry; default envelope only)."""
 
     @staticmethod
     def forward(ctx, dist, freq, cutoff, exponent=5):
@@ -378,7 +395,14 @@ class _RBF(torch.autograd.Function):
         else:
             lib.call('pamnet_rbf_bwd_env_f32', lib.ptr(dist), lib.ptr(_c(freq)), ctx.cutoff, ctx.exponent, dist.numel(),
                      lib.ptr(g), lib.ptr(dfreq), lib.ptr(partial), lib.stream_of(g))
-        return None, dfreq, None, None
+        ddist = None
+        if ctx.needs_input_grad[0]:
+            if ctx.exponent != 5:
+                raise NotImplementedError('d rbf / d dist: default envelope exponent (5) only')
+            ddist = torch.empty_like(dist)
+            lib.call('pamnet_rbf_ddist_f32', lib.ptr(dist), lib.ptr(_c(freq)), ctx.cutoff, dist.numel(), lib.ptr(g),
+                     lib.ptr(ddist), lib.stream_of(g))
+        return ddist, dfreq, None, None
 
 
 class _FusePool(torch.autograd.Function):
@@ -444,6 +468,23 @@ def _dense_bwd(g, z, x, w, act, need_dx, need_dw, need_db):
     return dx, dw, db
 
 
+def embed_input_grad(x, g, kind, sets, act=True):
+    """d x of act(x W_kind^T + b_kind) for the input embeddings whose kernels form no input gradient at that shape (the
+    42-wide spherical-basis rows, the 18-wide PDBbind features; needed only when positions require grad): per weight set
+    (W, b), z is formed again and (g restricted to the set's rows, times SiLU'(z)) W runs on the any-width GEMM kernels.
+    kind: int32 [rows] or None; rows of kind 0 use sets[0], the others sets[1]."""
+    x = _c(x)
+    dx = None
+    zero = torch.zeros((), dtype=g.dtype, device=g.device)
+    for s, (w, b) in enumerate(sets):
+        w = _c(w)
+        z = _dense_fwd(x, w, _c(b) if b is not None else None, True, True)[1] if act else None
+        gs = g if kind is None else _c(torch.where(((kind == 0) if s == 0 else (kind != 0)).unsqueeze(1), g, zero))
+        d = _dense_bwd(gs, z, x, w, act, True, False, False)[0]
+        dx = d if dx is None else dx + d
+    return dx
+
+
 class _Dense(torch.autograd.Function):
     """act(x W^T + b) for a width no engine is built for (hidden sizes above 128, models.py:25; the thin bias-free
     `init_linear` of the PDBbind branch, models.py:119, at such a dim): csrc/dense.hip -- fp32-accurate GEMMs on the bf16
@@ -481,12 +522,14 @@ class _DenseAct(torch.autograd.Function):
     """SiLU(x W_kind^T + b_kind) for an input width no embedding kernel is built for (the spherical-basis embedding with a
     non-default num_spherical * num_radial, models.py:187-188) on csrc/dense.hip.  `kind` (int32 [rows], nullable): rows of
     kind 0 use (wa, ba), the others (wb, bb) -- both layers run over all rows and a row keeps its own (the second set is
-    the pairs' embedding of the small model: same rows, other weights).  The input carries no gradient (geometry only)."""
+    the pairs' embedding of the small model: same rows, other weights).  The input's gradient is computed when it is
+    needed (positions that require grad)."""
 
     @staticmethod
     def forward(ctx, x, kind, wa, ba, wb, bb):
         x = _c(x)
         keep = any(ctx.needs_input_grad)
+        ctx.w = (_c(wa), _c(wb) if wb is not None else None) if (keep and ctx.needs_input_grad[0]) else None
         ya, za = _dense_fwd(x, _c(wa), _c(ba), True, keep)
         if kind is None:
             ctx.save_for_backward(x, za, None, None)
@@ -500,13 +543,15 @@ class _DenseAct(torch.autograd.Function):
     def backward(ctx, g):
         x, za, zb, mask = ctx.saved_tensors
         g = _c(g)
+        ndx = bool(ctx.needs_input_grad[0])
+        wa, wb = (ctx.w if ndx else (None, None))
         if mask is None:
-            _, dwa, dba = _dense_bwd(g, za, x, None, True, False, True, True)
-            return None, None, dwa, dba, None, None
+            dx, dwa, dba = _dense_bwd(g, za, x, wa, True, ndx, True, True)
+            return dx, None, dwa, dba, None, None
         zero = torch.zeros((), dtype=g.dtype, device=g.device)
-        _, dwa, dba = _dense_bwd(torch.where(mask, g, zero), za, x, None, True, False, True, True)
-        _, dwb, dbb = _dense_bwd(torch.where(mask, zero, g), zb, x, None, True, False, True, True)
-        return None, None, dwa, dba, dwb, dbb
+        dxa, dwa, dba = _dense_bwd(torch.where(mask, g, zero), za, x, wa, True, ndx, True, True)
+        dxb, dwb, dbb = _dense_bwd(torch.where(mask, zero, g), zb, x, wb, True, ndx, True, True)
+        return (dxa + dxb if ndx else None), None, dwa, dba, dwb, dbb
 
 
 def dense_act(x, lin_a, lin_b=None, kind=None, tape=None):

@@ -10,7 +10,7 @@ import torch
 
 from . import lib, narrow
 from .fused import D, _empty, _iarr, _parr, alloc_like_grouped, tail_params
-from .ops import apply as _apply
+from .ops import apply as _apply, direct_allowed
 
 
 class StackCtx(object):
@@ -218,7 +218,7 @@ def layer_stack(global_layers, local_layers, x0, e_g, rbf_e, e_sbf, graph, tape=
     save = torch.is_grad_enabled()
     if tape is not None:                       # direct-gradient mode on the model's own tape (ops.Tape)
         return tape.call(_Stack, x0, e_g, rbf_e, e_sbf, graph, plan, True, True)
-    if save and plan.direct():
+    if save and direct_allowed() and plan.direct():
         return _Stack.apply(x0, e_g, rbf_e, e_sbf, graph, plan, True, True)
     if not save:
         # forward-only: no autograd node (handing ~400 parameters to Function.apply costs ~0.1 ms of host time per
