@@ -550,8 +550,9 @@ int pamnet_wgrad_deferred_f32(int64_t njobs, const float* const* dZ, const int64
 int pamnet_wgrad_flush_f32(void* ctx /* host */, pamnet_stream_t stream);
 /* Riders: weight-gradient slots as extra workgroups of a node-chain backward launch (the chain owns ceil(n/16) workgroups,
  * 143 of the 256 CUs at the QM9 batch; the riders take the idle CUs and the layer's own weight-gradient launch shrinks).
- *   pamnet_wgrad_rider_plan_f32   : lay a batch (<= 12 jobs) out over <= max_slots slots; the plan goes to `rider`
- *                                   (caller-owned HOST memory of pamnet_wgrad_rider_bytes bytes); *slots_out = slots used
+ *   pamnet_wgrad_rider_plan_f32   : lay a batch (<= 16 jobs) out over njobs <= *slots_out <= max_slots slots (rows per slot: 256,
+ *                                   growing in steps of 64 until the batch fits; max_slots < njobs: PAMNET_EINVAL); the plan
+ *                                   goes to `rider` (caller-owned HOST memory of pamnet_wgrad_rider_bytes bytes)
  *   pamnet_node_pre_tail_bwd_f32  : takes the plan (`rider` argument) and appends the slots to its grid
  *   pamnet_wgrad_rider_enqueue_f32: registers the batch with a deferred context so that the next pamnet_wgrad_deferred_f32
  *                                   launch (or the flush) reduces its slots in the usual fixed order.  A second rider batch

@@ -53,13 +53,30 @@ constexpr int64_t rider_rows() { return 256; }
 // smallest chunk a plan may use (scratch is sized for it)
 constexpr int MIN_ROWS_PER_WG = 128;
 constexpr int64_t first_rows() { return ROWS_PER_WG < MIN_ROWS_PER_WG ? MIN_ROWS_PER_WG : ROWS_PER_WG; }
-inline int64_t plan_chunk(int64_t njobs, const int64_t* rows, int64_t max_slots, int64_t first_chunk = 0) {
+inline int64_t batch_slots(int64_t njobs, const int64_t* rows, int64_t chunk) {
+    int64_t slots = 0;
+    for (int64_t j = 0; j < njobs; ++j) slots += job_slots(rows[j], chunk);
+    return slots;
+}
+// max_slots is a TARGET for the stand-alone launches (the chunk stops growing at 16 384 rows: a batch that large runs several
+// rounds anyway) and a BOUND when `hard` (a rider plan: the caller sizes a grid from it; max_slots >= njobs, so a chunk that
+// fits exists -- one slot per job).  Either way the result is the smallest multiple of 64 from the first chunk on that fits.
+inline int64_t plan_chunk(int64_t njobs, const int64_t* rows, int64_t max_slots, int64_t first_chunk = 0, bool hard = false) {
     int64_t chunk = first_chunk > 0 ? first_chunk : first_rows();
-    for (;; chunk += RB) {
-        int64_t slots = 0;
-        for (int64_t j = 0; j < njobs; ++j) slots += job_slots(rows[j], chunk);
-        if (slots <= max_slots || chunk >= 16384) return chunk;
+    for (;; chunk += RB)
+        if (batch_slots(njobs, rows, chunk) <= max_slots) return chunk;
+        else if (chunk >= 16384) break;
+    if (!hard) return chunk;
+    // beyond the cap: slots fall monotonically with the chunk, so bisect over the multiples of 64 (a 10^7-row job in one slot
+    // would otherwise take 156 000 steps of the scan)
+    int64_t lo = chunk, hi = 2 * chunk;                        // lo does not fit
+    while (batch_slots(njobs, rows, hi) > max_slots) lo = hi, hi *= 2;
+    while (hi - lo > RB) {
+        const int64_t mid = lo + (hi - lo) / (2 * RB) * RB;
+        if (batch_slots(njobs, rows, mid) <= max_slots) hi = mid;
+        else lo = mid;
     }
+    return hi;
 }
 
 // Slot workgroups: 4 waves, one per SIMD, <= 256 registers each, so that a second workgroup -- the small reductions of the
@@ -260,10 +277,11 @@ struct WgradPending {
 template <typename Batch>
 inline int build_batch(Batch& b, int64_t njobs, const float* const* dZ, const int64_t* ld_dz, const float* const* A,
                        const int64_t* ld_a, const int32_t* a_mode, const int64_t* rows, float* const* dW,
-                       const int64_t* ld_dw, float* const* db, int64_t max_slots, int64_t first_chunk = 0) {
+                       const int64_t* ld_dw, float* const* db, int64_t max_slots, int64_t first_chunk = 0,
+                       bool hard = false) {
     b.njobs = (int)njobs;
     b.start[0] = 0;
-    const int64_t chunk = plan_chunk(njobs, rows, max_slots, first_chunk);
+    const int64_t chunk = plan_chunk(njobs, rows, max_slots, first_chunk, hard);
     for (int j = 0; j < njobs; ++j) {
         if (!dZ[j] || !A[j] || !dW[j]) return PAMNET_ENULL;
         b.job[j] = WJob{dZ[j], A[j], dW[j], db[j], rows[j], (int)ld_dz[j], (int)ld_a[j], (int)ld_dw[j], a_mode[j]};
@@ -406,7 +424,8 @@ extern "C" int pamnet_wgrad_flush_f32(void* ctx, pamnet_stream_t stream) {
 }
 
 // ---- riders: slots of a batch that run as extra workgroups of a node-chain backward launch -----------------------------
-// pamnet_wgrad_rider_plan_f32 lays a batch (<= 12 jobs) out over <= max_slots slots and stores the plan in `rider`
+// pamnet_wgrad_rider_plan_f32 lays a batch (<= 16 jobs) out over <= max_slots slots (max_slots >= njobs: the rows per slot
+// grow from 256 in steps of 64 until the batch fits) and stores the plan in `rider`
 // (caller-owned host memory, pamnet_wgrad_rider_bytes); pamnet_node_pre_tail_bwd_f32 takes the plan and appends the
 // slots to its grid; pamnet_wgrad_rider_enqueue_f32 then registers the batch with `ctx` so that the next deferred launch
 // (or the flush) reduces its slots.  *slots_out = workgroups the plan adds.
@@ -423,7 +442,8 @@ extern "C" int pamnet_wgrad_rider_plan_f32(int64_t njobs, const float* const* dZ
     if (njobs < 1 || njobs > MAXJ_S || max_slots < njobs) return PAMNET_EINVAL;
     if (!dZ || !ld_dz || !A || !ld_a || !a_mode || !rows || !dW || !ld_dw || !db || !partial || !rider) return PAMNET_ENULL;
     WgradRider* r = static_cast<WgradRider*>(rider);
-    const int rc = build_batch(r->batch, njobs, dZ, ld_dz, A, ld_a, a_mode, rows, dW, ld_dw, db, max_slots, rider_rows());
+    const int rc = build_batch(r->batch, njobs, dZ, ld_dz, A, ld_a, a_mode, rows, dW, ld_dw, db, max_slots, rider_rows(),
+                               /*hard=*/true);
     if (rc) return rc;
     r->partial = partial;
     r->slots = r->batch.start[njobs];
