@@ -29,7 +29,12 @@ from pamnet_amd.train import Trainer, WarmupExpLR, shard_range  # noqa: E402
 def run_target(args, cfg, target, dev, world, rank):
     """The body of main_qm9.py:84-132 for one target."""
     model = (PAMNet if args.model == 'PAMNet' else PAMNet_s)(cfg).to(dev)
-    trainer = Trainer(model, lr=args.lr, weight_decay=args.wd, ema_decay=0.999, max_grad_norm=1000.0, world_size=world)
+    # --freeze N: the embeddings and the first N layer pairs keep their values (fine-tuning); --accumulate K: one update per K
+    # batches, on the mean over all of them (both default to the reference's recipe)
+    groups = [{'params': ['embeddings'] + ['%s.%d.*' % (s, k) for k in range(args.freeze) for s in ('global_layer', 'local_layer')],
+               'frozen': True}] if args.freeze > 0 else None
+    trainer = Trainer(model, lr=args.lr, weight_decay=args.wd, ema_decay=0.999, max_grad_norm=1000.0, world_size=world,
+                      param_groups=groups, accumulate=args.accumulate)
     if rank == 0:
         print('Target %d. Number of model parameters: ' % target, sum(v.numel() for v in model.state_dict().values()))    # (the reference's shapes: a dim without a kernel family of its own is held zero-padded)
     gb = args.batch_size
@@ -72,7 +77,8 @@ def run_target(args, cfg, target, dev, world, rank):
         for step in range(steps_per_epoch):
             data, nxt = nxt, (train_batch(step + 1, epoch) if step + 1 < steps_per_epoch else None)
             # the LR the reference's optimiser has AT this step (scheduler stepped after optimizer.step, main_qm9.py:112-114)
-            loss = trainer.step(data, lr=sched.lr_for_step(epoch, step, steps_per_epoch), global_graphs=gb, next_data=nxt)
+            loss = trainer.step(data, lr=sched.lr_for_step(epoch, step, steps_per_epoch), global_graphs=gb * args.accumulate,
+                                next_data=nxt)
             loss_sum += loss.detach() * data.num_graphs
         if world > 1:
             dist.all_reduce(loss_sum)
@@ -105,6 +111,9 @@ def main():
     ap.add_argument('--target', default='7', help="index of the target (0-11; 7-10 read label columns 12-15 as in "
                     "main_qm9.py:60-66), or 'all': the 12 targets one after the other (BASELINE configs[2])")
     ap.add_argument('--save', default='')
+    ap.add_argument('--freeze', type=int, default=0, help='freeze the embeddings and the first N layer pairs')
+    ap.add_argument('--accumulate', type=int, default=1, help='batches per optimiser update (gradient accumulation); when the steps of an epoch are not a multiple of it, the '
+                    'last partial sum carries over the evaluation into the next epoch\'s first update')
     ap.add_argument('--resident', action='store_true', help='keep the training set on the device and collate batches there '
                     '(pamnet_amd.store.MoleculeStore): no device->host read per step; shuffled every epoch')
     args = ap.parse_args()

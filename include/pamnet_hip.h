@@ -41,7 +41,7 @@ typedef void* pamnet_stream_t; /* hipStream_t */
 
 /* Library / ABI version (bumped on any signature change).  pamnet_abi_version() returns the PAMNET_ABI_VERSION the library
  * was built against; a binding compares it with this header's (pamnet_amd/lib.py load(): a stale .so fails loudly). */
-#define PAMNET_ABI_VERSION 16
+#define PAMNET_ABI_VERSION 17
 int pamnet_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------------
@@ -813,6 +813,21 @@ int pamnet_smooth_l1_loss_f32(const float* out, const float* y, int64_t n, float
                               pamnet_stream_t stream);
 int pamnet_type_rows_grad_f32(const float* g, const int32_t* idx, int64_t n, int64_t n_types, int64_t d, void* scratch,
                               float* out, pamnet_stream_t stream);
+/* Chunked forms for parameter groups (pamnet_adam_ema_groups_f32 below).  chunk_group[c] (device, one byte per chunk of 64
+ * floats, n / 64 entries) is the group of g[64 c : 64 c + 64]; frozen[0:n_groups] is a HOST array, 1 <= n_groups <=
+ * PAMNET_MAX_PARAM_GROUPS; n % 64 == 0.
+ *   pamnet_sumsq_partials_masked_f32 : pamnet_sumsq_partials_f32 where chunks of a frozen group contribute nothing (same 256
+ *                                      slices, same order: with no frozen group the partials are bit for bit the unmasked ones)
+ *   pamnet_grad_accumulate_f32       : acc[0:n] += g[0:n]; g[0:n] = 0 -- one pass, no atomics (gradient accumulation over
+ *                                      micro-batches: the update then takes `acc` as its gradient); n % 4 == 0
+ *   pamnet_chunk_groups_check        : host-side validation of a chunk map BEFORE it is uploaded (chunk_group_host: HOST array):
+ *                                      PAMNET_EINVAL when an id is >= n_groups.  (The kernels themselves take an id modulo 16 and so never index
+ *                                      beyond their 16-entry table; table entries past n_groups are frozen.) */
+#define PAMNET_MAX_PARAM_GROUPS 16
+int pamnet_chunk_groups_check(const uint8_t* chunk_group_host, int64_t n_chunks, int64_t n_groups);
+int pamnet_sumsq_partials_masked_f32(const float* g, int64_t n, const uint8_t* chunk_group, int64_t n_groups,
+                                     const int32_t* frozen, double* partials, pamnet_stream_t stream);
+int pamnet_grad_accumulate_f32(float* acc, float* g, int64_t n, pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Optimiser tail of the reference loop on flat fp32 buffers, one pass (main_qm9.py:111-112,116; utils/ema.py:13-20):
@@ -832,6 +847,20 @@ int pamnet_adam_ema_norm_f32(float* p, float* g, float* m, float* v, float* shad
                              float beta2, float eps, float weight_decay, int64_t step_count, float ema_decay,
                              const double* sumsq_partials, float* norm_out, float max_norm, int32_t zero_grad,
                              pamnet_stream_t stream);
+/* The same pass with per-element hyper-parameters taken from parameter groups (one launch).  Element i belongs to group
+ * chunk_group[i / 64] (device bytes, see pamnet_sumsq_partials_masked_f32); lr_scale / weight_decay / frozen are HOST arrays of
+ * n_groups entries (1 <= n_groups <= PAMNET_MAX_PARAM_GROUPS; lr_scale, weight_decay >= 0), copied into the kernel's arguments:
+ *   group rate lr_g = lr * lr_scale[g], decay wd_g = weight_decay[g]
+ *   decoupled == 0 : g_clipped += wd_g * p          (L2 decay -- as pamnet_adam_ema_norm_f32)
+ *   decoupled != 0 : p *= 1 - lr_g * wd_g, then the Adam step on the clipped gradient      (AdamW)
+ *   frozen[g] != 0 : p, m, v and shadow of the chunk are neither read nor written; its g is zeroed when zero_grad != 0
+ * sumsq_partials: the 256 partials of pamnet_sumsq_partials_masked_f32 with the same map (frozen chunks outside the norm).
+ * n % 64 == 0.  With one group {1, wd, not frozen} and decoupled == 0 the result is bit for bit pamnet_adam_ema_norm_f32's. */
+int pamnet_adam_ema_groups_f32(float* p, float* g, float* m, float* v, float* shadow, int64_t n, const uint8_t* chunk_group,
+                               int64_t n_groups, const float* lr_scale, const float* weight_decay, const int32_t* frozen,
+                               float lr, float beta1, float beta2, float eps, int32_t decoupled, int64_t step_count,
+                               float ema_decay, const double* sumsq_partials, float* norm_out, float max_norm,
+                               int32_t zero_grad, pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Narrow widths (d = 16 / 32 / 64: the reference's RNA configurations, inference_rna_puzzles.py:29-30,

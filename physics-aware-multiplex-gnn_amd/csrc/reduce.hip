@@ -40,6 +40,63 @@ __global__ __launch_bounds__(256) void sumsq_partials_kernel(const float4* __res
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
+// The same slices and order with the chunks of frozen parameter groups left out (one group byte per 64 floats = 16 float4;
+// bit k of `frozen`: group k contributes nothing).  A masked vector is replaced by zero, not multiplied: the sum of squares
+// with no frozen group is bit for bit sumsq_partials_kernel's.
+__global__ __launch_bounds__(256) void sumsq_partials_masked_kernel(const float4* __restrict__ g, int64_t n4,
+                                                                    const uint8_t* __restrict__ chunk_group, uint32_t frozen,
+                                                                    double* __restrict__ partial) {
+    __shared__ double red[256];
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 a0 = zero, a1 = zero;
+    const int64_t per = (n4 + gridDim.x - 1) / gridDim.x;
+    const int64_t beg = blockIdx.x * per, end = beg + per < n4 ? beg + per : n4;
+    int64_t i = beg + threadIdx.x;
+    for (; i + 256 < end; i += 512) {
+        float4 u = g[i], v = g[i + 256];
+        if ((frozen >> (chunk_group[i >> 4] & 15)) & 1u) u = zero;
+        if ((frozen >> (chunk_group[(i + 256) >> 4] & 15)) & 1u) v = zero;
+        a0.x = fmaf(u.x, u.x, a0.x), a0.y = fmaf(u.y, u.y, a0.y), a0.z = fmaf(u.z, u.z, a0.z), a0.w = fmaf(u.w, u.w, a0.w);
+        a1.x = fmaf(v.x, v.x, a1.x), a1.y = fmaf(v.y, v.y, a1.y), a1.z = fmaf(v.z, v.z, a1.z), a1.w = fmaf(v.w, v.w, a1.w);
+    }
+    if (i < end) {
+        float4 u = g[i];
+        if ((frozen >> (chunk_group[i >> 4] & 15)) & 1u) u = zero;
+        a0.x = fmaf(u.x, u.x, a0.x), a0.y = fmaf(u.y, u.y, a0.y), a0.z = fmaf(u.z, u.z, a0.z), a0.w = fmaf(u.w, u.w, a0.w);
+    }
+    red[threadIdx.x] = ((double)a0.x + (double)a0.y) + ((double)a0.z + (double)a0.w) + ((double)a1.x + (double)a1.y) +
+                       ((double)a1.z + (double)a1.w);
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+// acc += g; g = 0 (gradient accumulation over micro-batches): 2 reads + 2 writes of n floats, four 16-byte loads in flight
+// per lane; every element is owned by one lane -- no atomics, the sum over micro-batches is in call order.
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float4* __restrict__ acc, float4* __restrict__ g, int64_t n4) {
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (; i + stride < n4; i += 2 * stride) {
+        float4 a0 = acc[i], a1 = acc[i + stride];
+        const float4 g0 = g[i], g1 = g[i + stride];
+        a0.x += g0.x, a0.y += g0.y, a0.z += g0.z, a0.w += g0.w;
+        a1.x += g1.x, a1.y += g1.y, a1.z += g1.z, a1.w += g1.w;
+        acc[i] = a0, acc[i + stride] = a1;
+        g[i] = zero, g[i + stride] = zero;
+    }
+    if (i < n4) {
+        float4 a0 = acc[i];
+        const float4 g0 = g[i];
+        a0.x += g0.x, a0.y += g0.y, a0.z += g0.z, a0.w += g0.w;
+        acc[i] = a0;
+        g[i] = zero;
+    }
+}
+
 // one workgroup: loss = mean_i l(out_i - y_i) ; d_out_i = l'(out_i - y_i) * grad_scale / n     (n graphs: a few hundred)
 //   KIND 0: l(d) = |d|                                   F.l1_loss        (main_qm9.py:108)
 //   KIND 1: l(d) = d^2                                   F.mse_loss       (main_pdbbind.py:93)
@@ -148,6 +205,45 @@ extern "C" int pamnet_sumsq_partials_f32(const float* g, int64_t n, double* part
     if (!g || !partials) return PAMNET_ENULL;
     hipLaunchKernelGGL(sumsq_partials_kernel, dim3(NORM_BLOCKS), dim3(256), 0, as_stream(stream), (const float4*)g, n / 4,
                        partials);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
+// Host-side check of a chunk map before its upload: every id below n_groups.
+extern "C" int pamnet_chunk_groups_check(const uint8_t* chunk_group_host, int64_t n_chunks, int64_t n_groups) {
+    if (n_chunks < 0 || n_groups < 1 || n_groups > PAMNET_MAX_PARAM_GROUPS) return PAMNET_EINVAL;
+    if (n_chunks > 0 && !chunk_group_host) return PAMNET_ENULL;
+    for (int64_t c = 0; c < n_chunks; ++c)
+        if (chunk_group_host[c] >= n_groups) return PAMNET_EINVAL;
+    return PAMNET_OK;
+}
+
+// pamnet_sumsq_partials_f32 without the chunks (64 floats) of frozen groups.  chunk_group: device, n / 64 bytes; frozen: host,
+// n_groups entries.  n % 64 == 0.
+extern "C" int pamnet_sumsq_partials_masked_f32(const float* g, int64_t n, const uint8_t* chunk_group, int64_t n_groups,
+                                                const int32_t* frozen, double* partials, pamnet_stream_t stream) {
+    if (n < 0 || (n & 63) || n_groups < 1 || n_groups > PAMNET_MAX_PARAM_GROUPS) return PAMNET_EINVAL;
+    if (!frozen || !partials || (n > 0 && (!g || !chunk_group))) return PAMNET_ENULL;
+    uint32_t mask = 0xffffffffu;                       // table entries past n_groups: frozen, as in the update kernel
+    for (int64_t k = 0; k < n_groups; ++k)
+        if (!frozen[k]) mask &= ~(1u << k);
+    hipLaunchKernelGGL(sumsq_partials_masked_kernel, dim3(NORM_BLOCKS), dim3(256), 0, as_stream(stream), (const float4*)g,
+                       n / 4, chunk_group, mask, partials);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
+// acc[0:n] += g[0:n]; g[0:n] = 0.  n % 4 == 0, buffers 16-byte aligned, acc and g distinct.
+extern "C" int pamnet_grad_accumulate_f32(float* acc, float* g, int64_t n, pamnet_stream_t stream) {
+    if (n < 0 || (n & 3)) return PAMNET_EINVAL;
+    if (n == 0) return PAMNET_OK;
+    if (!acc || !g) return PAMNET_ENULL;
+    if (acc == g) return PAMNET_EINVAL;
+    const int64_t n4 = n / 4;
+    int64_t blocks = ceil_div(n4, 512);
+    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+    hipLaunchKernelGGL(grad_accumulate_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (float4*)acc,
+                       (float4*)g, n4);
     PAMNET_LAUNCH_CHECK();
     return PAMNET_OK;
 }

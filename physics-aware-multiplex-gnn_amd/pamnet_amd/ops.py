@@ -365,6 +365,16 @@ def sumsq_partials(flat):
     return part
 
 
+def sumsq_partials_masked(flat, chunk_map, n_groups, frozen):
+    """sumsq_partials without the 64-float chunks of frozen parameter groups.  chunk_map: uint8 device tensor, one group id per
+    chunk; frozen: host ctypes int32 array of n_groups flags (train.Trainer builds both once)."""
+    import ctypes
+    part = torch.empty(256, dtype=torch.float64, device=flat.device)
+    lib.call('pamnet_sumsq_partials_masked_f32', lib.ptr(flat), flat.numel(), lib.ptr(chunk_map), int(n_groups),
+             ctypes.addressof(frozen), lib.ptr(part), lib.stream_of(flat))
+    return part
+
+
 class _RBF(torch.autograd.Function):
     """BesselBasisLayer (layers/basic.py:59-76); freq is trainable; dist is differentiated when it requires grad (positions
     that require grad: graph.differentiable_geometry; default envelope only)."""

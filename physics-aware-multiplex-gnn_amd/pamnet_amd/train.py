@@ -137,6 +137,50 @@ class MultiStepLR(object):
         return self.lr_at(epoch)
 
 
+MAX_EXPLICIT_GROUPS = 15                     # + the default group = the 16 entries of the update kernel's table
+_GROUP_KEYS = ('params', 'lr_scale', 'weight_decay', 'frozen')
+
+
+def resolve_param_groups(names, param_groups, weight_decay):
+    """Trainer(param_groups=...) -> (group_of, groups).  `param_groups`: a list of dicts {'params': [fnmatch patterns over
+    `names`], 'lr_scale': 1.0, 'weight_decay': <the trainer's>, 'frozen': False}.  A parameter belongs to the FIRST group one
+    of whose patterns matches it (group i of the list has index i + 1); parameters no group claims form the default group,
+    index 0, with the trainer's own values.  groups[k] = {'lr_scale', 'weight_decay', 'frozen'} resolved, k = 0 the default."""
+    import fnmatch
+    groups = [{'lr_scale': 1.0, 'weight_decay': float(weight_decay), 'frozen': False}]
+    group_of = {n: 0 for n in names}
+    if param_groups is None:
+        return group_of, groups
+    param_groups = list(param_groups)
+    if len(param_groups) > MAX_EXPLICIT_GROUPS:
+        raise ValueError('param_groups: %d groups given, at most %d are supported' % (len(param_groups), MAX_EXPLICIT_GROUPS))
+    for gi, spec in enumerate(param_groups):
+        if not isinstance(spec, dict):
+            raise ValueError('param_groups[%d] must be a dict, got %r' % (gi, type(spec).__name__))
+        for key in spec:
+            if key not in _GROUP_KEYS:
+                raise ValueError('param_groups[%d]: unknown key %r (known: %s)' % (gi, key, ', '.join(_GROUP_KEYS)))
+        pats = spec.get('params')
+        if isinstance(pats, str):
+            pats = [pats]
+        if not pats:
+            raise ValueError("param_groups[%d]: 'params' must be a non-empty list of name patterns" % gi)
+        res = {'lr_scale': float(spec.get('lr_scale', 1.0)), 'weight_decay': float(spec.get('weight_decay', weight_decay)),
+               'frozen': bool(spec.get('frozen', False))}
+        for key in ('lr_scale', 'weight_decay'):
+            if not res[key] >= 0.0:
+                raise ValueError('param_groups[%d]: %s must be >= 0 (got %r)' % (gi, key, spec.get(key)))
+        for pat in pats:
+            hit = [n for n in names if fnmatch.fnmatchcase(n, pat)]
+            if not hit:
+                raise ValueError('param_groups[%d]: pattern %r matches no parameter name' % (gi, pat))
+            for n in hit:
+                if group_of[n] == 0:
+                    group_of[n] = gi + 1
+        groups.append(res)
+    return group_of, groups
+
+
 def plan_buckets(layer_ranges, numel, n_buckets):
     """Tile the flat gradient [0, numel) into contiguous all-reduce slices by layer pair, in the order the backward
     completes them (FlatParams lays layer pair L-1 first).  Returns (buckets, tail): buckets = [(lo, hi, k_ready)] --
@@ -232,9 +276,19 @@ class Prefetcher(object):
 class Trainer(object):
     def __init__(self, model, lr=1e-4, weight_decay=0.0, ema_decay=0.999, max_grad_norm=1000.0, betas=(0.9, 0.999),
                  eps=1e-8, world_size=1, process_group=None, overlap_comm=True, n_buckets=3, native_optimizer=True,
-                 loss='l1'):
+                 loss='l1', param_groups=None, decoupled_weight_decay=False, accumulate=1):
         """loss: 'l1' | 'mse' | 'smooth_l1' (the three drivers' losses, mean over graphs); max_grad_norm=None: no
-        clip_grad_norm_; ema_decay=None: no EMA shadow (evaluate() then runs on the weights themselves)."""
+        clip_grad_norm_; ema_decay=None: no EMA shadow (evaluate() then runs on the weights themselves).
+
+        param_groups: per-group `lr_scale` / `weight_decay` / `frozen` by name pattern (resolve_param_groups; the resolved
+        assignment is `group_of`: name -> group index, 0 = the default group).  `lr_scale` multiplies the `lr` a step is
+        given.  Frozen parameters are never changed by the update (nor their Adam moments, nor their EMA shadow) and stay
+        out of the clipping norm and `last_grad_norm`; the backward still computes their gradients.
+        decoupled_weight_decay: AdamW (p *= 1 - lr_g * wd_g before the Adam step) instead of the L2 term in the gradient.
+        accumulate=k: step() runs forward + backward on every call and the communicate -> clip -> update -> EMA sequence
+        on every k-th, on the sum of the k micro-gradients; each call's loss gradient is scaled by its graphs /
+        global_graphs, the graphs ONE UPDATE averages over (all ranks, all micro-batches; default: this call's * world_size
+        * k).  `micro_step` is the position in the cycle, accumulated_grad() a copy of the sum so far."""
         from .ops import LOSS_ENTRIES
         if loss not in LOSS_ENTRIES:
             raise ValueError("loss must be one of 'l1', 'mse', 'smooth_l1' (got %r)" % (loss,))
@@ -244,17 +298,30 @@ class Trainer(object):
             model._disable_flat_view()                     # (this class owns the flat buffers; no second interface on top)
         self.fp = FlatParams(model, direct=True)           # fused layers write gradients straight into fp.grad
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        if int(accumulate) != accumulate or int(accumulate) < 1:
+            raise ValueError('accumulate must be an integer >= 1 (got %r)' % (accumulate,))
+        self.accumulate, self.micro_step = int(accumulate), 0
+        self.decoupled = bool(decoupled_weight_decay)
+        self.group_of, self.groups = resolve_param_groups(self.fp.names, param_groups, weight_decay)
+        # the default recipe (one rate, one L2 decay, everything trainable) keeps its own entry point / its one flat Parameter
+        self._grouped = bool(param_groups) or self.decoupled
+        self.acc = torch.zeros_like(self.fp.grad) if self.accumulate > 1 else None      # sum of the micro-gradients
         # On the GPU clip + Adam + EMA (+ the next zero_grad) are one pass of csrc/optim.hip over the flat buffers;
         # torch.optim.Adam on the flat tensor is the CPU path (gloo unit tests) and the cross-check of the kernel.
         self.native_opt = bool(native_optimizer and self.fp.flat.is_cuda)
+        gsrc = self.fp.grad if self.acc is None else self.acc               # what the update reads
         if self.native_opt:
             self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.fp.flat), torch.zeros_like(self.fp.flat)
             self.step_count = 0
-        else:
+            if self._grouped:
+                self._setup_native_groups()
+        elif not self._grouped:
             self.opt = torch.optim.Adam([torch.nn.Parameter(self.fp.flat)], lr=lr, betas=betas, eps=eps,
                                         weight_decay=weight_decay, amsgrad=False, fused=self.fp.flat.is_cuda)
             self._p = self.opt.param_groups[0]['params'][0]
-            self._p.grad = self.fp.grad
+            self._p.grad = gsrc
+        else:
+            self._setup_torch_groups(gsrc)
         self._grad_clean = True                            # fp.grad is all zeros (fresh buffer / zeroed by the update)
         # widths without a one-node forward (models._one_node: dim = 128 engine, narrow-width tape): autograd hands the
         # gradient tensors over and one multi-tensor add packs them into the flat buffer
@@ -271,13 +338,89 @@ class Trainer(object):
             dist.broadcast(self.fp.flat, 0, group=process_group)
             if self.shadow is not None:
                 self.shadow.copy_(self.fp.flat)
-        if overlap_comm and overlap_comm != 'force_single' and distributed and (world_size > 1 or overlap_comm == 'force'):
+        # (accumulating: the ranks exchange the SUM once per update, after the last backward -- nothing to overlap with)
+        if overlap_comm and overlap_comm != 'force_single' and distributed and (world_size > 1 or overlap_comm == 'force') \
+                and self.accumulate == 1:
             self._setup_buckets(n_buckets)
+
+    # -- parameter groups -----------------------------------------------------------------------------------------------
+    def _slices(self):
+        """(name, offset, numel, group index) of every parameter in the flat layout."""
+        return [(n, self.fp.offsets[n], p.numel(), self.group_of[n]) for n, p in zip(self.fp.names, self.fp.params)]
+
+    def _setup_native_groups(self):
+        """The update kernel's view of the groups: one group byte per 64-float chunk of the flat buffers (FlatParams starts
+        every tensor on a 64-float boundary; a tensor's padding belongs to its group) on the device, and the per-group
+        table as host arrays."""
+        import ctypes
+        from . import lib
+        n_chunks = self.fp.flat.numel() // 64
+        cmap = torch.zeros(n_chunks, dtype=torch.uint8)
+        for _, o, k, g in self._slices():
+            cmap[o // 64:(o + k + 63) // 64] = g
+        ng = len(self.groups)
+        lib.call('pamnet_chunk_groups_check', cmap.data_ptr(), n_chunks, ng)
+        self._chunk_map = cmap.to(self.fp.flat.device)
+        self._g_scale = (ctypes.c_float * ng)(*[g['lr_scale'] for g in self.groups])
+        self._g_wd = (ctypes.c_float * ng)(*[g['weight_decay'] for g in self.groups])
+        self._g_frozen = (ctypes.c_int32 * ng)(*[int(g['frozen']) for g in self.groups])
+
+    def _setup_torch_groups(self, gsrc):
+        """torch.optim.Adam / AdamW with real param_groups over per-tensor views of the flat buffers; frozen tensors are
+        left out (of the optimiser, the clipping norm and the EMA)."""
+        by_group = {}
+        self._views, self._shadow_views = [], None
+        for n, o, k, g in self._slices():
+            if self.groups[g]['frozen']:
+                continue
+            v = torch.nn.Parameter(self.fp.flat[o:o + k])
+            v.grad = gsrc[o:o + k]
+            by_group.setdefault(g, []).append(v)
+            self._views.append((o, k, v))
+        pgs = [{'params': by_group[g], 'lr': self.lr * self.groups[g]['lr_scale'],
+                'weight_decay': self.groups[g]['weight_decay'], 'lr_scale': self.groups[g]['lr_scale']}
+               for g in sorted(by_group)]
+        cls = torch.optim.AdamW if self.decoupled else torch.optim.Adam
+        self.opt = cls(pgs, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, amsgrad=False,
+                       fused=self.fp.flat.is_cuda) if pgs else None
+
+    def adam_moments(self):
+        """(exp_avg, exp_avg_sq) as flat copies in the layout of fp.flat, whichever optimiser holds them (zero where it
+        holds none: padding, frozen parameters, before the first update)."""
+        if self.native_opt:
+            return self.exp_avg.clone(), self.exp_avg_sq.clone()
+        m, v = torch.zeros_like(self.fp.flat), torch.zeros_like(self.fp.flat)
+        if not self._grouped:
+            st = self.opt.state.get(self._p, {})
+            if 'exp_avg' in st:
+                m.copy_(st['exp_avg']), v.copy_(st['exp_avg_sq'])
+            return m, v
+        for o, k, view in self._views:
+            st = self.opt.state.get(view, {})
+            if 'exp_avg' in st:
+                m[o:o + k].copy_(st['exp_avg']), v[o:o + k].copy_(st['exp_avg_sq'])
+        return m, v
+
+    def accumulated_grad(self):
+        """A copy of the sum of the micro-gradients of the current cycle (accumulate > 1), else of the flat gradient."""
+        return (self.fp.grad if self.acc is None else self.acc).clone()
+
+    def _accumulate(self):
+        """acc += grad; grad = 0 -- one kernel on the GPU."""
+        if self.fp.flat.is_cuda:
+            from . import lib
+            lib.call('pamnet_grad_accumulate_f32', lib.ptr(self.acc), lib.ptr(self.fp.grad), self.fp.grad.numel(),
+                     lib.stream_of(self.fp.grad))
+        else:
+            self.acc.add_(self.fp.grad)
+            self.fp.grad.zero_()
+        self._grad_clean = True
 
     # -- pieces (also timed individually by bench.py) ---------------------------------------------------------------
     def forward_backward(self, data, global_graphs=None):
         """One forward + backward into the flat gradient.  Overwrite semantics (the fused kernels write gradients in
-        place): a call always starts from a zeroed buffer, there is no gradient accumulation across calls."""
+        place): a call always starts from a zeroed buffer; gradients are summed over calls by step() with accumulate > 1
+        (into a second flat buffer), not here."""
         if not self._grad_clean:
             self.fp.zero_grad()
         self._grad_clean = False
@@ -287,9 +430,10 @@ class Trainer(object):
             self.fp.release_grads()
         out = self.model(data)
         # local mean -> contribution to the global-batch mean
-        if self.world_size > 1 and global_graphs is None:
-            global_graphs = out.numel() * self.world_size            # equal shards unless the caller says otherwise
-        scale = float(out.numel()) / float(global_graphs) if self.world_size > 1 else 1.0
+        split = self.world_size > 1 or self.accumulate > 1             # this call sees a part of what one update averages over
+        if split and global_graphs is None:                           # equal parts unless the caller says otherwise
+            global_graphs = out.numel() * self.world_size * self.accumulate
+        scale = float(out.numel()) / float(global_graphs) if split else 1.0
         if out.is_cuda and out.dtype == torch.float32:
             from . import ops
             loss, d_out = ops.loss_with_grad(self.loss_kind, out, data.y, scale)      # loss + its gradient: one launch
@@ -333,7 +477,7 @@ class Trainer(object):
         still working through it), the remainder after the backward's end; the main stream then waits for all of it."""
         if self._buckets is None:
             if self.world_size > 1 or self._force_single:
-                dist.all_reduce(self.fp.grad, op=dist.ReduceOp.SUM, group=self.pg)
+                dist.all_reduce(self.fp.grad if self.acc is None else self.acc, op=dist.ReduceOp.SUM, group=self.pg)
             return
         if not self.fp.flat.is_cuda:                       # same tiling, no streams
             for lo, hi, _ in self._buckets:
@@ -357,44 +501,97 @@ class Trainer(object):
             dist.all_reduce(self.fp.grad[lo:hi], op=dist.ReduceOp.SUM, group=self.pg)
         main.wait_stream(self._comm)
 
+    def _update_gradient(self):
+        """The buffer clip / the update read: the flat gradient, or with accumulate > 1 the sum step() builds.  The pieces
+        (forward_backward, clip, optimizer_step / native_update) called one by one do not build that sum: refused rather than
+        updating from a sum the last gradient never joined."""
+        if self.acc is None:
+            return self.fp.grad
+        if not self._grad_clean:
+            raise RuntimeError('accumulate > 1: the update reads the sum of the micro-gradients, which only step() builds; the '
+                               'gradient of the last forward_backward() has not been added to it -- call step()')
+        return self.acc
+
     def clip(self):
-        norm = torch.linalg.vector_norm(self.fp.grad)
+        g = self._update_gradient()
+        if self._grouped:
+            return self._clip_groups()
+        norm = torch.linalg.vector_norm(g)
         if self.max_grad_norm is None:
             return norm
         coef = torch.clamp(self.max_grad_norm / (norm + 1e-6), max=1.0)    # clip_grad_norm_ (main_qm9.py:111)
-        self.fp.grad.mul_(coef)
+        g.mul_(coef)
         return norm
 
+    def _clip_groups(self):
+        """clip_grad_norm_ over the trainable parameters (frozen ones are in neither the norm nor the scaling)."""
+        params = [v for _, _, v in self._views]
+        if not params:
+            return torch.zeros((), device=self.fp.flat.device)
+        if self.max_grad_norm is not None:
+            return torch.nn.utils.clip_grad_norm_(params, max_norm=self.max_grad_norm, norm_type=2)
+        return torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(v.grad) for v in params]))
+
     def optimizer_step(self, lr=None):
+        if self._grouped:
+            if lr is not None:
+                self.lr = lr
+            if self.opt is None:                                        # everything frozen
+                return
+            for pg in self.opt.param_groups:
+                pg['lr'] = self.lr * pg['lr_scale']
+            self.opt.step()
+            return
         if lr is not None:
             self.opt.param_groups[0]['lr'] = lr
         self.opt.step()
 
     def native_update(self, lr=None, num_updates=99999):
-        """[clip ->] Adam [-> EMA] -> zero the gradient, one kernel; the norm stays on the device."""
+        """[clip ->] Adam [-> EMA] -> zero the gradient, one kernel; the norm stays on the device.  With parameter groups or
+        AdamW: the masked norm and the grouped form of the same launch; with accumulate > 1 the gradient is the sum."""
         from . import lib
         if lr is not None:
             self.lr = lr
         from . import ops
-        # the pre-clip norm is reported either way (last_grad_norm); without a clip its partials only feed norm_out
-        part = ops.sumsq_partials(self.fp.grad)            # the kernel below adds the 256 partials and clips by the norm
+        g = self._update_gradient()
         norm = torch.empty(1, dtype=torch.float32, device=self.fp.flat.device)
-        self.step_count += 1
         decay = 0.0 if self.ema_decay is None else min(self.ema_decay, (1.0 + num_updates) / (10.0 + num_updates))   # utils/ema.py:14
         max_norm = float('inf') if self.max_grad_norm is None else float(self.max_grad_norm)
-        lib.call('pamnet_adam_ema_norm_f32', lib.ptr(self.fp.flat), lib.ptr(self.fp.grad), lib.ptr(self.exp_avg),
-                 lib.ptr(self.exp_avg_sq), lib.ptr(self.shadow), self.fp.flat.numel(), float(self.lr),
-                 float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
-                 self.step_count, float(decay), lib.ptr(part), lib.ptr(norm), max_norm, 1,
-                 lib.stream_of(self.fp.flat))
+        if not self._grouped:
+            # the pre-clip norm is reported either way (last_grad_norm); without a clip its partials only feed norm_out
+            part = ops.sumsq_partials(g)                   # the kernel below adds the 256 partials and clips by the norm
+            self.step_count += 1
+            lib.call('pamnet_adam_ema_norm_f32', lib.ptr(self.fp.flat), lib.ptr(g), lib.ptr(self.exp_avg),
+                     lib.ptr(self.exp_avg_sq), lib.ptr(self.shadow), self.fp.flat.numel(), float(self.lr),
+                     float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
+                     self.step_count, float(decay), lib.ptr(part), lib.ptr(norm), max_norm, 1,
+                     lib.stream_of(self.fp.flat))
+        else:
+            import ctypes
+            ng = len(self.groups)
+            part = ops.sumsq_partials_masked(g, self._chunk_map, ng, self._g_frozen)
+            self.step_count += 1
+            lib.call('pamnet_adam_ema_groups_f32', lib.ptr(self.fp.flat), lib.ptr(g), lib.ptr(self.exp_avg),
+                     lib.ptr(self.exp_avg_sq), lib.ptr(self.shadow), self.fp.flat.numel(), lib.ptr(self._chunk_map), ng,
+                     ctypes.addressof(self._g_scale), ctypes.addressof(self._g_wd), ctypes.addressof(self._g_frozen),
+                     float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), int(self.decoupled),
+                     self.step_count, float(decay), lib.ptr(part), lib.ptr(norm), max_norm, 1,
+                     lib.stream_of(self.fp.flat))
         norm = norm[0]
-        self._grad_clean = True
+        self._grad_clean = True                            # (accumulating: _accumulate() had left fp.grad zeroed already)
         return norm
 
     def ema_update(self, num_updates=99999):
         if self.ema_decay is None:
             return
         decay = min(self.ema_decay, (1.0 + num_updates) / (10.0 + num_updates))     # utils/ema.py:14
+        if self._grouped and not self.native_opt:                                   # the trainable slices only
+            if self._shadow_views is None:
+                self._shadow_views = [self.shadow[o:o + k] for o, k, _ in self._views]
+            if self._shadow_views:
+                torch._foreach_mul_(self._shadow_views, decay)
+                torch._foreach_add_(self._shadow_views, [v.data for _, _, v in self._views], alpha=1.0 - decay)
+            return
         self.shadow.mul_(decay).add_(self.fp.flat, alpha=1.0 - decay)
 
     def step(self, data, lr=None, global_graphs=None, next_data=None):
@@ -404,6 +601,14 @@ class Trainer(object):
         self._wait_prepared(data)
         self._throttle()
         loss = self.forward_backward(data, global_graphs)
+        if self.acc is not None:
+            self._accumulate()                                 # this call's gradient joins the sum before any norm is taken
+            self.micro_step += 1
+            if self.micro_step < self.accumulate:              # not an update call: the loss of this micro-batch, no more
+                if next_data is not None:
+                    self.prefetch(next_data)
+                return loss
+            self.micro_step = 0
         self.sync_gradients()
         if self.native_opt:
             self.last_grad_norm = self.native_update(lr)       # pre-clip L2 norm (device scalar; no host sync here)
@@ -411,6 +616,8 @@ class Trainer(object):
             self.last_grad_norm = self.clip()
             self.optimizer_step(lr)
             self.ema_update()
+            if self.acc is not None:
+                self.acc.zero_()
         if next_data is not None:
             self.prefetch(next_data)
         return loss
@@ -522,21 +729,50 @@ class Trainer(object):
         (zero-host-sync batches) are read before anything is saved -- a checkpoint never outlives an unchecked step."""
         self.drain()
         sd = {'model': {k: v.detach().clone() for k, v in self.model.state_dict().items()},
-              'shadow': None if self.shadow is None else self.shadow.clone(), 'lr': self.lr}
+              'shadow': None if self.shadow is None else self.shadow.clone(), 'lr': self.lr,
+              'param_groups': {'group_of': dict(self.group_of), 'groups': [dict(g) for g in self.groups]},
+              'decoupled_weight_decay': self.decoupled, 'accumulate': self.accumulate, 'micro_step': self.micro_step}
+        if self.micro_step > 0:
+            sd['accumulated_grad'] = self.acc.clone()                  # the partial sum of the cycle under way
         if self.native_opt:
             sd.update(exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(), step_count=self.step_count)
         else:
             import copy
-            sd['optimizer'] = copy.deepcopy(self.opt.state_dict())    # (a snapshot like the rest: torch hands out its live
-            #                                                             tensors, and a load from them would SHARE the step counter)
+            # (a snapshot like the rest: torch hands out its live tensors, and a load from them would SHARE the step counter;
+            #  no optimiser at all = every parameter frozen)
+            sd['optimizer'] = copy.deepcopy(self.opt.state_dict()) if self.opt is not None else {}
         return sd
 
     def load_state_dict(self, sd):
         """Restore what state_dict() saved.  The optimiser mode (the fused HIP Adam over the flat buffers, or torch's) and the
         flat layout must be those of the trainer that saved it: anything else raises ValueError instead of a bare KeyError or a
         silent mis-copy.  A checkpoint without an EMA shadow (a trainer that kept none) restarts the shadow from the loaded
-        weights -- evaluate() / predictions() never run under the constructor's weights."""
+        weights -- evaluate() / predictions() never run under the constructor's weights.  The parameter groups
+        (assignment and the explicit groups' values), the decay mode and `accumulate` must be the trainer's too; a checkpoint
+        that says nothing about them was saved by the default recipe."""
         self.drain()
+        saved = sd.get('param_groups')
+        if saved is None:
+            saved_of, saved_groups = {n: 0 for n in self.fp.names}, None
+        else:
+            saved_of, saved_groups = saved['group_of'], saved['groups']
+        if saved_of != self.group_of:
+            diff = sorted(n for n in set(saved_of) | set(self.group_of) if saved_of.get(n) != self.group_of.get(n))
+            raise ValueError('checkpoint assigns %d parameter(s) to other groups than this trainer (first: %r: %r there, %r '
+                             'here)' % (len(diff), diff[0], saved_of.get(diff[0]), self.group_of.get(diff[0])))
+        if (saved_groups[1:] if saved_groups is not None else []) != self.groups[1:]:      # (group 0: the constructor's values)
+            raise ValueError('checkpoint was saved with other param_groups values (%r) than this trainer\'s (%r)' % (
+                saved_groups[1:] if saved_groups is not None else [], self.groups[1:]))
+        if bool(sd.get('decoupled_weight_decay', False)) != self.decoupled:
+            raise ValueError('checkpoint was saved with decoupled_weight_decay=%r, this trainer runs %r' % (
+                bool(sd.get('decoupled_weight_decay', False)), self.decoupled))
+        if int(sd.get('accumulate', 1)) != self.accumulate:
+            raise ValueError('checkpoint was saved with accumulate=%d, this trainer runs %d' % (
+                int(sd.get('accumulate', 1)), self.accumulate))
+        micro = int(sd.get('micro_step', 0))
+        if micro > 0 and (sd.get('accumulated_grad') is None or tuple(sd['accumulated_grad'].shape) != tuple(self.acc.shape)):
+            raise ValueError('checkpoint was taken at micro_step %d without a partial gradient sum of this model\'s flat '
+                             'layout' % micro)
         saved_native = 'exp_avg' in sd
         if saved_native != bool(self.native_opt) or (not saved_native and 'optimizer' not in sd):
             raise ValueError('checkpoint holds %s optimiser state, this trainer runs %s' % (
@@ -561,7 +797,14 @@ class Trainer(object):
             self.exp_avg.copy_(sd['exp_avg']), self.exp_avg_sq.copy_(sd['exp_avg_sq'])
             self.step_count = int(sd['step_count'])
         else:
-            self.opt.load_state_dict(sd['optimizer'])
+            if self.opt is not None:
+                self.opt.load_state_dict(sd['optimizer'])
+        self.micro_step = micro
+        if self.acc is not None:
+            if micro > 0:
+                self.acc.copy_(sd['accumulated_grad'])
+            else:
+                self.acc.zero_()
 
     def close(self):
         """End of training: wait for the steps in flight and read their deferred checks (raises what they found)."""
