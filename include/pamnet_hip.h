@@ -9,9 +9,13 @@
  *   - arguments are raw DEVICE pointers, 64-bit sizes and a hipStream_t (passed as void*); no torch types;
  *   - the caller owns every device buffer; the library allocates no device memory, keeps no mutable state between calls
  *     and never synchronises (the pamnet_stack_* engine calls build small host-side pointer tables on the stack / heap per
- *     call).  The only process-wide data are five read-once developer switches taken from the environment on first use
- *     (PAMNET_EDGE_WAVES, PAMNET_EDGE_IMAGES, PAMNET_CHAIN_BF16, PAMNET_SMALL_FORMS, PAMNET_AGG_PIECES, PAMNET_CHAIN_LEAN: kernel-variant selection for measurements; C++11 static
- *     initialisation, thread-safe, constant afterwards);
+ *     call).  The only process-wide data are fifteen developer switches taken from the environment (kernel-variant selection
+ *     for measurements; INTEGRATION.md section 5 lists them).  Fourteen are read once, on first use (C++11 static
+ *     initialisation, thread-safe, constant afterwards): the layer-stack engine's nine in one block (csrc/engine.hip
+ *     Switches: PAMNET_EDGE_RECOMPUTE, PAMNET_EDGE_WGRAD, PAMNET_EDGE_IMAGES with PAMNET_EDGE_WAVES, PAMNET_FUSE_SEGSUM,
+ *     PAMNET_FUSE_LOCAL_AGG, PAMNET_CHAIN_BF16, PAMNET_CHAIN_BF16_TILES, PAMNET_TT_AUX), and PAMNET_EDGE_WAVES
+ *     (edge_chain.hip), PAMNET_CHAIN_LEAN, PAMNET_CHAIN_WAVES (node_tail.hip), PAMNET_AGG_PIECES (edge_agg.hip),
+ *     PAMNET_SMALL_FORMS, PAMNET_HIST_LDS (graph.hip) where they are used.  PAMNET_AGG_PP (edge_agg.hip) is read by every call;
  *   - work is enqueued on `stream`; return value 0 = OK, >0 = hipError_t of the failed launch, <0 = argument error
  *     (PAMNET_EINVAL: bad size / unsupported width; PAMNET_ENULL: required pointer is null);
  *   - float tensors are fp32 row-major [rows, d]; index tensors are int32; CSR pointers have rows+1 entries;
@@ -751,6 +755,7 @@ int pamnet_embed_multi_bwd_f32(const pamnet_embed_job* jobs, int32_t n_jobs, con
  *                W_out.weight, W_out.bias, W}
  *   lparams    : n_layer x 35 device pointers  {mlp_x1.W, .b, mlp_m_ji.W, .b, mlp_m_kj.W, .b, mlp_sbf.0.W, .b,
  *                mlp_sbf.1.W, .b, lin_rbf.W, lin_rbf_out.W, tail ...}
+ *                (the slots of both tables by name: csrc/common.h, namespace pslot)
  *   saved/temp : caller-owned arenas sized by pamnet_stack_workspace (floats); `saved` must survive until the backward
  *   outs/atts  : [2*n_layer, n] rows ordered (global_0, local_0, global_1, ...)
  * pamnet_stack_layout: layout[0] = floats per layer pair in `saved`, layout[1] / [2] = offset of the global / local

@@ -21,6 +21,28 @@ static inline hipStream_t as_stream(pamnet_stream_t s) {
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Size bounds of the d = 128 launch plans, shared by the engine (engine.hip make_plan) and the kernels' own launchers.
+constexpr int64_t NODE_TILE_ROWS = 16;          // rows per workgroup of a node-chain launch (node_tail.hip BMN)
+// Row tiles up to which a node-chain launch is a single round (one workgroup per CU of the 256): the parked chain forms
+// (bf16x6, segment sums / local aggregation formed by the launch's own tiles).  Above it the lean forms, which read
+// their planes (node_tail.hip LEAN_FROM_TILES).
+constexpr int64_t PARKED_TILES_MAX = 256;
+// Global edges from which a workgroup streams enough rows (512 each) to fill its pipeline: the ping-pong edge forward
+// (edge_agg.hip agg_pp) and the edge backward that forms its own weight gradients (engine.hip).
+constexpr int64_t STREAMED_EDGES_FROM = 256 * 512;
+
+// Slots of the layer-stack engine's parameter tables (pamnet_hip.h `gparams` / `lparams`; pamnet_amd/stack.py
+// global_params / local_params produce them in this order).  Both engines index the tables by these names.
+namespace pslot {
+enum Global { G_WX1, G_BX1, G_WM, G_BM, G_WEA, G_TAIL, G_COUNT = 28 };       // mlp_x1 W b | mlp_m W [d,3d] b | W_edge_attr
+enum Local {                                                                 // mlp_x1 | mlp_m_ji | mlp_m_kj | mlp_sbf 0, 1 |
+    L_WX1, L_BX1, L_WJI, L_BJI, L_WKJ, L_BKJ, L_WS1, L_BS1, L_WS2, L_BS2, L_WLR, L_WLO, L_TAIL, L_COUNT = 35   // lin_rbf, lin_rbf_out
+};
+// the 23-pointer tail block both tables end with (fused.py tail_params): W[10], b[10], W_out.weight, W_out.bias, W
+enum Tail { T_W = 0, T_B = 10, T_WOUT = 20, T_BOUT, T_WATT, T_COUNT };
+static_assert(G_TAIL + T_COUNT == G_COUNT && L_TAIL + T_COUNT == L_COUNT, "parameter tables end with the tail block");
+}  // namespace pslot
+
 // The narrow-width (d = 16 / 32 / 64) half of the pamnet_stack_* entry points, defined in narrow_engine.hip; engine.hip
 // dispatches on d.  Arguments as the entry points' less those the narrow engine ignores.  Not exported.
 #pragma GCC visibility push(hidden)

@@ -1540,7 +1540,7 @@ inline int64_t agg_grid(int64_t m) {
 inline bool agg_pp(int64_t n_edges) {
     const char* e = getenv("PAMNET_AGG_PP");            // (per call: a test flips it inside one process)
     if (e && e[0]) return atoi(e) != 0;
-    return n_edges >= 256 * 512;
+    return n_edges >= STREAMED_EDGES_FROM;
 }
 
 }  // namespace

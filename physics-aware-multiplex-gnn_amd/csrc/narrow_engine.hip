@@ -342,7 +342,7 @@ inline Idx make_idx(const int32_t* const* g) {
     return Idx{g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11], g[12], g[13], g[14]};
 }
 
-constexpr int GP = 28, LP = 35;            // pointers per global / local layer in the parameter tables (pamnet_hip.h)
+namespace ps = pslot;                     // slots of the parameter / gradient tables (common.h)
 
 // slots of a layer pair's [d, d] weight blocks in the packed-image area
 enum Slot { G_W1 = 0, G_P = 1, G_TAIL = 3, L_W1 = 13, L_P = 14, L_Q = 18, L_TAIL = 22 };
@@ -357,15 +357,17 @@ struct Images {
 
 int pack_all(int d, int64_t n_layer, const float* const* gparams, const float* const* lparams, float* out, hipStream_t st) {
     for (int64_t k = 0; k < n_layer; ++k) {
-        const float* const* g = gparams + k * GP;
-        const float* const* l = lparams + k * LP;
+        const float* const* g = gparams + k * ps::G_COUNT;
+        const float* const* l = lparams + k * ps::L_COUNT;
         PackJobs J;
         auto set = [&](int slot, const float* W, int ld) { J.W[slot] = W, J.ld[slot] = ld; };
-        set(G_W1, g[0], d), set(G_P, g[2], 3 * d), set(G_P + 1, g[2] + d, 3 * d);
-        for (int i = 0; i < 10; ++i) set(G_TAIL + i, g[5 + i], d), set(L_TAIL + i, l[12 + i], d);
-        set(L_W1, l[0], d);
-        set(L_P, l[2], 3 * d), set(L_P + 1, l[4], 3 * d), set(L_P + 2, l[2] + d, 3 * d), set(L_P + 3, l[4] + d, 3 * d);
-        set(L_Q, l[2] + 2 * d, 3 * d), set(L_Q + 1, l[4] + 2 * d, 3 * d), set(L_Q + 2, l[10], d), set(L_Q + 3, l[11], d);
+        set(G_W1, g[ps::G_WX1], d), set(G_P, g[ps::G_WM], 3 * d), set(G_P + 1, g[ps::G_WM] + d, 3 * d);
+        for (int i = 0; i < 10; ++i) set(G_TAIL + i, g[ps::G_TAIL + i], d), set(L_TAIL + i, l[ps::L_TAIL + i], d);
+        set(L_W1, l[ps::L_WX1], d);
+        set(L_P, l[ps::L_WJI], 3 * d), set(L_P + 1, l[ps::L_WKJ], 3 * d);
+        set(L_P + 2, l[ps::L_WJI] + d, 3 * d), set(L_P + 3, l[ps::L_WKJ] + d, 3 * d);
+        set(L_Q, l[ps::L_WJI] + 2 * d, 3 * d), set(L_Q + 1, l[ps::L_WKJ] + 2 * d, 3 * d);
+        set(L_Q + 2, l[ps::L_WLR], d), set(L_Q + 3, l[ps::L_WLO], d);
         float4* dst = reinterpret_cast<float4*>(out + k * 2 * PACK_SLOTS * (int64_t)d * d);
 #define CALL(DD) hipLaunchKernelGGL((npack_kernel<DD>), dim3(PACK_SLOTS, 2), dim3(256), 0, st, J, dst);
         NARROW_DISPATCH(d, CALL)
@@ -376,8 +378,8 @@ int pack_all(int d, int64_t n_layer, const float* const* gparams, const float* c
 }
 
 inline void tail_fwd_params(NTailFwd& t, const float* const* tp, const Images& im, int64_t pair, int slot0) {
-    for (int i = 0; i < 10; ++i) t.img[i] = im.at(pair, slot0 + i, 0), t.b[i] = tp[10 + i];
-    t.w_out = tp[20], t.b_out = tp[21], t.w_att = tp[22];
+    for (int i = 0; i < 10; ++i) t.img[i] = im.at(pair, slot0 + i, 0), t.b[i] = tp[ps::T_B + i];
+    t.w_out = tp[ps::T_WOUT], t.b_out = tp[ps::T_BOUT], t.w_att = tp[ps::T_WATT];
 }
 
 }  // namespace
@@ -428,19 +430,20 @@ int narrow_stack::fwd(const int64_t* sizes, const int32_t* const* graph_idx, int
     const float* x = x0;
     for (int64_t k = 0; k < n_layer; ++k) {
         float* S = saved + k * L.pair;
-        const float* const* g = gparams + k * GP;
-        const float* const* l = lparams + k * LP;
+        const float* const* g = gparams + k * ps::G_COUNT;
+        const float* const* l = lparams + k * ps::L_COUNT;
         // ---------------- global layer
         {
             NPreFwd p = {};
-            p.x = x, p.img1 = im.at(k, G_W1, 0), p.b1 = g[1], p.nb = 2, p.imgp[0] = im.at(k, G_P, 0), p.imgp[1] = im.at(k, G_P + 1, 0);
+            p.x = x, p.img1 = im.at(k, G_W1, 0), p.b1 = g[ps::G_BX1], p.nb = 2, p.imgp[0] = im.at(k, G_P, 0), p.imgp[1] = im.at(k, G_P + 1, 0);
             p.x1 = S + L.g_x1, p.P = S + L.g_P, p.m = n;
             TRY(launch_pre_fwd(D, p, st));
-            TRY(launch_global_fwd(D, e_g, eg, ix.g_row, ix.g_col, S + L.g_P, g[2] + 2 * D, 3 * D, g[3], g[4], D, temp + L.t_msg, st));
+            TRY(launch_global_fwd(D, e_g, eg, ix.g_row, ix.g_col, S + L.g_P, g[ps::G_WM] + 2 * D, 3 * D, g[ps::G_BM], g[ps::G_WEA], D,
+                                  temp + L.t_msg, st));
             TRY(pamnet_segment_sum_f32(S + L.g_x2, S + L.g_x1, temp + L.t_msg, nullptr, nullptr, nullptr, nullptr, ix.g_ptr, n,
                                        d, stream));
             NTailFwd t = {};
-            tail_fwd_params(t, g + 5, im, k, G_TAIL);
+            tail_fwd_params(t, g + ps::G_TAIL, im, k, G_TAIL);
             t.x2 = S + L.g_x2, t.res_x = x, t.H0 = S + L.g_H0, t.R1 = S + L.g_R1, t.R2 = S + L.g_R2, t.R3 = S + L.g_R3;
             t.T = S + L.g_T, t.O = S + L.g_O, t.out = outs + (2 * k) * n, t.att = atts + (2 * k) * n, t.m = n;
             TRY(launch_tail_fwd(D, t, st));
@@ -449,16 +452,16 @@ int narrow_stack::fwd(const int64_t* sizes, const int32_t* const* graph_idx, int
         // ---------------- local layer
         {
             NPreFwd p = {};
-            p.x = x, p.img1 = im.at(k, L_W1, 0), p.b1 = l[1], p.nb = 4, p.m = n, p.x1 = S + L.l_x1, p.P = S + L.l_P;
+            p.x = x, p.img1 = im.at(k, L_W1, 0), p.b1 = l[ps::L_BX1], p.nb = 4, p.m = n, p.x1 = S + L.l_x1, p.P = S + L.l_P;
             for (int b = 0; b < 4; ++b) p.imgp[b] = im.at(k, L_P + b, 0);
             TRY(launch_pre_fwd(D, p, st));
             NPreFwd q = {};
             q.x = rbf_e, q.nb = 4, q.m = el, q.P = S + L.l_Q;
             for (int b = 0; b < 4; ++b) q.imgp[b] = im.at(k, L_Q + b, 0);
             TRY(launch_pre_fwd(D, q, st));
-            TRY(pamnet_narrow_local_gate_fwd_f32(S + L.l_P, S + L.l_Q, ix.l_row, ix.l_col, l[3], l[5], el, d, S + L.l_mji,
+            TRY(pamnet_narrow_local_gate_fwd_f32(S + L.l_P, S + L.l_Q, ix.l_row, ix.l_col, l[ps::L_BJI], l[ps::L_BKJ], el, d, S + L.l_mji,
                                                  S + L.l_mnb, stream));
-            TRY(launch_mlp2_fwd(D, e_sbf, tp, l[6], l[7], l[8], l[9], S + L.l_s, st));
+            TRY(launch_mlp2_fwd(D, e_sbf, tp, l[ps::L_WS1], l[ps::L_BS1], l[ps::L_WS2], l[ps::L_BS2], S + L.l_s, st));
             TRY(pamnet_segment_sum_f32(S + L.l_mother, nullptr, S + L.l_mnb, ix.tp_col, S + L.l_s, nullptr, nullptr, ix.tp_ptr,
                                        el, d, stream));
             if (el > 0) {
@@ -470,7 +473,7 @@ int narrow_stack::fwd(const int64_t* sizes, const int32_t* const* graph_idx, int
             TRY(pamnet_segment_sum_f32(S + L.l_x2, S + L.l_x1, temp + L.t_msg, nullptr, nullptr, nullptr, nullptr, ix.l_ptr, n,
                                        d, stream));
             NTailFwd t = {};
-            tail_fwd_params(t, l + 12, im, k, L_TAIL);
+            tail_fwd_params(t, l + ps::L_TAIL, im, k, L_TAIL);
             t.x2 = S + L.l_x2, t.res_x = x, t.H0 = S + L.l_H0, t.R1 = S + L.l_R1, t.R2 = S + L.l_R2, t.R3 = S + L.l_R3;
             t.T = S + L.l_T, t.O = S + L.l_O, t.out = outs + (2 * k + 1) * n, t.att = atts + (2 * k + 1) * n, t.m = n;
             TRY(launch_tail_fwd(D, t, st));
@@ -504,22 +507,23 @@ int narrow_stack::bwd(const int64_t* sizes, const int32_t* const* graph_idx, int
     const float* g_x = nullptr;              // gradient w.r.t. the node output of the layer being differentiated
     for (int64_t k = n_layer - 1; k >= 0; --k) {
         const float* S = saved + k * L.pair;
-        const float* const* g = gparams + k * GP;
-        const float* const* l = lparams + k * LP;
-        float* const* gg = ggrads + k * GP;
-        float* const* lg = lgrads + k * LP;
+        const float* const* g = gparams + k * ps::G_COUNT;
+        const float* const* l = lparams + k * ps::L_COUNT;
+        float* const* gg = ggrads + k * ps::G_COUNT;
+        float* const* lg = lgrads + k * ps::L_COUNT;
         const bool first = k == n_layer - 1;                 // first layer pair to be differentiated: overwrite d e_*
         const float* x_glob = k == 0 ? x0 : saved + (k - 1) * L.pair + L.l_R3;       // input of global layer k
         const float* x_loc = S + L.g_R3;                                              // input of local layer k
         // ---------------- local layer
         {
             NTailBwd t = {};
-            for (int i = 0; i < 10; ++i) t.img[i] = im.at(k, L_TAIL + i, 0), t.imgt[i] = im.at(k, L_TAIL + i, 1), t.b[i] = l[22 + i];
-            t.w_out = l[32], t.w_att = l[34];
+            for (int i = 0; i < 10; ++i) t.img[i] = im.at(k, L_TAIL + i, 0), t.imgt[i] = im.at(k, L_TAIL + i, 1), t.b[i] = l[ps::L_TAIL + ps::T_B + i];
+            t.w_out = l[ps::L_TAIL + ps::T_WOUT], t.w_att = l[ps::L_TAIL + ps::T_WATT];
             t.x2 = S + L.l_x2, t.H0 = S + L.l_H0, t.R1 = S + L.l_R1, t.R2 = S + L.l_R2, t.R3 = S + L.l_R3, t.T = S + L.l_T;
             t.O = S + L.l_O, t.g_x = g_x, t.g_out = d_outs + (2 * k + 1) * n, t.g_att = d_atts + (2 * k + 1) * n;
             t.d_x2 = d_x2, t.d_resx = d_resx, t.m = n;
-            TRY(launch_tail_bwd(D, t, lg + 12, lg + 22, lg[32], lg[33], lg[34], R, st));
+            float* const* lt = lg + ps::L_TAIL;
+            TRY(launch_tail_bwd(D, t, lt, lt + ps::T_B, lt[ps::T_WOUT], lt[ps::T_BOUT], lt[ps::T_WATT], R, st));
             // x2 = x1 + sum m,  m = Q_3 (m_ji + m_other)
             float* dQ = temp + L.t_dQ;
             float* dmm = temp + L.t_dmm;
@@ -532,18 +536,18 @@ int narrow_stack::bwd(const int64_t* sizes, const int32_t* const* graph_idx, int
             float* dmnb = temp + L.t_dmnb;
             TRY(pamnet_gather_mul_f32(ds, S + L.l_mnb, ix.tp_col, dmm, ix.tp_row, tp, d, stream));
             TRY(pamnet_segment_sum_f32(dmnb, nullptr, S + L.l_s, nullptr, dmm, ix.tp_row, ix.tpT_perm, ix.tpT_ptr, el, d, stream));
-            TRY(launch_mlp2_bwd(D, e_sbf, tp, l[6], l[7], l[8], l[9], ds, d_sbf, first ? 0 : 1, R, lg[6], lg[7], lg[8],
-                                lg[9], st));
+            TRY(launch_mlp2_bwd(D, e_sbf, tp, l[ps::L_WS1], l[ps::L_BS1], l[ps::L_WS2], l[ps::L_BS2], ds, d_sbf, first ? 0 : 1, R,
+                                lg[ps::L_WS1], lg[ps::L_BS1], lg[ps::L_WS2], lg[ps::L_BS2], st));
             // gates: dz_l [el, 2d] and dQ blocks 0..2 (block 3 is already there)
             float* dzl = temp + L.t_dzl;
-            TRY(launch_gate_bwd(D, S + L.l_P, S + L.l_Q, ix.l_row, ix.l_col, l[3], l[5], el, dmm, dmnb, dzl, dQ, st));
+            TRY(launch_gate_bwd(D, S + L.l_P, S + L.l_Q, ix.l_row, ix.l_col, l[ps::L_BJI], l[ps::L_BKJ], el, dmm, dmnb, dzl, dQ, st));
             // node side: d P_i over the edges into i, d P_j over the edges out of j
             float* dpi = temp + L.t_dpi;
             float* dpj = temp + L.t_dpj;
             TRY(pamnet_segment_sum_f32(dpi, nullptr, dzl, nullptr, nullptr, nullptr, nullptr, ix.l_ptr, n, 2 * d, stream));
             TRY(pamnet_segment_sum_f32(dpj, nullptr, dzl, nullptr, nullptr, nullptr, ix.lT_perm, ix.lT_ptr, n, 2 * d, stream));
             // edge side: the four projection blocks of Q; their partial rows interleave so that one reduce serves all
-            const float* Wq[4] = {l[2] + 2 * D, l[4] + 2 * D, l[10], l[11]};
+            const float* Wq[4] = {l[ps::L_WJI] + 2 * D, l[ps::L_WKJ] + 2 * D, l[ps::L_WLR], l[ps::L_WLO]};
             const int ldq[4] = {3 * D, 3 * D, D, D};
             const int qs = D * D + D;
             float* qpart = nullptr;
@@ -568,47 +572,48 @@ int narrow_stack::bwd(const int64_t* sizes, const int32_t* const* graph_idx, int
             }
             {
                 SegTable& T = R.T;
-                T.mat(lg[2] + 2 * D, 0 * qs, D, D, D, 3 * D);
-                T.vec(lg[3], 0 * qs + D * D, D);                 // d b_ji = column sums of d z_ji
-                T.mat(lg[4] + 2 * D, 1 * qs, D, D, D, 3 * D);
-                T.vec(lg[5], 1 * qs + D * D, D);
-                T.mat(lg[10], 2 * qs, D, D, D, D);
-                T.mat(lg[11], 3 * qs, D, D, D, D);
+                T.mat(lg[ps::L_WJI] + 2 * D, 0 * qs, D, D, D, 3 * D);
+                T.vec(lg[ps::L_BJI], 0 * qs + D * D, D);                 // d b_ji = column sums of d z_ji
+                T.mat(lg[ps::L_WKJ] + 2 * D, 1 * qs, D, D, D, 3 * D);
+                T.vec(lg[ps::L_BKJ], 1 * qs + D * D, D);
+                T.mat(lg[ps::L_WLR], 2 * qs, D, D, D, D);
+                T.mat(lg[ps::L_WLO], 3 * qs, D, D, D, D);
             }
             NPreBwd p = {};
-            p.x = x_loc, p.x1 = S + L.l_x1, p.img1 = im.at(k, L_W1, 0), p.img1t = im.at(k, L_W1, 1), p.b1 = l[1], p.nb = 4, p.m = n;
+            p.x = x_loc, p.x1 = S + L.l_x1, p.img1 = im.at(k, L_W1, 0), p.img1t = im.at(k, L_W1, 1), p.b1 = l[ps::L_BX1], p.nb = 4, p.m = n;
             for (int b = 0; b < 4; ++b) p.imgpt[b] = im.at(k, L_P + b, 1);
             p.dP[0] = dpi, p.dP[1] = dpi + D, p.dP[2] = dpj, p.dP[3] = dpj + D;
             p.lddp[0] = p.lddp[1] = p.lddp[2] = p.lddp[3] = 2 * D;
             p.d_direct = d_x2, p.d_add = d_resx, p.dx = gx[0];
-            float* gWp[4] = {lg[2], lg[4], lg[2] + D, lg[4] + D};
+            float* gWp[4] = {lg[ps::L_WJI], lg[ps::L_WKJ], lg[ps::L_WJI] + D, lg[ps::L_WKJ] + D};
             const int ldg[4] = {3 * D, 3 * D, 3 * D, 3 * D};
-            TRY(launch_pre_bwd(D, p, gWp, ldg, lg[0], lg[1], R, st));
+            TRY(launch_pre_bwd(D, p, gWp, ldg, lg[ps::L_WX1], lg[ps::L_BX1], R, st));
         }
         // ---------------- global layer
         {
             NTailBwd t = {};
-            for (int i = 0; i < 10; ++i) t.img[i] = im.at(k, G_TAIL + i, 0), t.imgt[i] = im.at(k, G_TAIL + i, 1), t.b[i] = g[15 + i];
-            t.w_out = g[25], t.w_att = g[27];
+            for (int i = 0; i < 10; ++i) t.img[i] = im.at(k, G_TAIL + i, 0), t.imgt[i] = im.at(k, G_TAIL + i, 1), t.b[i] = g[ps::G_TAIL + ps::T_B + i];
+            t.w_out = g[ps::G_TAIL + ps::T_WOUT], t.w_att = g[ps::G_TAIL + ps::T_WATT];
             t.x2 = S + L.g_x2, t.H0 = S + L.g_H0, t.R1 = S + L.g_R1, t.R2 = S + L.g_R2, t.R3 = S + L.g_R3, t.T = S + L.g_T;
             t.O = S + L.g_O, t.g_x = gx[0], t.g_out = d_outs + (2 * k) * n, t.g_att = d_atts + (2 * k) * n;
             t.d_x2 = d_x2, t.d_resx = d_resx, t.m = n;
-            TRY(launch_tail_bwd(D, t, gg + 5, gg + 15, gg[25], gg[26], gg[27], R, st));
+            float* const* gt = gg + ps::G_TAIL;
+            TRY(launch_tail_bwd(D, t, gt, gt + ps::T_B, gt[ps::T_WOUT], gt[ps::T_BOUT], gt[ps::T_WATT], R, st));
             float* dz = temp + L.t_dz;
-            TRY(launch_global_bwd(D, e_g, eg, ix.g_row, ix.g_col, S + L.g_P, g[2] + 2 * D, 3 * D, g[3], g[4], D, d_x2, dz, d_eg,
-                                  first ? 0 : 1, R, gg[2] + 2 * D, 3 * D, gg[4], gg[3], st));
+            TRY(launch_global_bwd(D, e_g, eg, ix.g_row, ix.g_col, S + L.g_P, g[ps::G_WM] + 2 * D, 3 * D, g[ps::G_BM], g[ps::G_WEA], D,
+                                  d_x2, dz, d_eg, first ? 0 : 1, R, gg[ps::G_WM] + 2 * D, 3 * D, gg[ps::G_WEA], gg[ps::G_BM], st));
             float* dpi = temp + L.t_dpi;
             float* dpj = temp + L.t_dpj;
             TRY(pamnet_segment_sum_f32(dpi, nullptr, dz, nullptr, nullptr, nullptr, nullptr, ix.g_ptr, n, d, stream));
             TRY(pamnet_segment_sum_f32(dpj, nullptr, dz, nullptr, nullptr, nullptr, ix.gT_perm, ix.gT_ptr, n, d, stream));
             NPreBwd p = {};
-            p.x = x_glob, p.x1 = S + L.g_x1, p.img1 = im.at(k, G_W1, 0), p.img1t = im.at(k, G_W1, 1), p.b1 = g[1], p.nb = 2, p.m = n;
+            p.x = x_glob, p.x1 = S + L.g_x1, p.img1 = im.at(k, G_W1, 0), p.img1t = im.at(k, G_W1, 1), p.b1 = g[ps::G_BX1], p.nb = 2, p.m = n;
             p.imgpt[0] = im.at(k, G_P, 1), p.imgpt[1] = im.at(k, G_P + 1, 1);
             p.dP[0] = dpi, p.dP[1] = dpj, p.lddp[0] = p.lddp[1] = D;
             p.d_direct = d_x2, p.d_add = d_resx, p.dx = k == 0 ? d_x0 : gx[1];
-            float* gWp[2] = {gg[2], gg[2] + D};
+            float* gWp[2] = {gg[ps::G_WM], gg[ps::G_WM] + D};
             const int ldg[2] = {3 * D, 3 * D};
-            TRY(launch_pre_bwd(D, p, gWp, ldg, gg[0], gg[1], R, st));
+            TRY(launch_pre_bwd(D, p, gWp, ldg, gg[ps::G_WX1], gg[ps::G_BX1], R, st));
             g_x = gx[1];
         }
         TRY(R.flush());                   // this pair's gradients are complete before its event is recorded

@@ -75,7 +75,7 @@ constexpr int BMN = 16;                       // rows per workgroup
 constexpr int SLOT = BMN * LDT;               // floats per LDS slot
 constexpr int TWG = 512;                      // 8 waves
 // more row tiles than CUs: a CU gets several workgroups in turn -- the lean chain forms (co-resident workgroups) from here
-constexpr unsigned LEAN_FROM_TILES = 256;
+constexpr unsigned LEAN_FROM_TILES = (unsigned)PARKED_TILES_MAX;
 // PAMNET_CHAIN_LEAN=0: never, 1: forward only (default: both directions) -- read once, for A/B timing
 inline int lean_mode() {
     static const int v = [] { const char* e = getenv("PAMNET_CHAIN_LEAN"); return e ? atoi(e) : 2; }();
@@ -1891,6 +1891,30 @@ extern "C" int pamnet_node_tail_fwd_f32(const float* x2, const float* res_x, int
                            next_wp, next_ldwp, next_nblk, next_Zx1, next_x1, next_P, packed, nullptr, 0, stream);
 }
 
+// The deferred-heads launch with an optional rider and an optional aggregation: the body of the two entry points below.
+static int tail_fwd_ride(const float* x2, const float* res_x, int64_t n, const float* const* weights,
+                         const float* const* biases, const float* w_out, const float* b_out, const float* w_att, float* Z,
+                         float* R, float* x_out, const float* next_Wx1, const float* next_bx1,
+                         const float* const* next_wp, int64_t next_ldwp, int64_t next_nblk, float* next_Zx1, float* next_x1,
+                         float* next_P, const float* mlp_x, int64_t mlp_rows, int64_t mlp_tile0, int64_t mlp_ntiles,
+                         const float* const* mlp, float* const* mlp_out, int64_t rider_wgs, int32_t packed,
+                         const pamnet_local_agg* agg, pamnet_stream_t stream) {
+    if (mlp_rows < 0 || mlp_tile0 < 0 || mlp_ntiles < 0 || rider_wgs < 0 || (packed != 1 && packed != 2)) return PAMNET_EINVAL;
+    if (mlp_ntiles == 0 || rider_wgs == 0)
+        return tail_fwd_launch(x2, res_x, n, weights, biases, w_out, b_out, w_att, Z, R, x_out, nullptr, nullptr, next_Wx1,
+                               next_bx1, next_wp, next_ldwp, next_nblk, next_Zx1, next_x1, next_P, packed, nullptr, 0, stream, agg);
+    if (!mlp_x || !mlp || !mlp_out || !mlp[0] || !mlp[1] || !mlp[2] || !mlp[3] || !mlp_out[2]) return PAMNET_ENULL;
+    if (n == 0) return PAMNET_EINVAL;                        // no chain to ride on
+    Mlp2Rider rd{};
+    rd.x = mlp_x, rd.m = mlp_rows;
+    rd.set = edge::Mlp2Set{mlp[0], mlp[1], mlp[2], mlp[3], mlp_out[0], mlp_out[1], mlp_out[2]};
+    rd.tile0 = (int)mlp_tile0, rd.ntiles = (int)mlp_ntiles;
+    if (rider_wgs > mlp_ntiles) rider_wgs = mlp_ntiles;       // never more workgroups than tiles
+    return tail_fwd_launch(x2, res_x, n, weights, biases, w_out, b_out, w_att, Z, R, x_out, nullptr, nullptr, next_Wx1,
+                           next_bx1, next_wp, next_ldwp, next_nblk, next_Zx1, next_x1, next_P, packed, &rd, (int)rider_wgs, stream,
+                           agg);
+}
+
 // The same launch (packed weight images, deferred heads: out = att = null) with a rider: row tiles
 // [mlp_tile0, mlp_tile0 + mlp_ntiles) (16 rows each) of the two-layer MLP  y = SiLU(W2 SiLU(W1 x + b1) + b2)  over
 // mlp_x [mlp_rows, 128] are computed by `rider_wgs` extra workgroups (mlp = {W1, b1, W2, b2}; mlp_out = {z1, z2, y},
@@ -1903,19 +1927,9 @@ extern "C" int pamnet_node_tail_fwd_rider_f32(const float* x2, const float* res_
                                               float* next_P, const float* mlp_x, int64_t mlp_rows, int64_t mlp_tile0,
                                               int64_t mlp_ntiles, const float* const* mlp, float* const* mlp_out,
                                               int64_t rider_wgs, int32_t packed, pamnet_stream_t stream) {
-    if (mlp_rows < 0 || mlp_tile0 < 0 || mlp_ntiles < 0 || rider_wgs < 0 || (packed != 1 && packed != 2)) return PAMNET_EINVAL;
-    if (mlp_ntiles == 0 || rider_wgs == 0)
-        return tail_fwd_launch(x2, res_x, n, weights, biases, w_out, b_out, w_att, Z, R, x_out, nullptr, nullptr, next_Wx1,
-                               next_bx1, next_wp, next_ldwp, next_nblk, next_Zx1, next_x1, next_P, packed, nullptr, 0, stream);
-    if (!mlp_x || !mlp || !mlp_out || !mlp[0] || !mlp[1] || !mlp[2] || !mlp[3] || !mlp_out[2]) return PAMNET_ENULL;
-    if (n == 0) return PAMNET_EINVAL;                        // no chain to ride on
-    Mlp2Rider rd{};
-    rd.x = mlp_x, rd.m = mlp_rows;
-    rd.set = edge::Mlp2Set{mlp[0], mlp[1], mlp[2], mlp[3], mlp_out[0], mlp_out[1], mlp_out[2]};
-    rd.tile0 = (int)mlp_tile0, rd.ntiles = (int)mlp_ntiles;
-    if (rider_wgs > mlp_ntiles) rider_wgs = mlp_ntiles;       // never more workgroups than tiles
-    return tail_fwd_launch(x2, res_x, n, weights, biases, w_out, b_out, w_att, Z, R, x_out, nullptr, nullptr, next_Wx1,
-                           next_bx1, next_wp, next_ldwp, next_nblk, next_Zx1, next_x1, next_P, packed, &rd, (int)rider_wgs, stream);
+    return tail_fwd_ride(x2, res_x, n, weights, biases, w_out, b_out, w_att, Z, R, x_out, next_Wx1, next_bx1, next_wp, next_ldwp,
+                         next_nblk, next_Zx1, next_x1, next_P, mlp_x, mlp_rows, mlp_tile0, mlp_ntiles, mlp, mlp_out, rider_wgs,
+                         packed, nullptr, stream);
 }
 
 // pamnet_node_tail_fwd_rider_f32 (mlp_ntiles = 0: without riders) whose chain input x2 is FORMED by the launch -- `agg` holds the
@@ -1929,20 +1943,9 @@ extern "C" int pamnet_node_tail_fwd_agg_f32(float* x2, const float* res_x, int64
                                             const float* const* mlp, float* const* mlp_out, int64_t rider_wgs, int32_t packed,
                                             const pamnet_local_agg* agg, pamnet_stream_t stream) {
     if (!agg) return PAMNET_ENULL;
-    if (mlp_rows < 0 || mlp_tile0 < 0 || mlp_ntiles < 0 || rider_wgs < 0 || (packed != 1 && packed != 2)) return PAMNET_EINVAL;
-    if (mlp_ntiles == 0 || rider_wgs == 0)
-        return tail_fwd_launch(x2, res_x, n, weights, biases, w_out, b_out, w_att, Z, R, x_out, nullptr, nullptr, next_Wx1,
-                               next_bx1, next_wp, next_ldwp, next_nblk, next_Zx1, next_x1, next_P, packed, nullptr, 0, stream, agg);
-    if (!mlp_x || !mlp || !mlp_out || !mlp[0] || !mlp[1] || !mlp[2] || !mlp[3] || !mlp_out[2]) return PAMNET_ENULL;
-    if (n == 0) return PAMNET_EINVAL;
-    Mlp2Rider rd{};
-    rd.x = mlp_x, rd.m = mlp_rows;
-    rd.set = edge::Mlp2Set{mlp[0], mlp[1], mlp[2], mlp[3], mlp_out[0], mlp_out[1], mlp_out[2]};
-    rd.tile0 = (int)mlp_tile0, rd.ntiles = (int)mlp_ntiles;
-    if (rider_wgs > mlp_ntiles) rider_wgs = mlp_ntiles;
-    return tail_fwd_launch(x2, res_x, n, weights, biases, w_out, b_out, w_att, Z, R, x_out, nullptr, nullptr, next_Wx1,
-                           next_bx1, next_wp, next_ldwp, next_nblk, next_Zx1, next_x1, next_P, packed, &rd, (int)rider_wgs, stream,
-                           agg);
+    return tail_fwd_ride(x2, res_x, n, weights, biases, w_out, b_out, w_att, Z, R, x_out, next_Wx1, next_bx1, next_wp, next_ldwp,
+                         next_nblk, next_Zx1, next_x1, next_P, mlp_x, mlp_rows, mlp_tile0, mlp_ntiles, mlp, mlp_out, rider_wgs,
+                         packed, agg, stream);
 }
 
 extern "C" int pamnet_node_heads_fwd_f32(int64_t n_layers, const float* const* x_out, const float* const* weights,

@@ -31,13 +31,13 @@ def stack_ctx(global_layers):
     return ctx
 
 
-def global_params(layer):
+def global_params(layer):      # slot order: csrc/common.h pslot::Global
     lin_m = layer.mlp_m[0][0]
     return [layer.mlp_x1[0][0].weight, layer.mlp_x1[0][0].bias, lin_m.weight, lin_m.bias,
             layer.W_edge_attr.weight] + tail_params(layer)
 
 
-def local_params(layer):
+def local_params(layer):       # slot order: csrc/common.h pslot::Local
     lin_ji = layer.mlp_m_ji[0][0]
     lin_kj = (layer.mlp_m_jj if layer.small else layer.mlp_m_kj)[0][0]
     s1, s2 = layer.mlp_sbf[0][0], layer.mlp_sbf[1][0]

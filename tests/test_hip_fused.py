@@ -641,3 +641,86 @@ def test_riders_of_the_bf16_forward_chain(dev, tile0, ntiles, wgs):
     for got, want in zip(mo, ref):
         assert torch.equal(got[r0:r1], want[r0:r1])
         assert bool((got[:r0] == 7.0).all()) and bool((got[r1:] == 7.0).all())
+
+
+_GUARD_FLOATS, _GUARD_BITS = 4096, 0x7FC5A3E1        # a NaN payload: no kernel computes it (an arithmetic NaN is 0x7FC00000)
+
+
+def _step_in_guarded_arenas(case):
+    """One Trainer.forward_backward of a d = 128, two-layer model whose layer-stack arenas are exactly the floats
+    pamnet_stack_workspace reports, each followed by _GUARD_FLOATS floats of _GUARD_BITS inside the same allocation.  Returns
+    the failures (empty: every guard is intact, both arenas were written, the loss is finite)."""
+    import ctypes
+    import models
+    from pamnet_amd import lib, synth
+    from pamnet_amd.train import Trainer
+    dev = torch.device('cuda:0')
+    torch.manual_seed(3)
+    if case == 'qm9':
+        cfg = models.Config(dataset='QM9', dim=D, n_layer=2, cutoff_l=5.0, cutoff_g=5.0)
+        b = synth.qm9_batch(5, 0, 4).to(dev)
+    else:
+        cfg = models.Config(dataset='PDBbind', dim=D, n_layer=2, cutoff_l=2.0, cutoff_g=6.0)
+        b = synth.pdbbind_batch(3, 0, 2, n_pocket=60, n_ligand=12).to(dev)
+    tr = Trainer(models.PAMNet(cfg).to(dev), loss='l1', max_grad_norm=None, ema_decay=None, lr=1e-3)
+    arenas, calls, real = {}, [], lib.call
+
+    def call(name, *args):
+        if name in ('pamnet_stack_fwd_f32', 'pamnet_stack_bwd_f32'):          # (sizes, idx, L, d, 6 tensors / tables, saved, temp, ...)
+            args = list(args)
+            if name == 'pamnet_stack_fwd_f32':
+                need = (ctypes.c_int64 * 2)()
+                real('pamnet_stack_workspace', *[int(v) for v in args[0]], args[2], args[3], ctypes.addressof(need),
+                     ctypes.addressof(need) + 8)
+                for k, key in enumerate(('saved', 'temp')):
+                    arenas[key] = (torch.full((int(need[k]) + _GUARD_FLOATS,), _GUARD_BITS, dtype=torch.int32, device=dev),
+                                   int(need[k]))
+            args[10], args[11] = arenas['saved'][0].data_ptr(), arenas['temp'][0].data_ptr()
+            calls.append((name, [int(v) for v in args[0]]))
+        return real(name, *args)
+
+    lib.call = call
+    try:
+        loss = tr.forward_backward(b)
+        torch.cuda.synchronize()
+    finally:
+        lib.call = real
+    bad = []
+    if [c[0] for c in calls] != ['pamnet_stack_fwd_f32', 'pamnet_stack_bwd_f32']:
+        bad.append('engine calls: %r' % (calls,))
+    else:
+        n, eg, el, tp = calls[0][1]
+        if not ((n + 15) // 16 <= 256 - 80 and tp > 0):                      # the riders plan (test_hip_model.py PLAN_BOUNDS)
+            bad.append('not the riders plan: n = %d, tp = %d' % (n, tp))
+    for key, (buf, floats) in arenas.items():
+        if not bool((buf[floats:] == _GUARD_BITS).all()):
+            hit = torch.nonzero(buf[floats:] != _GUARD_BITS).flatten()
+            bad.append('%s: %d guard floats overwritten, the first %d past the %d reported' % (key, hit.numel(), int(hit[0]), floats))
+        if floats and bool((buf[:floats] == _GUARD_BITS).all()):
+            bad.append('%s: never written' % key)
+    if not np.isfinite(float(loss)) or not bool(torch.isfinite(tr.fp.grad).all()):
+        bad.append('loss / gradient not finite')
+    return bad
+
+
+def test_engine_writes_stay_inside_the_reported_arenas():
+    """The d = 128 layer stack carves `saved` and `temp` by the walk whose end offsets pamnet_stack_workspace reports
+    (csrc/engine.hip make_arena).  A caller who allocates exactly those floats must see nothing written behind them:
+    StackPlan.temp_arena's 25 % slack would hide a slab missing from the count.  QM9, 4 molecules, two layers, riders plan:
+    the smallest stack in which the merged weight-gradient launch and both fused backward launches exist."""
+    assert _step_in_guarded_arenas('qm9') == []
+
+
+def test_engine_writes_stay_inside_the_reported_arenas_edge_wgrad_recompute():
+    """The same with PAMNET_EDGE_WGRAD=1 PAMNET_EDGE_RECOMPUTE=1 on a small PDBbind batch, in a process of its own (the switches
+    are read once): the layout variant no default small batch reaches -- partial tiles of the edge backward's own weight
+    gradients and the recompute launch's discarded node output in `temp`, node planes instead of edge rows in `saved`."""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import sys; sys.path.insert(0, %r)\nimport conftest, test_hip_fused as T\n"
+            "bad = T._step_in_guarded_arenas('pdbbind')\nprint('GUARDS', bad)\nsys.exit(1 if bad else 0)\n" % here)
+    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, PAMNET_EDGE_WGRAD='1', PAMNET_EDGE_RECOMPUTE='1'))
+    assert r.returncode == 0 and 'GUARDS []' in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

@@ -681,11 +681,11 @@ def test_fused_engine_fresh_inputs_vs_oracle(dev, case):
 # The d = 128 layer-stack engine picks its launch plan from the batch: from its row tiles, ceil(n / 16), and its global
 # edges E_g.  The bounds, each with the function it comes from:
 PLAN_BOUNDS = {
-    'rider_tiles': 256 - 80,        # engine.hip riders_fit(): the chain launches carry riders up to RIDER_MAX_SLOTS - 80 tiles
-    'bf16_tiles': 256,              # engine.hip chain_bf16_tiles(), fuse_local_agg(): bf16x6 chains, fused local aggregation
-    'lean_from_tiles': 256,         # node_tail.hip LEAN_FROM_TILES: the lean fp32 chains above this many tiles
-    'edge_wgrad_edges': 256 * 512,  # engine.hip edge_wgrad(), edge_agg.hip agg_pp(): from this many global edges on, the
-}                                   # ping-pong edge forward and the edge backward that forms its own weight gradients
+    'rider_tiles': 256 - 80,        # engine.hip make_plan(): the chain launches carry riders up to RIDER_MAX_SLOTS - 80 tiles
+    'bf16_tiles': 256,              # common.h PARKED_TILES_MAX (engine.hip make_plan()): bf16x6 chains, fused local aggregation
+    'lean_from_tiles': 256,         # common.h PARKED_TILES_MAX (node_tail.hip LEAN_FROM_TILES): the lean fp32 chains above it
+    'edge_wgrad_edges': 256 * 512,  # common.h STREAMED_EDGES_FROM (engine.hip make_plan(), edge_agg.hip agg_pp()): from this
+}                                   # many global edges on, the ping-pong edge forward and the edge backward that forms its own weight gradients
 
 
 def _launch_plan(gc):
