@@ -45,7 +45,7 @@ typedef void* pamnet_stream_t; /* hipStream_t */
 
 /* Library / ABI version (bumped on any signature change).  pamnet_abi_version() returns the PAMNET_ABI_VERSION the library
  * was built against; a binding compares it with this header's (pamnet_amd/lib.py load(): a stale .so fails loudly). */
-#define PAMNET_ABI_VERSION 17
+#define PAMNET_ABI_VERSION 18
 int pamnet_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------------
@@ -330,6 +330,24 @@ int pamnet_mol_graph_fill_i32(const float* pos, const int32_t* gptr, int64_t n, 
                               const int32_t* dst, int64_t n_bonds, float cutoff_g, int32_t with_triplets, int32_t need_grad,
                               const int32_t* mol_tot, int64_t eg_cap, int64_t tp_cap, const pamnet_mol_graph_out* out,
                               pamnet_stream_t stream);
+/* Bond-free form of the same builder: no bond list is given, the local graph is the radius graph at cutoff_l inside every
+ * molecule -- all ordered pairs (j -> i), i != j, |pos_i - pos_j| <= cutoff_l, by the rule and fp32 arithmetic of
+ * pamnet_radius_count/fill_i32, no neighbour cap -- stored by target i, then source j; the global graph is the one at
+ * cutoff_g as above (either cutoff may be the larger; both must be positive).  Limits as above: <= 64 atoms and <= 256
+ * directed LOCAL edges per molecule (violation bits 1 / 2).  Every array is bit-identical to what the step-by-step entry
+ * points give for that edge list (the transposed local list is the reverse-edge index: lT_ptr = l_ptr).
+ *   count: mol_tot [n_graphs, 4] = (global edges, triplet + pair rows, LOCAL EDGES, violation bits) per molecule;
+ *          totals [4] (zeroed by the caller) += (global edges, triplet + pair rows, violation bits (OR), local edges);
+ *   fill:  n_local = totals[3] of the count launch over the same inputs; sizes as above with n_bonds = n_local.  A molecule's
+ *          first local edge is the sum of the preceding molecules' counts in mol_tot; a molecule whose edges would not fit
+ *          in n_local writes nothing. */
+int pamnet_mol_graph_free_count_i32(const float* pos, const int32_t* gptr, int64_t n, int64_t n_graphs, float cutoff_l,
+                                    float cutoff_g, int32_t with_triplets, int32_t* mol_tot, int32_t* totals,
+                                    pamnet_stream_t stream);
+int pamnet_mol_graph_free_fill_i32(const float* pos, const int32_t* gptr, int64_t n, int64_t n_graphs, int64_t n_local,
+                                   float cutoff_l, float cutoff_g, int32_t with_triplets, int32_t need_grad,
+                                   const int32_t* mol_tot, int64_t eg_cap, int64_t tp_cap, const pamnet_mol_graph_out* out,
+                                   pamnet_stream_t stream);
 
 int pamnet_graph_plan(const pamnet_graph_desc* desc, int64_t* layout /* [PAMNET_GRAPH_FIELDS] */, int64_t* arena_ints);
 int pamnet_graph_build_i32(const pamnet_graph_desc* desc, int32_t* arena, float* sbf /* [tp, 42], nullable */,

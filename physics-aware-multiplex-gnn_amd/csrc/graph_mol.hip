@@ -16,6 +16,12 @@
 // bonds grouped by molecule in batch order (what torch_geometric's collation and pamnet_collate_f32 produce), both ends
 // of a bond in the same molecule, no molecule over the caps below.  Self loops must have been stripped (the ingest launch
 // notes them).
+//
+// Bond-free form (pamnet_mol_graph_free_*): no bond list is given, the local graph is the radius graph at cutoff_l.  The
+// atoms' local adjacency masks come out of the same loop as the cutoff_g masks, and their bits -- target ascending, source
+// ascending -- ARE the bonds in CSR order of their targets: no input reads, no bond range, no stray-bond check; everything
+// behind that point runs unchanged.  The local edge count of a molecule is data dependent: the count launch leaves it in
+// mol_tot[g, 2] (where the bonded form keeps the first bond) and the fill launch sums the preceding molecules' counts.
 #include "common.h"
 #include "geom_core.h"
 
@@ -29,6 +35,7 @@ struct MolIn {
     int64_t n, n_graphs, n_bonds;
     float cutoff_g;
     int with_triplets, need_grad;
+    float cutoff_l;                                           // bond-free form only
 };
 
 __device__ __forceinline__ int wave_sum(int v) {
@@ -75,7 +82,20 @@ __device__ __forceinline__ void bond_range(const int32_t* __restrict__ dst, int 
     b1 = __builtin_amdgcn_readlane(lo, 32);
 }
 
-template <bool FILL>
+// Adjacency masks of this lane's atom inside its molecule at cutoff_g (and, bond-free form, at cutoff_l): the rule and
+// arithmetic of pamnet_radius_count/fill_i32 (self excluded, d <= r on the rounded fp32 distance).
+template <bool FREE>
+__device__ __forceinline__ void radius_masks(float xi, float yi, float zi, int lane, int na, float cutoff_g, float cutoff_l,
+                                             unsigned long long& mask, unsigned long long& lmask) {
+    mask = lmask = 0ull;
+    for (int j = 0; j < na; ++j) {
+        const float d = dist3_xyz(xi, yi, zi, lane_value(xi, j), lane_value(yi, j), lane_value(zi, j));
+        if (j != lane && lane < na && d <= cutoff_g) mask |= 1ull << j;
+        if (FREE && j != lane && lane < na && d <= cutoff_l) lmask |= 1ull << j;
+    }
+}
+
+template <bool FILL, bool FREE>
 __global__ __launch_bounds__(64) void mol_graph_kernel(MolIn in, int32_t* __restrict__ mol_tot,
                                                        int32_t* __restrict__ totals, pamnet_mol_graph_out out,
                                                        int64_t eg_cap, int64_t tp_cap) {
@@ -89,9 +109,14 @@ __global__ __launch_bounds__(64) void mol_graph_kernel(MolIn in, int32_t* __rest
     const int g = blockIdx.x, lane = threadIdx.x;
     const int a0 = in.gptr[g], a1 = in.gptr[g + 1], na = a1 - a0;
     const bool last = g == (int)in.n_graphs - 1;
-    int b0, b1;
+    int b0 = 0, b1 = 0;
     int se = 0, st = 0;
-    if constexpr (FILL) {
+    if constexpr (FILL && FREE) {
+        int sl = 0;                                           // (the local edges before this molecule: data dependent too)
+        for (int q = lane; q < g; q += 64) se += mol_tot[4 * q], st += mol_tot[4 * q + 1], sl += mol_tot[4 * q + 2];
+        b0 = b1 = wave_sum(sl);
+    } else if constexpr (FREE) {
+    } else if constexpr (FILL) {
         // the count launch left every molecule's first bond and totals: this molecule's slices start at the sums over the
         // preceding molecules (all of these loads are independent of each other: one round trip)
         b0 = mol_tot[4 * g + 2];
@@ -100,14 +125,14 @@ __global__ __launch_bounds__(64) void mol_graph_kernel(MolIn in, int32_t* __rest
     } else {
         bond_range(in.dst, (int)in.n_bonds, a0, a1, lane, b0, b1);
     }
-    const int nb = b1 - b0;
+    int nb = b1 - b0;
     int flags = 0;
     if (na < 0 || na > MOL_ATOMS) flags |= 1;
     if (nb < 0 || nb > MOL_BONDS) flags |= 2;
     if (flags) {                                              // wave-uniform
         if (!FILL && lane == 0) {
             mol_tot[4 * g] = mol_tot[4 * g + 1] = 0;
-            mol_tot[4 * g + 2] = b0;
+            mol_tot[4 * g + 2] = FREE ? 0 : b0;
             mol_tot[4 * g + 3] = flags;
             atomicOr(&totals[2], flags);
         }
@@ -119,11 +144,34 @@ __global__ __launch_bounds__(64) void mol_graph_kernel(MolIn in, int32_t* __rest
         xi = in.pos[3 * a], yi = in.pos[3 * a + 1], zi = in.pos[3 * a + 2];
         px[lane] = xi, py[lane] = yi, pz[lane] = zi;
     }
+    unsigned long long mask = 0ull, lmask = 0ull;
+    if constexpr (FREE) {
+        // ---- both radius graphs' adjacency masks; the local one's bits are the bonds in CSR order of their targets
+        radius_masks<true>(xi, yi, zi, lane, na, in.cutoff_g, in.cutoff_l, mask, lmask);
+        const int ldeg = __popcll(lmask);
+        const int linc = wave_incl(ldeg, lane);
+        nb = __shfl(linc, 63, 64);
+        if (nb > MOL_BONDS || (FILL && (int64_t)b0 + nb > in.n_bonds)) {     // wave-uniform; FILL: not the count launch's total
+            if (!FILL && lane == 0) {
+                mol_tot[4 * g] = mol_tot[4 * g + 1] = mol_tot[4 * g + 2] = 0;
+                mol_tot[4 * g + 3] = 2;
+                atomicOr(&totals[2], 2);
+            }
+            return;
+        }
+        int w = linc - ldeg;
+        if (lane < na) lptr[lane] = w;
+        if (lane == 0) lptr[na] = nb;
+        for (unsigned long long m = lmask; m; m &= m - 1) {
+            l_src[w] = __ffsll((long long)m) - 1, l_dst[w] = lane;
+            ++w;
+        }
+    }
     const int nchunk = (nb + 63) >> 6;
     int bs[MOL_CHUNKS], bd[MOL_CHUNKS];                       // bond c * 64 + lane in input order (-1: none)
     bool stray = false;
 #pragma unroll
-    for (int c = 0; c < MOL_CHUNKS; ++c) {
+    for (int c = 0; c < (FREE ? 0 : MOL_CHUNKS); ++c) {
         const int k = c * 64 + lane;
         bs[c] = bd[c] = -1;
         if (k < nb) {
@@ -136,7 +184,7 @@ __global__ __launch_bounds__(64) void mol_graph_kernel(MolIn in, int32_t* __rest
 
     // ---- bonds in CSR order of their targets, stable (as the counting sort of pamnet_csr_from_keys_i32): for atom i the
     // bonds with target i are a ballot; a bond's slot = bonds of earlier atoms + earlier such bonds.  No memory traffic.
-    {
+    if constexpr (!FREE) {
         int run = 0, mine = 0;
         for (int i = 0; i < na; ++i) {
             if (lane == i) mine = run;
@@ -205,11 +253,7 @@ __global__ __launch_bounds__(64) void mol_graph_kernel(MolIn in, int32_t* __rest
     const int tp_m = carry;
 
     // ---- radius graph inside the molecule: adjacency masks + degrees
-    unsigned long long mask = 0ull;
-    for (int j = 0; j < na; ++j) {
-        const float d = dist3_xyz(xi, yi, zi, lane_value(xi, j), lane_value(yi, j), lane_value(zi, j));
-        if (j != lane && lane < na && d <= in.cutoff_g) mask |= 1ull << j;
-    }
+    if constexpr (!FREE) radius_masks<false>(xi, yi, zi, lane, na, in.cutoff_g, 0.f, mask, lmask);
     const int deg = __popcll(mask);
     const int ginc = wave_incl(deg, lane);
     const int eg_m = __shfl(ginc, 63, 64);
@@ -218,7 +262,7 @@ __global__ __launch_bounds__(64) void mol_graph_kernel(MolIn in, int32_t* __rest
         if (lane == 0) {
             mol_tot[4 * g] = flags ? 0 : eg_m;
             mol_tot[4 * g + 1] = flags ? 0 : tp_m;
-            mol_tot[4 * g + 2] = b0;
+            mol_tot[4 * g + 2] = FREE ? nb : b0;
             mol_tot[4 * g + 3] = flags;
             if (flags) {
                 atomicOr(&totals[2], flags);
@@ -364,6 +408,15 @@ int check_in(const float* pos, const int32_t* gptr, int64_t n, int64_t n_graphs,
     return PAMNET_OK;
 }
 
+int check_free(const float* pos, const int32_t* gptr, int64_t n, int64_t n_graphs, int64_t n_local, float cutoff_l,
+               float cutoff_g) {
+    if (n < 0 || n_graphs < 1 || n_local < 0 || n >= ((int64_t)1 << 31) || n_local >= ((int64_t)1 << 30) || !(cutoff_l > 0.f) ||
+        !(cutoff_g > 0.f))
+        return PAMNET_EINVAL;
+    if (!pos || !gptr) return PAMNET_ENULL;
+    return PAMNET_OK;
+}
+
 }  // namespace
 
 extern "C" int pamnet_mol_graph_count_i32(const float* pos, const int32_t* gptr, int64_t n, int64_t n_graphs,
@@ -373,9 +426,9 @@ extern "C" int pamnet_mol_graph_count_i32(const float* pos, const int32_t* gptr,
     const int rc = check_in(pos, gptr, n, n_graphs, src, dst, n_bonds, cutoff_g);
     if (rc) return rc;
     if (!mol_tot || !totals) return PAMNET_ENULL;
-    const MolIn in{pos, gptr, src, dst, n, n_graphs, n_bonds, cutoff_g, with_triplets ? 1 : 0, 0};
+    const MolIn in{pos, gptr, src, dst, n, n_graphs, n_bonds, cutoff_g, with_triplets ? 1 : 0, 0, 0.f};
     const pamnet_mol_graph_out none{};
-    hipLaunchKernelGGL((mol_graph_kernel<false>), dim3((unsigned)n_graphs), dim3(64), 0, as_stream(stream), in, mol_tot, totals,
+    hipLaunchKernelGGL((mol_graph_kernel<false, false>), dim3((unsigned)n_graphs), dim3(64), 0, as_stream(stream), in, mol_tot, totals,
                        none, (int64_t)0, (int64_t)0);
     PAMNET_LAUNCH_CHECK();
     return PAMNET_OK;
@@ -395,8 +448,44 @@ extern "C" int pamnet_mol_graph_fill_i32(const float* pos, const int32_t* gptr, 
     if (n_bonds > 0 && (!o.l_row || !o.l_col || !o.l_dist || (need_grad && !o.lT_perm))) return PAMNET_ENULL;
     if (tp_cap > 0 && (!o.t_row || !o.t_col || !o.t_angle || !o.t_kind || (need_grad && !o.tT_perm))) return PAMNET_ENULL;
     if (need_grad && (!o.lT_ptr || !o.tT_ptr)) return PAMNET_ENULL;
-    const MolIn in{pos, gptr, src, dst, n, n_graphs, n_bonds, cutoff_g, with_triplets ? 1 : 0, need_grad ? 1 : 0};
-    hipLaunchKernelGGL((mol_graph_kernel<true>), dim3((unsigned)n_graphs), dim3(64), 0, as_stream(stream), in,
+    const MolIn in{pos, gptr, src, dst, n, n_graphs, n_bonds, cutoff_g, with_triplets ? 1 : 0, need_grad ? 1 : 0, 0.f};
+    hipLaunchKernelGGL((mol_graph_kernel<true, false>), dim3((unsigned)n_graphs), dim3(64), 0, as_stream(stream), in,
+                       const_cast<int32_t*>(mol_tot), (int32_t*)nullptr, o, eg_cap, tp_cap);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
+extern "C" int pamnet_mol_graph_free_count_i32(const float* pos, const int32_t* gptr, int64_t n, int64_t n_graphs,
+                                               float cutoff_l, float cutoff_g, int32_t with_triplets, int32_t* mol_tot,
+                                               int32_t* totals, pamnet_stream_t stream) {
+    const int rc = check_free(pos, gptr, n, n_graphs, 0, cutoff_l, cutoff_g);
+    if (rc) return rc;
+    if (!mol_tot || !totals) return PAMNET_ENULL;
+    const MolIn in{pos, gptr, nullptr, nullptr, n, n_graphs, 0, cutoff_g, with_triplets ? 1 : 0, 0, cutoff_l};
+    const pamnet_mol_graph_out none{};
+    hipLaunchKernelGGL((mol_graph_kernel<false, true>), dim3((unsigned)n_graphs), dim3(64), 0, as_stream(stream), in, mol_tot,
+                       totals, none, (int64_t)0, (int64_t)0);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
+extern "C" int pamnet_mol_graph_free_fill_i32(const float* pos, const int32_t* gptr, int64_t n, int64_t n_graphs,
+                                              int64_t n_local, float cutoff_l, float cutoff_g, int32_t with_triplets,
+                                              int32_t need_grad, const int32_t* mol_tot, int64_t eg_cap, int64_t tp_cap,
+                                              const pamnet_mol_graph_out* out, pamnet_stream_t stream) {
+    const int rc = check_free(pos, gptr, n, n_graphs, n_local, cutoff_l, cutoff_g);
+    if (rc) return rc;
+    if (!mol_tot || !out) return PAMNET_ENULL;
+    if (eg_cap < 0 || tp_cap < 0) return PAMNET_EINVAL;
+    const pamnet_mol_graph_out& o = *out;
+    if (!o.g_ptr || !o.l_ptr || !o.t_ptr) return PAMNET_ENULL;
+    if (eg_cap > 0 && (!o.g_row || !o.g_col || !o.g_dist || (need_grad && !o.gT_perm))) return PAMNET_ENULL;
+    if (n_local > 0 && (!o.l_row || !o.l_col || !o.l_dist || (need_grad && !o.lT_perm))) return PAMNET_ENULL;
+    if (tp_cap > 0 && (!o.t_row || !o.t_col || !o.t_angle || !o.t_kind || (need_grad && !o.tT_perm))) return PAMNET_ENULL;
+    if (need_grad && (!o.lT_ptr || !o.tT_ptr)) return PAMNET_ENULL;
+    const MolIn in{pos, gptr, nullptr, nullptr, n, n_graphs, n_local, cutoff_g, with_triplets ? 1 : 0, need_grad ? 1 : 0,
+                   cutoff_l};
+    hipLaunchKernelGGL((mol_graph_kernel<true, true>), dim3((unsigned)n_graphs), dim3(64), 0, as_stream(stream), in,
                        const_cast<int32_t*>(mol_tot), (int32_t*)nullptr, o, eg_cap, tp_cap);
     PAMNET_LAUNCH_CHECK();
     return PAMNET_OK;

@@ -6,7 +6,8 @@ Same constructor arguments, attribute names, `state_dict()` keys/shapes and `for
 (include/pamnet_hip.h).  Put this directory on sys.path in place of the reference checkout's root.
 
 forward(data): duck-typed `data` with `.x`, `.batch` (sorted) and, for QM9, `.pos` [N,3] and `.edge_index` [2,E]
-(optionally `.num_graphs`).  Returns fp32 [num_graphs], differentiable w.r.t. every parameter.  MI355X only: tensors must
+(optionally `.num_graphs`).  QM9 without `.edge_index` (absent or None): bond-free molecules, the local graph is the radius
+graph at cutoff_l.  Returns fp32 [num_graphs], differentiable w.r.t. every parameter.  MI355X only: tensors must
 live on a HIP device -- there is no CPU path (the CPU oracle in oracle/ is test infrastructure and is never imported
 from here).
 """
@@ -237,7 +238,7 @@ class _PAMNetBase(nn.Module):
     small = False
     max_num_neighbors = 1000            # radius(..., max_num_neighbors=1000), models.py:110,128
 
-    def __init__(self, config, num_spherical=7, num_radial=6, envelope_exponent=5, _pad=True):
+    def __init__(self, config, num_spherical=7, num_radial=6, envelope_exponent=5, _pad=True, num_atom_types=5):
         super().__init__()
         self.dataset = config.dataset
         self.config_dim = int(config.dim)
@@ -257,6 +258,13 @@ class _PAMNetBase(nn.Module):
         self._rna = self.dataset[:3].lower() == 'rna'
         self.__dict__['_pending_checks'] = []            # device flag words of forwards that ran without a host round trip
         self.__dict__['_ctor'] = (config, num_spherical, num_radial, envelope_exponent)
+        # rows of the QM9 type table (`embeddings`): 5 (H C N O F) in the reference; bond-free data brings other element sets
+        if isinstance(num_atom_types, bool) or not isinstance(num_atom_types, int) or not 1 <= num_atom_types <= ops.TYPE_MAX:
+            raise ValueError('num_atom_types must be an integer in 1..%d (got %r)' % (ops.TYPE_MAX, num_atom_types))
+        if num_atom_types != 5 and self.dataset != 'QM9':
+            raise ValueError('num_atom_types applies to the QM9 schema only (PDBbind rows carry features, the RNA table has '
+                             'its three types): dataset is %r' % (self.dataset,))
+        self.num_atom_types = num_atom_types
 
     # ---- parameter walks -------------------------------------------------------------------------------------------
     # `model.parameters()` / `named_parameters()` walk ~250 sub-modules for ~390 tensors: 1.4 ms of host time per walk, and
@@ -384,7 +392,7 @@ class _PAMNetBase(nn.Module):
         if self.__dict__.get('_rng_at_ctor') is not None:
             _rng_restore(self.__dict__.pop('_rng_at_ctor'))
         base = PAMNet_s if self.small else PAMNet         # (explicit class: a subclass may have another constructor)
-        twin = base(*self._ctor, _pad=False)
+        twin = base(*self._ctor, _pad=False, num_atom_types=self.num_atom_types)
         tsd = twin.state_dict()
         self.__dict__['_logical_shapes'] = {k: tuple(v.shape) for k, v in tsd.items()}
         self._register_load_state_dict_pre_hook(self._pad_incoming)
@@ -478,8 +486,12 @@ class _PAMNetBase(nn.Module):
             return None
         if isinstance(sz, dict):
             from pamnet_amd.store import size_key
-            return sz.get(size_key(self))
+            return sz.get(size_key(self, self._bonded(data)))
         return sz
+
+    def _bonded(self, data):
+        """False for a QM9-schema batch without a bond list (its local graph is the radius graph at cutoff_l)."""
+        return self.dataset != 'QM9' or getattr(data, 'edge_index', None) is not None
 
     def _mol_local_of(self, data):
         """True: a store vouches that this batch is inside the molecule-local graph builder's contract (graph.build_graph);
@@ -487,7 +499,7 @@ class _PAMNetBase(nn.Module):
         ml = getattr(data, 'mol_local', None)
         if isinstance(ml, dict):
             from pamnet_amd.store import size_key
-            return ml.get(size_key(self))
+            return ml.get(size_key(self, self._bonded(data)))
         return ml
 
     def verify(self):
@@ -748,13 +760,13 @@ def _slice_outgoing(module, state_dict, prefix, local_metadata):
 class PAMNet(_PAMNetBase):
     """models.py:21-224."""
 
-    def __init__(self, config, num_spherical=7, num_radial=6, envelope_exponent=5, _pad=True):
-        super().__init__(config, num_spherical, num_radial, envelope_exponent, _pad)
+    def __init__(self, config, num_spherical=7, num_radial=6, envelope_exponent=5, _pad=True, *, num_atom_types=5):
+        super().__init__(config, num_spherical, num_radial, envelope_exponent, _pad, num_atom_types)
         d = self.dim
         if self._rna:
             self.embeddings = nn.Parameter(torch.ones((3, d)))       # C, N, O
         else:
-            self.embeddings = nn.Parameter(torch.ones((5, d)))
+            self.embeddings = nn.Parameter(torch.ones((self.num_atom_types, d)))
             self.init_linear = nn.Linear(18, d, bias=False)
         self._build_common(num_spherical, num_radial, envelope_exponent)
         self.mlp_sbf1 = MLP([num_spherical * num_radial, d])
@@ -801,10 +813,10 @@ class PAMNet_s(_PAMNetBase):
     small = True
     max_num_neighbors = 500             # radius(..., max_num_neighbors=500), models.py:301
 
-    def __init__(self, config, num_spherical=7, num_radial=6, envelope_exponent=5, _pad=True):
-        super().__init__(config, num_spherical, num_radial, envelope_exponent, _pad)
+    def __init__(self, config, num_spherical=7, num_radial=6, envelope_exponent=5, _pad=True, *, num_atom_types=5):
+        super().__init__(config, num_spherical, num_radial, envelope_exponent, _pad, num_atom_types)
         d = self.dim
-        self.embeddings = nn.Parameter(torch.ones((5, d)))
+        self.embeddings = nn.Parameter(torch.ones((self.num_atom_types, d)))
         self._build_common(num_spherical, num_radial, envelope_exponent)
         self.mlp_sbf = MLP([num_spherical * num_radial, d])
         self.global_layer = nn.ModuleList([GlobalMP(d) for _ in range(self.n_layer)])

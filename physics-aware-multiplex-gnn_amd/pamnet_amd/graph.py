@@ -631,22 +631,31 @@ def _engine_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos, edge_ind
     return g
 
 
-def _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad):
+def _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=None):
     """QM9 schema, plain tensors: the molecule-local builder (csrc/graph_mol.hip) -- count launch, ONE host round trip for
     the sizes / validity / qualification, fill launch.  Fills `g` and returns True; False when the batch does not qualify
-    (a molecule over the builder's limits, bonds not grouped by molecule, self loops): nothing of `g` was touched."""
+    (a molecule over the builder's limits, bonds not grouped by molecule, self loops): nothing of `g` was touched.
+    `cutoff_l`: the bond-free form -- `ing` carries no bonds, the local graph is the radius graph at cutoff_l and its size
+    comes back with the other totals."""
     import ctypes
     node_graph, gptr, _, src0, dst0, flag, loops, totals = ing       # totals: four zeroed words behind the flags
     dev = pos.device
+    free = cutoff_l is not None
     n, ng, m = g.n, g.n_graphs, int(src0.numel())
     st = lib.stream_of(pos)
     mol_tot = _i32(4 * ng, dev)
     wt = 1 if with_triplets else 0
-    lib.call('pamnet_mol_graph_count_i32', lib.ptr(pos), lib.ptr(gptr), n, ng, lib.ptr(src0), lib.ptr(dst0), m, float(cutoff_g),
-             wt, lib.ptr(mol_tot), lib.ptr(totals), st)
+    if free:
+        lib.call('pamnet_mol_graph_free_count_i32', lib.ptr(pos), lib.ptr(gptr), n, ng, float(cutoff_l), float(cutoff_g), wt,
+                 lib.ptr(mol_tot), lib.ptr(totals), st)
+    else:
+        lib.call('pamnet_mol_graph_count_i32', lib.ptr(pos), lib.ptr(gptr), n, ng, lib.ptr(src0), lib.ptr(dst0), m,
+                 float(cutoff_g), wt, lib.ptr(mol_tot), lib.ptr(totals), st)
     eg, tp, viol, counted, bad, lp_ = host_ints(totals[0], totals[1], totals[2], totals[3], flag, loops)
     if bad:
         _raise_bad_inputs()
+    if free:
+        m = counted
     if viol or lp_ or counted != m or eg <= 0 or tp <= 0:
         return False
     def carve(sizes):                                 # one int32 allocation, 16-byte aligned slices
@@ -668,8 +677,12 @@ def _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad):
     if need_grad:
         o.gT_perm, o.lT_ptr, o.lT_perm = gT_perm.data_ptr(), lT_ptr.data_ptr(), lT_perm.data_ptr()
         o.tT_ptr, o.tT_perm = tT_ptr.data_ptr(), tT_perm.data_ptr()
-    lib.call('pamnet_mol_graph_fill_i32', lib.ptr(pos), lib.ptr(gptr), n, ng, lib.ptr(src0), lib.ptr(dst0), m, float(cutoff_g),
-             wt, 1 if need_grad else 0, lib.ptr(mol_tot), eg, tp, ctypes.addressof(o), st)
+    if free:
+        lib.call('pamnet_mol_graph_free_fill_i32', lib.ptr(pos), lib.ptr(gptr), n, ng, m, float(cutoff_l), float(cutoff_g), wt,
+                 1 if need_grad else 0, lib.ptr(mol_tot), eg, tp, ctypes.addressof(o), st)
+    else:
+        lib.call('pamnet_mol_graph_fill_i32', lib.ptr(pos), lib.ptr(gptr), n, ng, lib.ptr(src0), lib.ptr(dst0), m,
+                 float(cutoff_g), wt, 1 if need_grad else 0, lib.ptr(mol_tot), eg, tp, ctypes.addressof(o), st)
     g.loops = loops
     g.pos = pos
     g.glob, g.dist_g = CSR(g_ptr, g_row, g_col), g_dist
@@ -694,6 +707,9 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
     the host numbers, the fills are capped by them, and one launch compares them with the device-side counts (and
     folds in the input-validity flag); the result waits in `g.check` (an int32 device scalar) for the caller's next
     synchronisation (PAMNet.verify).  Without them: one host round trip for the sizes and the flag.
+
+    `edge_index` None (QM9 schema): bond-free molecules -- the local graph is the radius graph at cutoff_l inside every molecule
+    (self excluded, no neighbour cap), stored by target, then source.
 
     `mol_local` (QM9 schema): True = the caller vouches that every molecule is within the molecule-local builder's limits
     (MOL_ATOMS / MOL_BONDS) with its bonds grouped by molecule (a resident store knows); None = try it when the
@@ -728,7 +744,7 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
     ing = None
     if batch.is_cuda and n > 0:
         if dataset == 'QM9':
-            if edge_index is not None and n_types is not None:
+            if n_types is not None:                   # (edge_index None: the bond-free batch, validated without edges)
                 ing = ingest(batch, g.n_graphs, x_raw, n_types, edge_index)
         elif rna and n_types is not None and x_raw.dim() == 2:                      # the type id is x's last column
             ing = ingest(batch, g.n_graphs, x_raw[:, -1], n_types)
@@ -748,8 +764,48 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
     checks = []                                   # (device total, value the host assumed), verified by one launch at the end
     glob_rows = []                                # row ids of the global edges when the launch that fills them writes them
     glob_inv = loc_inv = None                     # InverseTranspose of a list that was stored by query and then transposed
+    loc_radius = False                            # the local graph is an uncapped radius graph of its own (symmetric)
 
-    if dataset == 'QM9':
+    if dataset == 'QM9' and edge_index is None:
+        # Bond-free molecules: the local graph is the radius graph at cutoff_l inside every molecule (what the reference's
+        # forward, models.py:104-115, computes when handed edge_index = radius(pos, pos, cutoff_l, batch, batch): get_edge_info
+        # strips the self loops) -- a search of its own, without a neighbour cap, so cutoff_l may lie on either side of cutoff_g
+        # and a cap that binds in the global search leaves it alone.
+        pos = pos.to(torch.float32).contiguous()
+        if ing is not None:
+            flag = ing[5]
+        else:
+            flag = _input_flag(node_graph, g.n_graphs, x_raw.to(torch.float32).reshape(-1), n_types)
+        if (sizes is None and ing is not None and MOL_LOCAL and mol_local is not False
+                and not 0 < max_nb <= MOL_ATOMS
+                and (mol_local is True or n <= MOL_ATOMS * g.n_graphs // 2)):
+            if _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=cutoff_l):
+                return _with_seg_cuts(g, dataset) if aux_tables else g
+        gptr_g = radius_count(pos, node_graph, g.gptr, cutoff_g, max_nb, flag)
+        lp = radius_count(pos, node_graph, g.gptr, cutoff_l)
+        if sizes is not None:                     # zero host round trips (see `sizes`)
+            total_g, total_l, tp_hint = (int(v) for v in sizes)
+            g.check = flag
+            checks += [(gptr_g[-1:], total_g), (lp[-1:], total_l)]
+            hinted = _ZeroArena(3 * total_g + 3 * total_l + 5 * tp_hint + 64, dev)
+            gptr_g, lp = torch.clamp(gptr_g, max=total_g), torch.clamp(lp, max=total_l)
+        else:
+            # ONE host round trip: the triplet / pair total of a symmetric graph follows from its degrees (see PDBbind below)
+            deg = (lp[1:] - lp[:-1]).long()
+            tp_dev = (deg * deg + (deg * (deg - 1) if with_triplets else 0)).sum()
+            total_g, total_l, tp_hint, bad = host_ints(gptr_g[-1], lp[-1], tp_dev, flag)
+            if bad & ~CAP_BIT:
+                _raise_bad_inputs()
+            capped = bool(bad & CAP_BIT)
+        gp, gn, gd = radius_fill(pos, node_graph, g.gptr, cutoff_g, gptr_g, total_g, zeroed=hinted, rows_out=glob_rows,
+                                 max_neighbors=max_nb)
+        if capped and flow != 'target_to_source':     # (stored by neighbour: see the bonded branch below)
+            gp, gn, gd, glob_inv = _transpose_edges(gp, gn, gd, n, want_inverse=need_grad, q=glob_rows.pop())
+        loc_rows = []
+        lp, l_src, l_dist = radius_fill(pos, node_graph, g.gptr, cutoff_l, lp, total_l, zeroed=hinted, rows_out=loc_rows)
+        l_dst = loc_rows[0]
+        loc_radius = True
+    elif dataset == 'QM9':
         pos = pos.to(torch.float32).contiguous()
         # One host round trip for all three data-dependent sizes: the bond graph's CSR and its triplet / pair counts do
         # not depend on the radius graph, so they are computed first, on the assumption that the bond list has no self
@@ -940,9 +996,9 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
         # transposition that stored it by neighbour; a counting sort otherwise
         g.glob_T = SymmetricTranspose(g.glob) if radius_g else (glob_inv if glob_inv is not None
                                                                else Transpose(g.glob.col, n))
-        # d x[j] of the local gather: a radius graph for PDBbind, the inverse transposition for RNA; user-supplied bonds
-        # (QM9) take the counting sort
-        g.loc_T = SymmetricTranspose(g.loc) if (dataset == 'PDBbind' and not capped) else (
+        # d x[j] of the local gather: a radius graph for PDBbind and bond-free QM9, the inverse transposition for RNA;
+        # user-supplied bonds (QM9) take the counting sort
+        g.loc_T = SymmetricTranspose(g.loc) if ((dataset == 'PDBbind' and not capped) or loc_radius) else (
             loc_inv if loc_inv is not None else Transpose(g.loc.col, n))
         # d m_neighbor[e'] of the triplet/pair gather
         g.tp_T = (TripletTranspose(g.loc, g.loc_T, tp_ptr, tcount, tot, with_triplets, zeroed=hinted) if (e_l > 0 and tot > 0)

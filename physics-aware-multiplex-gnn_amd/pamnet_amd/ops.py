@@ -318,9 +318,12 @@ class _TypeRows(torch.autograd.Function):
         return (None if ctx.direct is not None else gt), None, None
 
 
+TYPE_MAX = 8          # rows of a type table the kernels take (type_rows::TYPE_MAX, csrc/type_rows_core.h)
+
+
 def type_rows_supported(table):
     d4 = table.size(1) // 4
-    return table.is_cuda and table.size(0) <= 8 and table.size(1) % 4 == 0 and 1 <= d4 <= 64 and (d4 & (d4 - 1)) == 0
+    return table.is_cuda and table.size(0) <= TYPE_MAX and table.size(1) % 4 == 0 and 1 <= d4 <= 64 and (d4 & (d4 - 1)) == 0
 
 
 def type_rows(table, idx, direct_grad=None, tape=None):

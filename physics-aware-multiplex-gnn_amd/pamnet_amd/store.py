@@ -24,14 +24,16 @@ I32 = torch.int32
 KNN_K = G.KNN_K       # neighbours of the RNA kNN graph (models.py:143): build_graph's default, the only k the sizes are counted for
 
 
-def size_key(model):
+def size_key(model, bonded=True):
     """Everything the per-graph sizes of a forward depend on: the schema (which graph construction runs), both cutoffs,
     the layer kind (triplets or pairs only), the flow and the kNN neighbour count.  Two models that share a store but
-    differ in any of these get their own count tables."""
+    differ in any of these get their own count tables.  bonded=False: a QM9-schema batch without a bond list, whose local
+    graph is the radius graph at cutoff_l -- other sizes than those of the same molecules with bonds, so another key."""
     ds = model.dataset
     schema = 'rna' if ds[:3].lower() == 'rna' else ds
-    return (schema, float(model.cutoff_g), float(model.cutoff_l), not model.small, str(model.flow), KNN_K,
-            int(getattr(model, 'max_num_neighbors', 0) or 0))
+    key = (schema, float(model.cutoff_g), float(model.cutoff_l), not model.small, str(model.flow), KNN_K,
+           int(getattr(model, 'max_num_neighbors', 0) or 0))
+    return key if (bonded or schema != 'QM9') else key + ('bond-free',)
 
 
 class Batch(object):
@@ -50,7 +52,8 @@ class MoleculeStore(object):
 
     data_list: objects / dicts with x ([n] atom types for QM9; [n, w] rows of coordinates + features for PDBbind / RNA),
     optionally pos [n, 3] and edge_index [2, e] (QM9: node ids local to the molecule, both directions present as in
-    qm9_dataset.py:243) and y (scalar target)."""
+    qm9_dataset.py:243) and y (scalar target).  QM9 schema without edge_index: bond-free molecules -- the local graph is
+    the radius graph at the model's cutoff_l (graph.build_graph), its sizes are counted like every other."""
 
     def __init__(self, data_list, device):
         self.device = torch.device(device)
@@ -127,7 +130,7 @@ class MoleculeStore(object):
         layer kind): counted on the device by the forward's own graph construction, `chunk` graphs per pass, read back
         ONCE per dataset.  The local edges of a graph are contiguous in the batch's CSR (sorted by target node), so every
         count is a difference of CSR pointers at the graph's node range."""
-        key = size_key(model)
+        key = size_key(model, self.has_edges)
         if key in self._counts:
             return self._counts[key]
         m = len(self)
