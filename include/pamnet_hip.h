@@ -133,6 +133,32 @@ int pamnet_radius_fill_i32(const float* pos, const int32_t* node_graph, const in
                            int32_t* row_of /* nullable: the query node of every entry */, int64_t cap,
                            pamnet_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Periodic cells (QM9-schema batches that carry `cell`): every displacement between two atoms of one graph is the
+ * minimum-image one.  ONE image rule (csrc/geom_core.h min_image), used by every *_pbc_* entry point: the fp64 difference of
+ * the two fp32 positions times the graph's inverse cell, the three fractional components rounded to the nearest integer
+ * (the image n), n @ cell subtracted in fp64; the fp32 kernels round the three components once to fp32 and go on with the
+ * arithmetic of their open-space twins.  n(i, j) == -n(j, i) exactly, so both directions of an edge carry bitwise equal
+ * lengths, and with n = 0 the values are bitwise the open-space kernels'.
+ *   pamnet_cell_prepare_f64: cell fp32 [n_graphs, 9] (row k of a graph's 3 x 3 = lattice vector a_k; an image of an atom is
+ *     pos + n @ cell) -> cell_table [n_graphs, 18] doubles: the cell and its inverse (adjugate / determinant, fp64).  ORs 128
+ *     into *flag (not zeroed here: the batch's validity word) when a cell is singular, not finite, or one of its three
+ *     perpendicular heights |det| / |a_i x a_j| does not exceed 2 * cutoff -- the condition under which every ordered pair has
+ *     at most one image within the cutoff and nearest-integer rounding finds it for any triclinic cell.  cutoff: the larger
+ *     of the model's two.
+ *   pamnet_radius_pbc_count/fill_i32: pamnet_radius_count/fill_i32 with the distance taken by the image rule: the same row
+ *     order (ascending j), max_neighbors / cap_flag semantics, cap guard and launch-shape selection.  An atom never sees itself.
+ * Argument order: the twin's, with cell_table (and node_graph where the twin has none) behind pos.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int pamnet_cell_prepare_f64(const float* cell, int64_t n_graphs, float cutoff, double* cell_table, int32_t* flag,
+                            pamnet_stream_t stream);
+int pamnet_radius_pbc_count_i32(const float* pos, const double* cell_table, const int32_t* node_graph, const int32_t* gptr,
+                                int64_t n, int64_t n_graphs, float r, int64_t max_neighbors, int32_t* count,
+                                int32_t* cap_flag, pamnet_stream_t stream);
+int pamnet_radius_pbc_fill_i32(const float* pos, const double* cell_table, const int32_t* node_graph, const int32_t* gptr,
+                               int64_t n, int64_t n_graphs, float r, int64_t max_neighbors, const int32_t* ptr, int32_t* nbr,
+                               float* dist, int32_t* row_of /* nullable */, int64_t cap, pamnet_stream_t stream);
+
 /* knn: for every query node its k nearest nodes of the same graph (itself included, as torch_cluster.knn does),
  * ordered by (distance, index); then the self entry is dropped and entries with dist > cutoff are masked out:
  * nbr[i*k + s] = neighbour index or -1, dist[i*k + s] = distance.  (models.py:143-150) */
@@ -173,6 +199,12 @@ int pamnet_triplet_count_i32(const int32_t* lptr, const int32_t* src, const int3
 int pamnet_triplet_fill_f32(const float* pos, const int32_t* lptr, const int32_t* src, const int32_t* dst,
                             int64_t n_edges, int32_t with_triplets, const int32_t* tp_ptr, int32_t* tp_idx,
                             int32_t* tp_edge, float* tp_angle, int32_t* tp_kind, int64_t cap, pamnet_stream_t stream);
+/* The same with both bond vectors of every row by the image rule of the periodic cells (see pamnet_cell_prepare_f64);
+ * node_graph [n]: the graph of every atom. */
+int pamnet_triplet_fill_pbc_f32(const float* pos, const double* cell_table, const int32_t* node_graph, const int32_t* lptr,
+                                const int32_t* src, const int32_t* dst, int64_t n_edges, int32_t with_triplets,
+                                const int32_t* tp_ptr, int32_t* tp_idx, int32_t* tp_edge, float* tp_angle, int32_t* tp_kind,
+                                int64_t cap, pamnet_stream_t stream);
 /* Transposed triplet / pair row list (for every source bond the rows that gather it, ascending: the (ptr, perm) that
  * pamnet_csr_from_keys_i32 returns for keys = tp_idx over n_edges rows) from the graph's structure instead of a counting sort
  * over the rows: count -> caller scans -> fill.  lt_ptr [n + 1] / lt_perm [n_edges]: the transposed bond list (bonds by source
@@ -413,6 +445,17 @@ int pamnet_pos_bwd_f32(const float* pos, int64_t n, const int32_t* g_ptr, const 
                        const float* ddist_l, int64_t el, const int32_t* t_ptr, const int32_t* t_row, const int32_t* t_col,
                        const int32_t* t_kind, const int32_t* tt_ptr, const int32_t* tt_perm, const float* dangle, int64_t tp,
                        double* bond_work, float* dpos, pamnet_stream_t stream);
+
+/* pamnet_pos_bwd_f32 for a graph built under periodic cells: every bond and global-edge vector is the minimum-image
+ * displacement (the image integer from the function the forward's kernels used, the vector kept in fp64; the image does not
+ * depend on the positions differentiably).  Same sums in the same fixed order, no atomics, same return codes. */
+int pamnet_pos_bwd_pbc_f32(const float* pos, const double* cell_table, const int32_t* node_graph, int64_t n,
+                           const int32_t* g_ptr, const int32_t* g_row, const int32_t* g_col, const int32_t* gt_ptr,
+                           const int32_t* gt_perm, const float* ddist_g, int64_t eg, const int32_t* l_ptr, const int32_t* l_row,
+                           const int32_t* l_col, const int32_t* lt_ptr, const int32_t* lt_perm, const float* ddist_l, int64_t el,
+                           const int32_t* t_ptr, const int32_t* t_row, const int32_t* t_col, const int32_t* t_kind,
+                           const int32_t* tt_ptr, const int32_t* tt_perm, const float* dangle, int64_t tp, double* bond_work,
+                           float* dpos, pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Attention fusion + per-graph pooling  (models.py:206-224)

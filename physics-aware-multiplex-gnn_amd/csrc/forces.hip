@@ -8,6 +8,7 @@
 // 3-vector per local edge, and the positions gather those per atom.  No atomics: every sum runs over a CSR row or a
 // transposed row list in a fixed order, so the result is bitwise the same from run to run.  Arithmetic in fp64.
 #include "common.h"
+#include "geom_core.h"
 
 namespace {
 
@@ -28,10 +29,38 @@ __device__ __forceinline__ V3 cross(V3 a, V3 b) {
 __device__ __forceinline__ V3 load_pos(const float* __restrict__ pos, int64_t i) {
     return v3((double)pos[3 * i], (double)pos[3 * i + 1], (double)pos[3 * i + 2]);
 }
+// How the backward turns two atoms into p_a - p_b: the fp64 difference in open space, or the minimum-image displacement of
+// a periodic cell -- geom_core.h min_image, the function the forward's kernels chose the image with, kept in fp64 here.  The
+// image integers do not depend on the positions differentiably, so every derivative below is the open-space one.
+struct OpenDiff {
+    __device__ __forceinline__ void bind(const int32_t* __restrict__, int64_t) {}
+    __device__ __forceinline__ V3 diff(const float* __restrict__ pos, int64_t a, int64_t b) const {
+        return load_pos(pos, a) - load_pos(pos, b);
+    }
+    __device__ __forceinline__ V3 from(V3 pa, const float* __restrict__ pos, int64_t b) const { return pa - load_pos(pos, b); }
+};
+struct PeriodicDiff {
+    const double* __restrict__ table;
+    PbcCell t;
+    __device__ __forceinline__ void bind(const int32_t* __restrict__ node_graph, int64_t atom) {
+        t = load_cell(table, node_graph[atom]);
+    }
+    __device__ __forceinline__ V3 diff(const float* __restrict__ pos, int64_t a, int64_t b) const {
+        const Disp d = min_image(t, pos, a, b);
+        return v3(d.x, d.y, d.z);
+    }
+    // pa: an fp32 position held as doubles (load_pos)
+    __device__ __forceinline__ V3 from(V3 pa, const float* __restrict__ pos, int64_t b) const {
+        const Disp d = min_image(t, (float)pa.x, (float)pa.y, (float)pa.z, pos[3 * b], pos[3 * b + 1], pos[3 * b + 2]);
+        return v3(d.x, d.y, d.z);
+    }
+};
+
 // u_e = p[src] - p[dst] of local edge e (loc: rows = dst, col = src)
-__device__ __forceinline__ V3 bond(const float* __restrict__ pos, const int32_t* __restrict__ l_row,
+template <class GEOM>
+__device__ __forceinline__ V3 bond(const GEOM& geom, const float* __restrict__ pos, const int32_t* __restrict__ l_row,
                                    const int32_t* __restrict__ l_col, int64_t e) {
-    return load_pos(pos, l_col[e]) - load_pos(pos, l_row[e]);
+    return geom.diff(pos, l_col[e], l_row[e]);
 }
 
 // theta = atan2(|a x b|, a.b):  d theta / d a = (a.b (b x c) / |c| - |c| b) / s,  d theta / d b = (a.b (c x a) / |c| - |c| a) / s,
@@ -65,17 +94,19 @@ __device__ __forceinline__ V3 wave_sum(V3 v) {
 
 // One wavefront per local edge e: G_e = d/d u_e of everything that depends on u_e -- its length, the rows of e (operand a)
 // and the rows that gather e (operand b, transposed row list); the lanes stride over the rows.
-__global__ __launch_bounds__(256) void bond_grad_kernel(const float* __restrict__ pos, const int32_t* __restrict__ l_row,
-                                                        const int32_t* __restrict__ l_col, const float* __restrict__ ddist,
-                                                        int64_t el, const int32_t* __restrict__ t_ptr,
-                                                        const int32_t* __restrict__ t_row, const int32_t* __restrict__ t_col,
-                                                        const int32_t* __restrict__ t_kind, const int32_t* __restrict__ tt_ptr,
-                                                        const int32_t* __restrict__ tt_perm, const float* __restrict__ dangle,
-                                                        double* __restrict__ G) {
+template <class GEOM>
+__device__ __forceinline__ void bond_grad(GEOM geom, const int32_t* __restrict__ node_graph, const float* __restrict__ pos,
+                                          const int32_t* __restrict__ l_row, const int32_t* __restrict__ l_col,
+                                          const float* __restrict__ ddist, int64_t el, const int32_t* __restrict__ t_ptr,
+                                          const int32_t* __restrict__ t_row, const int32_t* __restrict__ t_col,
+                                          const int32_t* __restrict__ t_kind, const int32_t* __restrict__ tt_ptr,
+                                          const int32_t* __restrict__ tt_perm, const float* __restrict__ dangle,
+                                          double* __restrict__ G) {
     const int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (e >= el) return;                                          // (uniform over the wavefront)
-    const V3 u = bond(pos, l_row, l_col, e);
+    geom.bind(node_graph, l_row[e]);                              // (every bond of e's rows lies in e's graph)
+    const V3 u = bond(geom, pos, l_row, l_col, e);
     V3 acc = v3(0.0, 0.0, 0.0);
     if (lane == 0) {
         const double r = sqrt(dot(u, u));
@@ -84,14 +115,14 @@ __global__ __launch_bounds__(256) void bond_grad_kernel(const float* __restrict_
     for (int t = t_ptr[e] + lane; t < t_ptr[e + 1]; t += 64) {   // rows of e: a = +-u_e
         const double sg = t_kind[t] == 0 ? 1.0 : -1.0;
         V3 ga, gb;
-        angle_grads(sg * u, bond(pos, l_row, l_col, t_col[t]), (double)dangle[t], &ga, &gb);
+        angle_grads(sg * u, bond(geom, pos, l_row, l_col, t_col[t]), (double)dangle[t], &ga, &gb);
         acc = acc + sg * ga;
     }
     for (int k = tt_ptr[e] + lane; k < tt_ptr[e + 1]; k += 64) { // rows gathering e: b = u_e
         const int64_t t = tt_perm[k];
         const double sg = t_kind[t] == 0 ? 1.0 : -1.0;
         V3 ga, gb;
-        angle_grads(sg * bond(pos, l_row, l_col, t_row[t]), u, (double)dangle[t], &ga, &gb);
+        angle_grads(sg * bond(geom, pos, l_row, l_col, t_row[t]), u, (double)dangle[t], &ga, &gb);
         acc = acc + gb;
     }
     acc = wave_sum(acc);
@@ -102,28 +133,54 @@ __global__ __launch_bounds__(256) void bond_grad_kernel(const float* __restrict_
     }
 }
 
+__global__ __launch_bounds__(256) void bond_grad_kernel(const float* __restrict__ pos, const int32_t* __restrict__ l_row,
+                                                        const int32_t* __restrict__ l_col, const float* __restrict__ ddist,
+                                                        int64_t el, const int32_t* __restrict__ t_ptr,
+                                                        const int32_t* __restrict__ t_row, const int32_t* __restrict__ t_col,
+                                                        const int32_t* __restrict__ t_kind, const int32_t* __restrict__ tt_ptr,
+                                                        const int32_t* __restrict__ tt_perm, const float* __restrict__ dangle,
+                                                        double* __restrict__ G) {
+    bond_grad(OpenDiff{}, nullptr, pos, l_row, l_col, ddist, el, t_ptr, t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, G);
+}
+
+__global__ __launch_bounds__(256) void bond_grad_pbc_kernel(const float* __restrict__ pos, const double* __restrict__ cells,
+                                                            const int32_t* __restrict__ node_graph,
+                                                            const int32_t* __restrict__ l_row, const int32_t* __restrict__ l_col,
+                                                            const float* __restrict__ ddist, int64_t el,
+                                                            const int32_t* __restrict__ t_ptr, const int32_t* __restrict__ t_row,
+                                                            const int32_t* __restrict__ t_col, const int32_t* __restrict__ t_kind,
+                                                            const int32_t* __restrict__ tt_ptr,
+                                                            const int32_t* __restrict__ tt_perm,
+                                                            const float* __restrict__ dangle, double* __restrict__ G) {
+    PeriodicDiff geom;
+    geom.table = cells;
+    bond_grad(geom, node_graph, pos, l_row, l_col, ddist, el, t_ptr, t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, G);
+}
+
 // One wavefront per atom a, the lanes striding over: the global edges of row a and of column a (transposed list), then the
 // bond gradients of the local edges leaving a (+G) and arriving at a (-G).
-__global__ __launch_bounds__(256) void pos_grad_kernel(const float* __restrict__ pos, int64_t n,
-                                                       const int32_t* __restrict__ g_ptr, const int32_t* __restrict__ g_row,
-                                                       const int32_t* __restrict__ g_col, const int32_t* __restrict__ gt_ptr,
-                                                       const int32_t* __restrict__ gt_perm, const float* __restrict__ ddist_g,
-                                                       const int32_t* __restrict__ l_ptr, const int32_t* __restrict__ lt_ptr,
-                                                       const int32_t* __restrict__ lt_perm, const double* __restrict__ G,
-                                                       float* __restrict__ dpos) {
+template <class GEOM>
+__device__ __forceinline__ void pos_grad(GEOM geom, const int32_t* __restrict__ node_graph, const float* __restrict__ pos,
+                                         int64_t n, const int32_t* __restrict__ g_ptr, const int32_t* __restrict__ g_row,
+                                         const int32_t* __restrict__ g_col, const int32_t* __restrict__ gt_ptr,
+                                         const int32_t* __restrict__ gt_perm, const float* __restrict__ ddist_g,
+                                         const int32_t* __restrict__ l_ptr, const int32_t* __restrict__ lt_ptr,
+                                         const int32_t* __restrict__ lt_perm, const double* __restrict__ G,
+                                         float* __restrict__ dpos) {
     const int64_t a = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (a >= n) return;                                           // (uniform over the wavefront)
+    geom.bind(node_graph, a);
     const V3 pa = load_pos(pos, a);
     V3 acc = v3(0.0, 0.0, 0.0);
     for (int q = g_ptr[a] + lane; q < g_ptr[a + 1]; q += 64) {
-        const V3 w = pa - load_pos(pos, g_col[q]);
+        const V3 w = geom.from(pa, pos, g_col[q]);
         const double r = sqrt(dot(w, w));
         if (r > 0.0) acc = acc + ((double)ddist_g[q] / r) * w;
     }
     for (int k = gt_ptr[a] + lane; k < gt_ptr[a + 1]; k += 64) {
         const int64_t q = gt_perm[k];
-        const V3 w = pa - load_pos(pos, g_row[q]);
+        const V3 w = geom.from(pa, pos, g_row[q]);
         const double r = sqrt(dot(w, w));
         if (r > 0.0) acc = acc + ((double)ddist_g[q] / r) * w;
     }
@@ -138,6 +195,30 @@ __global__ __launch_bounds__(256) void pos_grad_kernel(const float* __restrict__
         dpos[3 * a + 1] = (float)acc.y;
         dpos[3 * a + 2] = (float)acc.z;
     }
+}
+
+__global__ __launch_bounds__(256) void pos_grad_kernel(const float* __restrict__ pos, int64_t n,
+                                                       const int32_t* __restrict__ g_ptr, const int32_t* __restrict__ g_row,
+                                                       const int32_t* __restrict__ g_col, const int32_t* __restrict__ gt_ptr,
+                                                       const int32_t* __restrict__ gt_perm, const float* __restrict__ ddist_g,
+                                                       const int32_t* __restrict__ l_ptr, const int32_t* __restrict__ lt_ptr,
+                                                       const int32_t* __restrict__ lt_perm, const double* __restrict__ G,
+                                                       float* __restrict__ dpos) {
+    pos_grad(OpenDiff{}, nullptr, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm, G, dpos);
+}
+
+__global__ __launch_bounds__(256) void pos_grad_pbc_kernel(const float* __restrict__ pos, const double* __restrict__ cells,
+                                                           const int32_t* __restrict__ node_graph, int64_t n,
+                                                           const int32_t* __restrict__ g_ptr, const int32_t* __restrict__ g_row,
+                                                           const int32_t* __restrict__ g_col, const int32_t* __restrict__ gt_ptr,
+                                                           const int32_t* __restrict__ gt_perm,
+                                                           const float* __restrict__ ddist_g, const int32_t* __restrict__ l_ptr,
+                                                           const int32_t* __restrict__ lt_ptr,
+                                                           const int32_t* __restrict__ lt_perm, const double* __restrict__ G,
+                                                           float* __restrict__ dpos) {
+    PeriodicDiff geom;
+    geom.table = cells;
+    pos_grad(geom, node_graph, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm, G, dpos);
 }
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)(n > 0 ? ceil_div(n, 256) : 1); }
@@ -164,6 +245,31 @@ extern "C" int pamnet_pos_bwd_f32(const float* pos, int64_t n, const int32_t* g_
     }
     hipLaunchKernelGGL(pos_grad_kernel, dim3(blocks_for(n * 64)), dim3(256), 0, st, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm,
                        ddist_g, l_ptr, lt_ptr, lt_perm, bond_work, dpos);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
+extern "C" int pamnet_pos_bwd_pbc_f32(const float* pos, const double* cell_table, const int32_t* node_graph, int64_t n,
+                                      const int32_t* g_ptr, const int32_t* g_row, const int32_t* g_col, const int32_t* gt_ptr,
+                                      const int32_t* gt_perm, const float* ddist_g, int64_t eg, const int32_t* l_ptr,
+                                      const int32_t* l_row, const int32_t* l_col, const int32_t* lt_ptr, const int32_t* lt_perm,
+                                      const float* ddist_l, int64_t el, const int32_t* t_ptr, const int32_t* t_row,
+                                      const int32_t* t_col, const int32_t* t_kind, const int32_t* tt_ptr, const int32_t* tt_perm,
+                                      const float* dangle, int64_t tp, double* bond_work, float* dpos, pamnet_stream_t stream) {
+    if (n < 0 || eg < 0 || el < 0 || tp < 0) return PAMNET_EINVAL;
+    if (!pos || !cell_table || !node_graph || !g_ptr || !g_row || !g_col || !gt_ptr || !gt_perm || !ddist_g || !l_ptr ||
+        !l_row || !l_col || !lt_ptr || !lt_perm || !ddist_l || !t_ptr || !t_row || !t_col || !t_kind || !tt_ptr || !tt_perm ||
+        !dangle || !bond_work || !dpos)
+        return PAMNET_EINVAL;
+    if (n == 0) return PAMNET_OK;
+    hipStream_t st = as_stream(stream);
+    if (el > 0) {
+        hipLaunchKernelGGL(bond_grad_pbc_kernel, dim3(blocks_for(el * 64)), dim3(256), 0, st, pos, cell_table, node_graph, l_row,
+                           l_col, ddist_l, el, t_ptr, t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, bond_work);
+        PAMNET_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(pos_grad_pbc_kernel, dim3(blocks_for(n * 64)), dim3(256), 0, st, pos, cell_table, node_graph, n, g_ptr,
+                       g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm, bond_work, dpos);
     PAMNET_LAUNCH_CHECK();
     return PAMNET_OK;
 }

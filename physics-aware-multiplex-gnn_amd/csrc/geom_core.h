@@ -24,3 +24,73 @@ __device__ __forceinline__ float angle3(float ax, float ay, float az, float bx, 
     const float n2 = __fadd_rn(__fadd_rn(__fmul_rn(cx, cx), __fmul_rn(cy, cy)), __fmul_rn(cz, cz));
     return atan2f(__fsqrt_rn(n2), dot);
 }
+
+// ---- periodic cells: the one image rule ------------------------------------------------------------------------------
+// A graph's row of the cell table (pamnet_cell_prepare_f64): 18 doubles, the cell (row k = lattice vector a_k) and then its
+// inverse.  Every periodic kernel takes the displacement between two atoms of one graph from min_image() below and from
+// nowhere else, with cell and inverse out of that one row, so no two kernels can choose different images of a pair.
+constexpr int PBC_ROW = 18;
+constexpr int PBC_BIT = 128;          // flag-word bit: a cell is singular or too small for the cutoff
+
+struct PbcCell {
+    double c[9], inv[9];
+};
+
+__device__ __forceinline__ PbcCell load_cell(const double* __restrict__ table, int64_t g) {
+    PbcCell t;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) t.c[k] = table[PBC_ROW * g + k], t.inv[k] = table[PBC_ROW * g + 9 + k];
+    return t;
+}
+
+struct Disp {
+    double x, y, z;
+};
+
+// Minimum-image displacement a - b: the fp64 difference of the two fp32 positions (exact), times the inverse cell, the three
+// fractional components rounded to the nearest integer (the image n), n @ cell subtracted -- all in fp64, every step an
+// explicit fma / product, so the value does not depend on the kernel the function is inlined into.  Every step is odd in
+// (a - b): n(a, b) == -n(b, a) and the result negates exactly.  With n = 0 the result is the exact difference, whose
+// rounding to fp32 is what the fp32 subtraction of the non-periodic kernels gives.
+__device__ __forceinline__ Disp min_image(const PbcCell& t, float ax, float ay, float az, float bx, float by, float bz) {
+    const double dx = (double)ax - (double)bx, dy = (double)ay - (double)by, dz = (double)az - (double)bz;
+    const double n0 = rint(fma(dz, t.inv[6], fma(dy, t.inv[3], __dmul_rn(dx, t.inv[0]))));
+    const double n1 = rint(fma(dz, t.inv[7], fma(dy, t.inv[4], __dmul_rn(dx, t.inv[1]))));
+    const double n2 = rint(fma(dz, t.inv[8], fma(dy, t.inv[5], __dmul_rn(dx, t.inv[2]))));
+    Disp d;
+    d.x = fma(-n2, t.c[6], fma(-n1, t.c[3], fma(-n0, t.c[0], dx)));
+    d.y = fma(-n2, t.c[7], fma(-n1, t.c[4], fma(-n0, t.c[1], dy)));
+    d.z = fma(-n2, t.c[8], fma(-n1, t.c[5], fma(-n0, t.c[2], dz)));
+    return d;
+}
+
+__device__ __forceinline__ Disp min_image(const PbcCell& t, const float* __restrict__ pos, int64_t a, int64_t b) {
+    return min_image(t, pos[3 * a], pos[3 * a + 1], pos[3 * a + 2], pos[3 * b], pos[3 * b + 1], pos[3 * b + 2]);
+}
+
+// How a kernel of graph construction turns two atoms into a displacement: open space (the raw difference, the arithmetic
+// the kernels always had) or a periodic cell (the image rule, rounded once to fp32).  bind(): once per thread, for the graph
+// its atoms belong to.
+struct OpenSpace {
+    __device__ __forceinline__ void bind(int) {}
+    __device__ __forceinline__ float dist(const float* __restrict__ pos, int64_t a, int64_t b) const { return dist3(pos, a, b); }
+    __device__ __forceinline__ void sub(float ax, float ay, float az, float bx, float by, float bz, float& x, float& y,
+                                        float& z) const {
+        x = ax - bx, y = ay - by, z = az - bz;
+    }
+};
+
+struct Periodic {
+    const double* __restrict__ table;
+    PbcCell t;
+    __device__ __forceinline__ void bind(int g) { t = load_cell(table, g); }
+    __device__ __forceinline__ float dist(const float* __restrict__ pos, int64_t a, int64_t b) const {
+        const Disp d = min_image(t, pos, a, b);
+        return dist3_xyz((float)d.x, (float)d.y, (float)d.z, 0.f, 0.f, 0.f);
+    }
+    __device__ __forceinline__ void sub(float ax, float ay, float az, float bx, float by, float bz, float& x, float& y,
+                                        float& z) const {
+        const Disp d = min_image(t, ax, ay, az, bx, by, bz);
+        x = (float)d.x, y = (float)d.y, z = (float)d.z;
+    }
+};

@@ -377,22 +377,25 @@ __global__ __launch_bounds__(SMALL_THREADS) void csr_small_kernel(const int32_t*
 // reference tree -- parity unpinned, as SURVEY 8c records for every third-party boundary.)
 constexpr int CAP_BIT = 64;
 
-template <bool FILL>
-__global__ __launch_bounds__(256) void radius_kernel(const float* __restrict__ pos,
-                                                     const int32_t* __restrict__ node_graph,
-                                                     const int32_t* __restrict__ gptr, int64_t n, float r,
-                                                     int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
-                                                     int32_t* __restrict__ nbr, float* __restrict__ dist, int64_t cap,
-                                                     int32_t* __restrict__ row_of, int max_nb,
-                                                     int32_t* __restrict__ cap_flag) {
+// GEOM (geom_core.h): OpenSpace = the raw difference of two positions; Periodic = their minimum-image displacement.  One
+// statement of the search for both: the kernels below only choose the policy.
+template <bool FILL, class GEOM>
+__device__ __forceinline__ void radius_search(GEOM geom, const float* __restrict__ pos,
+                                              const int32_t* __restrict__ node_graph,
+                                              const int32_t* __restrict__ gptr, int64_t n, float r,
+                                              int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
+                                              int32_t* __restrict__ nbr, float* __restrict__ dist, int64_t cap,
+                                              int32_t* __restrict__ row_of, int max_nb,
+                                              int32_t* __restrict__ cap_flag) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int g = node_graph[i];
     const int beg = gptr[g], end = gptr[g + 1];
+    geom.bind(g);
     int c = 0, seen = 0;
     int64_t w = FILL ? ptr[i] : 0;
     for (int j = beg; j < end; ++j) {
-        const float d = j == i ? 0.f : dist3(pos, i, j);
+        const float d = j == i ? 0.f : geom.dist(pos, i, j);
         if (j != i && !(d <= r)) continue;
         if (max_nb > 0 && seen >= max_nb) {                    // this hit and everything behind it is cut off
             if (!FILL && cap_flag) atomicOr(cap_flag, CAP_BIT);
@@ -413,23 +416,48 @@ __global__ __launch_bounds__(256) void radius_kernel(const float* __restrict__ p
     if (!FILL) count[i] = c;
 }
 
+template <bool FILL>
+__global__ __launch_bounds__(256) void radius_kernel(const float* __restrict__ pos,
+                                                     const int32_t* __restrict__ node_graph,
+                                                     const int32_t* __restrict__ gptr, int64_t n, float r,
+                                                     int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
+                                                     int32_t* __restrict__ nbr, float* __restrict__ dist, int64_t cap,
+                                                     int32_t* __restrict__ row_of, int max_nb,
+                                                     int32_t* __restrict__ cap_flag) {
+    radius_search<FILL>(OpenSpace{}, pos, node_graph, gptr, n, r, count, ptr, nbr, dist, cap, row_of, max_nb, cap_flag);
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void radius_pbc_kernel(const float* __restrict__ pos, const double* __restrict__ cells,
+                                                         const int32_t* __restrict__ node_graph,
+                                                         const int32_t* __restrict__ gptr, int64_t n, float r,
+                                                         int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
+                                                         int32_t* __restrict__ nbr, float* __restrict__ dist, int64_t cap,
+                                                         int32_t* __restrict__ row_of, int max_nb,
+                                                         int32_t* __restrict__ cap_flag) {
+    Periodic geom;
+    geom.table = cells;
+    radius_search<FILL>(geom, pos, node_graph, gptr, n, r, count, ptr, nbr, dist, cap, row_of, max_nb, cap_flag);
+}
+
 // The same search with one WAVEFRONT per node, for graphs of hundreds of nodes (PDBbind complexes: ~600 atoms): the lanes
 // take 64 consecutive candidates, vote, and the survivors keep ascending order through the prefix population count of
 // the ballot -- identical output.  (One thread per node walks the whole graph alone: 137 + 169 us per batch of 19 000
 // atoms with only 75 workgroups in flight.)
-template <bool FILL>
-__global__ __launch_bounds__(256) void radius_wave_kernel(const float* __restrict__ pos,
-                                                          const int32_t* __restrict__ node_graph,
-                                                          const int32_t* __restrict__ gptr, int64_t n, float r,
-                                                          int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
-                                                          int32_t* __restrict__ nbr, float* __restrict__ dist,
-                                                          int64_t cap, int32_t* __restrict__ row_of, int max_nb,
-                                                          int32_t* __restrict__ cap_flag) {
+template <bool FILL, class GEOM>
+__device__ __forceinline__ void radius_wave_search(GEOM geom, const float* __restrict__ pos,
+                                                   const int32_t* __restrict__ node_graph,
+                                                   const int32_t* __restrict__ gptr, int64_t n, float r,
+                                                   int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
+                                                   int32_t* __restrict__ nbr, float* __restrict__ dist,
+                                                   int64_t cap, int32_t* __restrict__ row_of, int max_nb,
+                                                   int32_t* __restrict__ cap_flag) {
     const int lane = threadIdx.x & 63;
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (i >= n) return;
     const int g = node_graph[i];
     const int beg = gptr[g], end = gptr[g + 1];
+    geom.bind(g);
     int c = 0, seen = 0;
     const int64_t w0 = FILL ? ptr[i] : 0;
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -438,7 +466,7 @@ __global__ __launch_bounds__(256) void radius_wave_kernel(const float* __restric
         float d = 0.f;
         bool keep = false;
         if (j < end && j != i) {
-            d = dist3(pos, i, j);
+            d = geom.dist(pos, i, j);
             keep = d <= r;
         }
         if (max_nb > 0) {                                      // (wave-uniform branch; hits = kept candidates + the query)
@@ -463,6 +491,31 @@ __global__ __launch_bounds__(256) void radius_wave_kernel(const float* __restric
         if (max_nb > 0 && seen >= max_nb && FILL) break;       // nothing behind the cap is written (the count pass keeps
     }                                                          // scanning: a later hit is what raises the flag)
     if (!FILL && lane == 0) count[i] = c;
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void radius_wave_kernel(const float* __restrict__ pos,
+                                                          const int32_t* __restrict__ node_graph,
+                                                          const int32_t* __restrict__ gptr, int64_t n, float r,
+                                                          int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
+                                                          int32_t* __restrict__ nbr, float* __restrict__ dist,
+                                                          int64_t cap, int32_t* __restrict__ row_of, int max_nb,
+                                                          int32_t* __restrict__ cap_flag) {
+    radius_wave_search<FILL>(OpenSpace{}, pos, node_graph, gptr, n, r, count, ptr, nbr, dist, cap, row_of, max_nb, cap_flag);
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void radius_wave_pbc_kernel(const float* __restrict__ pos,
+                                                              const double* __restrict__ cells,
+                                                              const int32_t* __restrict__ node_graph,
+                                                              const int32_t* __restrict__ gptr, int64_t n, float r,
+                                                              int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
+                                                              int32_t* __restrict__ nbr, float* __restrict__ dist,
+                                                              int64_t cap, int32_t* __restrict__ row_of, int max_nb,
+                                                              int32_t* __restrict__ cap_flag) {
+    Periodic geom;
+    geom.table = cells;
+    radius_wave_search<FILL>(geom, pos, node_graph, gptr, n, r, count, ptr, nbr, dist, cap, row_of, max_nb, cap_flag);
 }
 
 // graphs this large on average take the wavefront-per-node form (QM9 molecules: ~18 atoms -> one thread per node)
@@ -912,17 +965,18 @@ __global__ __launch_bounds__(256) void triplet_count_kernel(const int32_t* __res
 
 
 // rows of edge e: [tp_ptr[e], tp_ptr[e+1]) = its triplets (kind 0) followed by its pairs (kind 1)
-__global__ __launch_bounds__(256) void triplet_fill_kernel(const float* __restrict__ pos,
-                                                           const int32_t* __restrict__ lptr,
-                                                           const int32_t* __restrict__ src,
-                                                           const int32_t* __restrict__ dst, int64_t n_edges,
-                                                           int with_triplets, const int32_t* __restrict__ tp_ptr,
-                                                           int32_t* __restrict__ tp_idx, int32_t* __restrict__ tp_edge,
-                                                           float* __restrict__ tp_angle, int32_t* __restrict__ tp_kind,
-                                                           int64_t cap) {
+// GEOM as in radius_search; node_graph: read by the periodic policy alone (the cell of the edge's graph)
+template <class GEOM>
+__device__ __forceinline__ void triplet_fill(GEOM geom, const int32_t* __restrict__ node_graph, const float* __restrict__ pos,
+                                             const int32_t* __restrict__ lptr, const int32_t* __restrict__ src,
+                                             const int32_t* __restrict__ dst, int64_t n_edges, int with_triplets,
+                                             const int32_t* __restrict__ tp_ptr, int32_t* __restrict__ tp_idx,
+                                             int32_t* __restrict__ tp_edge, float* __restrict__ tp_angle,
+                                             int32_t* __restrict__ tp_kind, int64_t cap) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n_edges) return;
     const int j = src[e], i = dst[e];
+    if (node_graph) geom.bind(node_graph[i]);
     const float pix = pos[3 * (int64_t)i], piy = pos[3 * (int64_t)i + 1], piz = pos[3 * (int64_t)i + 2];
     const float pjx = pos[3 * (int64_t)j], pjy = pos[3 * (int64_t)j + 1], pjz = pos[3 * (int64_t)j + 2];
     int64_t w = tp_ptr[e];
@@ -936,7 +990,10 @@ __global__ __launch_bounds__(256) void triplet_fill_kernel(const float* __restri
             tp_idx[w] = q;
             tp_edge[w] = (int32_t)e;
             tp_kind[w] = 0;
-            tp_angle[w] = angle3(pjx - pix, pjy - piy, pjz - piz, pkx - pjx, pky - pjy, pkz - pjz);
+            float ax, ay, az, bx, by, bz;
+            geom.sub(pjx, pjy, pjz, pix, piy, piz, ax, ay, az);
+            geom.sub(pkx, pky, pkz, pjx, pjy, pjz, bx, by, bz);
+            tp_angle[w] = angle3(ax, ay, az, bx, by, bz);
             ++w;
         }
     }
@@ -948,9 +1005,76 @@ __global__ __launch_bounds__(256) void triplet_fill_kernel(const float* __restri
         tp_idx[w] = q;
         tp_edge[w] = (int32_t)e;
         tp_kind[w] = 1;
-        tp_angle[w] = angle3(pix - pjx, piy - pjy, piz - pjz, px - pix, py - piy, pz - piz);
+        float ax, ay, az, bx, by, bz;
+        geom.sub(pix, piy, piz, pjx, pjy, pjz, ax, ay, az);
+        geom.sub(px, py, pz, pix, piy, piz, bx, by, bz);
+        tp_angle[w] = angle3(ax, ay, az, bx, by, bz);
         ++w;
     }
+}
+
+__global__ __launch_bounds__(256) void triplet_fill_kernel(const float* __restrict__ pos,
+                                                           const int32_t* __restrict__ lptr,
+                                                           const int32_t* __restrict__ src,
+                                                           const int32_t* __restrict__ dst, int64_t n_edges,
+                                                           int with_triplets, const int32_t* __restrict__ tp_ptr,
+                                                           int32_t* __restrict__ tp_idx, int32_t* __restrict__ tp_edge,
+                                                           float* __restrict__ tp_angle, int32_t* __restrict__ tp_kind,
+                                                           int64_t cap) {
+    triplet_fill(OpenSpace{}, nullptr, pos, lptr, src, dst, n_edges, with_triplets, tp_ptr, tp_idx, tp_edge, tp_angle, tp_kind,
+                 cap);
+}
+
+__global__ __launch_bounds__(256) void triplet_fill_pbc_kernel(const float* __restrict__ pos, const double* __restrict__ cells,
+                                                               const int32_t* __restrict__ node_graph,
+                                                               const int32_t* __restrict__ lptr,
+                                                               const int32_t* __restrict__ src,
+                                                               const int32_t* __restrict__ dst, int64_t n_edges,
+                                                               int with_triplets, const int32_t* __restrict__ tp_ptr,
+                                                               int32_t* __restrict__ tp_idx, int32_t* __restrict__ tp_edge,
+                                                               float* __restrict__ tp_angle, int32_t* __restrict__ tp_kind,
+                                                               int64_t cap) {
+    Periodic geom;
+    geom.table = cells;
+    triplet_fill(geom, node_graph, pos, lptr, src, dst, n_edges, with_triplets, tp_ptr, tp_idx, tp_edge, tp_angle, tp_kind, cap);
+}
+
+// One thread per graph: the cell (row k = lattice vector a_k) and its inverse by adjugate, in fp64, into the graph's row of
+// the table; PBC_BIT when the cell is singular, not finite, or one of its perpendicular heights |det| / |a_i x a_j| does not
+// exceed 2 * cutoff (a pair could then have two images within the cutoff).  A singular cell gets a zero inverse (image 0:
+// the open-space distances), so that whatever runs before the host reads the flag stays finite.
+__global__ __launch_bounds__(256) void cell_prepare_kernel(const float* __restrict__ cell, int64_t n_graphs, double cutoff,
+                                                           double* __restrict__ table, int32_t* __restrict__ flag) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_graphs) return;
+    double a[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) a[k] = (double)cell[9 * g + k];
+    // x[k] = a_{k+1} x a_{k+2}: column k of the adjugate; det = a_0 . x[0]
+    double x[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double* u = a + 3 * ((k + 1) % 3);
+        const double* v = a + 3 * ((k + 2) % 3);
+        x[k][0] = u[1] * v[2] - u[2] * v[1];
+        x[k][1] = u[2] * v[0] - u[0] * v[2];
+        x[k][2] = u[0] * v[1] - u[1] * v[0];
+    }
+    const double det = a[0] * x[0][0] + a[1] * x[0][1] + a[2] * x[0][2];
+    bool ok = isfinite(det) && det != 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double area = sqrt(x[k][0] * x[k][0] + x[k][1] * x[k][1] + x[k][2] * x[k][2]);
+        ok = ok && (fabs(det) / area > 2.0 * cutoff);         // (NaN compares false)
+    }
+    const bool invertible = isfinite(det) && det != 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) table[PBC_ROW * g + k] = a[k];
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) table[PBC_ROW * g + 9 + 3 * m + k] = invertible ? x[k][m] / det : 0.0;
+    if (!ok) atomicOr(flag, PBC_BIT);
 }
 
 // ---- transposed triplet / pair row list without a sort -----------------------------------------------------------------
@@ -1220,6 +1344,55 @@ extern "C" int pamnet_radius_fill_i32(const float* pos, const int32_t* node_grap
     return PAMNET_OK;
 }
 
+extern "C" int pamnet_cell_prepare_f64(const float* cell, int64_t n_graphs, float cutoff, double* table, int32_t* flag,
+                                       pamnet_stream_t stream) {
+    if (n_graphs < 0 || !(cutoff > 0.f) || !(cutoff <= 3.0e38f)) return PAMNET_EINVAL;      // (NaN and inf refused)
+    if (n_graphs == 0) return PAMNET_OK;
+    if (!cell || !table || !flag) return PAMNET_ENULL;
+    hipLaunchKernelGGL(cell_prepare_kernel, dim3(blocks_for(n_graphs)), dim3(256), 0, as_stream(stream), cell, n_graphs,
+                       (double)cutoff, table, flag);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
+extern "C" int pamnet_radius_pbc_count_i32(const float* pos, const double* cell_table, const int32_t* node_graph,
+                                           const int32_t* gptr, int64_t n, int64_t n_graphs, float r, int64_t max_neighbors,
+                                           int32_t* count, int32_t* cap_flag, pamnet_stream_t stream) {
+    if (n < 0 || n_graphs < 0 || max_neighbors < 0 || max_neighbors > 0x7fffffff) return PAMNET_EINVAL;
+    if (n == 0) return PAMNET_OK;
+    if (!pos || !cell_table || !node_graph || !gptr || !count) return PAMNET_ENULL;
+    const int mx = (int)max_neighbors;
+    if (n_graphs > 0 && n >= RADIUS_WAVE_MIN_NODES * n_graphs)
+        hipLaunchKernelGGL((radius_wave_pbc_kernel<false>), dim3(blocks_for(n, 4)), dim3(256), 0, as_stream(stream), pos,
+                           cell_table, node_graph, gptr, n, r, count, (const int32_t*)nullptr, (int32_t*)nullptr,
+                           (float*)nullptr, (int64_t)0, (int32_t*)nullptr, mx, cap_flag);
+    else
+        hipLaunchKernelGGL((radius_pbc_kernel<false>), dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), pos, cell_table,
+                           node_graph, gptr, n, r, count, (const int32_t*)nullptr, (int32_t*)nullptr, (float*)nullptr,
+                           (int64_t)0, (int32_t*)nullptr, mx, cap_flag);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
+extern "C" int pamnet_radius_pbc_fill_i32(const float* pos, const double* cell_table, const int32_t* node_graph,
+                                          const int32_t* gptr, int64_t n, int64_t n_graphs, float r, int64_t max_neighbors,
+                                          const int32_t* ptr, int32_t* nbr, float* dist, int32_t* row_of, int64_t cap,
+                                          pamnet_stream_t stream) {
+    if (n < 0 || cap < 0 || n_graphs < 0 || max_neighbors < 0 || max_neighbors > 0x7fffffff) return PAMNET_EINVAL;
+    if (n == 0) return PAMNET_OK;
+    if (!pos || !cell_table || !node_graph || !gptr || !ptr || !nbr || !dist) return PAMNET_ENULL;
+    const int mx = (int)max_neighbors;
+    if (n_graphs > 0 && n >= RADIUS_WAVE_MIN_NODES * n_graphs)
+        hipLaunchKernelGGL((radius_wave_pbc_kernel<true>), dim3(blocks_for(n, 4)), dim3(256), 0, as_stream(stream), pos,
+                           cell_table, node_graph, gptr, n, r, (int32_t*)nullptr, ptr, nbr, dist, cap, row_of, mx,
+                           (int32_t*)nullptr);
+    else
+        hipLaunchKernelGGL((radius_pbc_kernel<true>), dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), pos, cell_table,
+                           node_graph, gptr, n, r, (int32_t*)nullptr, ptr, nbr, dist, cap, row_of, mx, (int32_t*)nullptr);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
 extern "C" int pamnet_knn_i32(const float* pos, const int32_t* node_graph, const int32_t* gptr, int64_t n, int32_t k,
                               float cutoff, int32_t* nbr, float* dist, pamnet_stream_t stream) {
     if (n < 0 || k < 1 || k > 64) return PAMNET_EINVAL;
@@ -1403,6 +1576,20 @@ extern "C" int pamnet_triplet_fill_f32(const float* pos, const int32_t* lptr, co
     return PAMNET_OK;
 }
 
+extern "C" int pamnet_triplet_fill_pbc_f32(const float* pos, const double* cell_table, const int32_t* node_graph,
+                                           const int32_t* lptr, const int32_t* src, const int32_t* dst, int64_t n_edges,
+                                           int32_t with_triplets, const int32_t* tp_ptr, int32_t* tp_idx, int32_t* tp_edge,
+                                           float* tp_angle, int32_t* tp_kind, int64_t cap, pamnet_stream_t stream) {
+    if (n_edges < 0 || cap < 0) return PAMNET_EINVAL;
+    if (n_edges == 0) return PAMNET_OK;
+    if (!pos || !cell_table || !node_graph || !lptr || !src || !dst || !tp_ptr || !tp_idx || !tp_edge || !tp_angle || !tp_kind)
+        return PAMNET_ENULL;
+    hipLaunchKernelGGL(triplet_fill_pbc_kernel, dim3(blocks_for(n_edges)), dim3(256), 0, as_stream(stream), pos, cell_table,
+                       node_graph, lptr, src, dst, n_edges, (int)with_triplets, tp_ptr, tp_idx, tp_edge, tp_angle, tp_kind,
+                       cap);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
 
 // ---- transposed CSR of a symmetric graph = the reverse-edge index --------------------------------------------------------
 // Rows = aggregation targets i, columns j ascending inside a row (radius graphs: pamnet_radius_fill_i32).  The transposed

@@ -7,7 +7,8 @@ Same constructor arguments, attribute names, `state_dict()` keys/shapes and `for
 
 forward(data): duck-typed `data` with `.x`, `.batch` (sorted) and, for QM9, `.pos` [N,3] and `.edge_index` [2,E]
 (optionally `.num_graphs`).  QM9 without `.edge_index` (absent or None): bond-free molecules, the local graph is the radius
-graph at cutoff_l.  Returns fp32 [num_graphs], differentiable w.r.t. every parameter.  MI355X only: tensors must
+graph at cutoff_l; such a batch may carry `.cell` (fp32 [num_graphs, 3, 3], row k = lattice vector a_k): periodic boundaries, every
+displacement the model uses is then the minimum-image one (graph.build_graph).  Returns fp32 [num_graphs], differentiable w.r.t. every parameter.  MI355X only: tensors must
 live on a HIP device -- there is no CPU path (the CPU oracle in oracle/ is test infrastructure and is never imported
 from here).
 """
@@ -471,7 +472,8 @@ class _PAMNetBase(nn.Module):
                           need_grad=torch.is_grad_enabled(), with_triplets=not self.small,
                           n_types=self.embeddings.size(0) if hasattr(self, 'embeddings') else None,
                           sizes=self._sizes_of(data), default_basis=self.sbf.default, mol_local=self._mol_local_of(data),
-                          max_num_neighbors=self.max_num_neighbors, aux_tables=self.dim == fused.D)
+                          max_num_neighbors=self.max_num_neighbors, aux_tables=self.dim == fused.D,
+                          cell=getattr(data, 'cell', None))
         if g.check is not None:                          # zero-host-sync path: the flag word waits for verify()
             self._pending_checks.append(g.check)
         g.need_grad = torch.is_grad_enabled()

@@ -192,6 +192,7 @@ class Graph(object):
     """All index / geometry tensors one forward needs (int32 / fp32 on the device)."""
 
     capped = False        # max_num_neighbors cut a row of the radius graph: not symmetric, general transposes (build_graph)
+    cell_tab = None       # periodic batch: the cell table [num_graphs, 18] fp64 every *_pbc_* kernel reads (cell_table)
     pos_grad = False      # geometry linked to positions that require grad (differentiable_geometry)
 
     # Row lists / counts per kind are only needed by the generic (non-fused) path and by tests: built on first use so
@@ -217,25 +218,47 @@ class Graph(object):
         return int(self.pair_rows.numel())
 
 
-def radius_count(pos, node_graph, gptr, r, max_neighbors=0, cap_flag=None):
+PBC_BIT = 128         # flag-word bit: a periodic cell is singular or too small for the cutoffs (csrc/geom_core.h)
+
+
+def cell_table(cell, cutoff, flag):
+    """The table every periodic kernel reads (pamnet_cell_prepare_f64): per graph the cell and its inverse, fp64 [G, 18].  ORs
+    PBC_BIT into `flag` (the batch's validity word) when a cell is singular or has a perpendicular height <= 2 * cutoff."""
+    ng = int(cell.size(0))
+    tab = torch.empty((ng, 18), dtype=torch.float64, device=cell.device)
+    lib.call('pamnet_cell_prepare_f64', lib.ptr(cell), ng, float(cutoff), lib.ptr(tab), lib.ptr(flag), lib.stream_of(cell))
+    return tab
+
+
+def radius_count(pos, node_graph, gptr, r, max_neighbors=0, cap_flag=None, cell_tab=None):
     """Scanned neighbour counts of the radius search.  max_neighbors > 0: torch_cluster's max_num_neighbors (first hits in
-    index order, the query itself counted); a truncated row ORs CAP_BIT into `cap_flag` (an int32 device word)."""
+    index order, the query itself counted); a truncated row ORs CAP_BIT into `cap_flag` (an int32 device word).
+    `cell_tab` (cell_table): the search under periodic cells, distances by the minimum image."""
     n = pos.size(0)
     count = _i32(n, pos.device)
-    lib.call('pamnet_radius_count_i32', lib.ptr(pos), lib.ptr(node_graph), lib.ptr(gptr), n, int(gptr.numel()) - 1,
-             float(r), int(max_neighbors or 0), lib.ptr(count), lib.ptr(cap_flag), lib.stream_of(pos))
+    if cell_tab is not None:
+        lib.call('pamnet_radius_pbc_count_i32', lib.ptr(pos), lib.ptr(cell_tab), lib.ptr(node_graph), lib.ptr(gptr), n,
+                 int(gptr.numel()) - 1, float(r), int(max_neighbors or 0), lib.ptr(count), lib.ptr(cap_flag), lib.stream_of(pos))
+    else:
+        lib.call('pamnet_radius_count_i32', lib.ptr(pos), lib.ptr(node_graph), lib.ptr(gptr), n, int(gptr.numel()) - 1,
+                 float(r), int(max_neighbors or 0), lib.ptr(count), lib.ptr(cap_flag), lib.stream_of(pos))
     return exclusive_scan(count)
 
 
-def radius_fill(pos, node_graph, gptr, r, ptr, total, zeroed=False, rows_out=None, max_neighbors=0):
+def radius_fill(pos, node_graph, gptr, r, ptr, total, zeroed=False, rows_out=None, max_neighbors=0, cell_tab=None):
     """`rows_out`: a one-element list that receives the expanded row ids (the query node of every entry), written by the
     same launch."""
     nbr = _alloc_i32(total, pos.device, zeroed)
     dist = _alloc_f32(total, pos.device, zeroed)
     row_of = _alloc_i32(total, pos.device, zeroed) if rows_out is not None else None
-    lib.call('pamnet_radius_fill_i32', lib.ptr(pos), lib.ptr(node_graph), lib.ptr(gptr), pos.size(0), int(gptr.numel()) - 1,
-             float(r), int(max_neighbors or 0), lib.ptr(ptr), lib.ptr(nbr), lib.ptr(dist), lib.ptr(row_of), int(total),
-             lib.stream_of(pos))
+    if cell_tab is not None:
+        lib.call('pamnet_radius_pbc_fill_i32', lib.ptr(pos), lib.ptr(cell_tab), lib.ptr(node_graph), lib.ptr(gptr), pos.size(0),
+                 int(gptr.numel()) - 1, float(r), int(max_neighbors or 0), lib.ptr(ptr), lib.ptr(nbr), lib.ptr(dist),
+                 lib.ptr(row_of), int(total), lib.stream_of(pos))
+    else:
+        lib.call('pamnet_radius_fill_i32', lib.ptr(pos), lib.ptr(node_graph), lib.ptr(gptr), pos.size(0), int(gptr.numel()) - 1,
+                 float(r), int(max_neighbors or 0), lib.ptr(ptr), lib.ptr(nbr), lib.ptr(dist), lib.ptr(row_of), int(total),
+                 lib.stream_of(pos))
     if rows_out is not None:
         rows_out.append(row_of)
     return ptr, nbr, dist
@@ -430,6 +453,39 @@ CAP_BIT = 64          # flag-word bit: max_num_neighbors truncated a row of the 
 def _raise_bad_inputs():
     raise IndexError('index out of range in the batch handed to PAMNet.forward: `batch` must be sorted with ids in '
                      '[0, num_graphs), atom types in [0, embeddings.size(0)), edge_index in [0, num_nodes)')
+
+
+def _raise_bad_cell(cutoff_l, cutoff_g):
+    rc = max(float(cutoff_l), float(cutoff_g))
+    raise ValueError('periodic cell too small or singular: every cell of the batch must be non-singular with each of its three '
+                     'perpendicular heights |det| / |a_i x a_j| above 2 * max(cutoff_l, cutoff_g) = %g (each pair then has at '
+                     'most one image within the cutoffs) -- replicate the cell into a supercell, or lower the cutoffs' % (2 * rc))
+
+
+def _checked_cell(cell, dataset, edge_index, sizes, n_graphs, pos):
+    """`data.cell` as the kernels read it (fp32 [num_graphs, 9], contiguous), or the refusal that says what to do instead."""
+    if dataset != 'QM9':
+        raise ValueError('periodic cells (`cell`) are implemented for the QM9 schema (pos + atom types) only, not for %r: drop '
+                         '`cell`, or hand the structure over as a QM9-schema batch' % (dataset,))
+    if edge_index is not None:
+        raise ValueError('periodic batches are bond-free: hand over `cell` without `edge_index` (the local graph is then the '
+                         'minimum-image radius graph at cutoff_l), or drop `cell` for a bonded molecule in open space')
+    if sizes is not None:
+        raise ValueError('a batch that carries host-side `sizes` (store.MoleculeStore) has no periodic path: hand the periodic '
+                         'batch over as plain tensors (x, pos, batch, cell) without `sizes`')
+    if pos is None:
+        raise ValueError('`cell` needs `pos`')
+    if not isinstance(cell, torch.Tensor) or cell.dtype != torch.float32 or tuple(cell.shape) != (int(n_graphs), 3, 3):
+        raise ValueError('`cell` must be a float32 tensor of shape [num_graphs, 3, 3] = [%d, 3, 3] (row k of cell[g] = lattice '
+                         'vector a_k of graph g); got %s %s' % (int(n_graphs), getattr(cell, 'dtype', type(cell)),
+                                                                tuple(getattr(cell, 'shape', ()))))
+    if cell.device != pos.device:
+        raise ValueError('`cell` must live on the device of `pos` (%s); it is on %s -- move it with cell.to(pos.device)'
+                         % (pos.device, cell.device))
+    if cell.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError('gradients with respect to `cell` (stress, virial) are not implemented: detach the cell '
+                                  '(cell.detach()); forces with respect to `pos` are available')
+    return cell.detach().contiguous().view(int(n_graphs), 9)
 
 
 class GraphCheckError(IndexError):
@@ -699,8 +755,14 @@ def _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=N
 
 def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_index=None, num_graphs=None,
                 need_grad=True, knn_k=None, with_triplets=True, n_types=None, sizes=None, default_basis=True, mol_local=None,
-                max_num_neighbors=None, aux_tables=True):
+                max_num_neighbors=None, aux_tables=True, cell=None):
     """Graph-construction part of PAMNet.forward (models.py:104-177).  Returns a Graph.
+
+    `cell` (QM9 schema, bond-free, no `sizes`): fp32 [num_graphs, 3, 3] on the device, row k of cell[g] = lattice vector a_k of
+    graph g.  Every displacement between two atoms of a graph is then the minimum-image one (csrc/geom_core.h min_image): both
+    radius searches, the bond lengths, both angle kinds and the position backward.  Positions need not be wrapped.  Each cell
+    must be non-singular with all three perpendicular heights above 2 * max(cutoff_l, cutoff_g) (ValueError otherwise, with the
+    sizes' round trip).  Always the step-by-step launches.
 
     `sizes`: (global edges, local edges, triplet + pair rows) of this batch as host integers -- what a batch collated by
     pamnet_amd.store.MoleculeStore carries.  With them no value is read back from the device: buffers are sized from
@@ -724,6 +786,8 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
     `aux_tables`: also make what only the dim = 128 layer engine reads (the node-aligned work split of its fused global-edge
     kernels, the two index hops of its local aggregation's backward); a model of a narrow width passes False."""
     dev = batch.device
+    if cell is not None:                          # (before anything is built: every refusal of a periodic batch)
+        cell = _checked_cell(cell, dataset, edge_index, sizes, num_graphs if num_graphs is not None else int(batch[-1]) + 1, pos)
     max_nb = int(max_num_neighbors or 0)
     capped = False
     knn_k = KNN_K if knn_k is None else int(knn_k)
@@ -776,13 +840,17 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
             flag = ing[5]
         else:
             flag = _input_flag(node_graph, g.n_graphs, x_raw.to(torch.float32).reshape(-1), n_types)
-        if (sizes is None and ing is not None and MOL_LOCAL and mol_local is not False
+        if (sizes is None and ing is not None and MOL_LOCAL and mol_local is not False and cell is None
                 and not 0 < max_nb <= MOL_ATOMS
                 and (mol_local is True or n <= MOL_ATOMS * g.n_graphs // 2)):
             if _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=cutoff_l):
                 return _with_seg_cuts(g, dataset) if aux_tables else g
-        gptr_g = radius_count(pos, node_graph, g.gptr, cutoff_g, max_nb, flag)
-        lp = radius_count(pos, node_graph, g.gptr, cutoff_l)
+        # Periodic cells: the same sequence with the minimum-image forms of the two searches and of the angle fill (the index
+        # kernels do not know: under the cell condition the graph is still a simple symmetric one).  The table is prepared
+        # first; its verdict (PBC_BIT) travels in the validity word with the sizes' round trip.
+        tab = g.cell_tab = None if cell is None else cell_table(cell, max(float(cutoff_l), float(cutoff_g)), flag)
+        gptr_g = radius_count(pos, node_graph, g.gptr, cutoff_g, max_nb, flag, cell_tab=tab)
+        lp = radius_count(pos, node_graph, g.gptr, cutoff_l, cell_tab=tab)
         if sizes is not None:                     # zero host round trips (see `sizes`)
             total_g, total_l, tp_hint = (int(v) for v in sizes)
             g.check = flag
@@ -794,15 +862,18 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
             deg = (lp[1:] - lp[:-1]).long()
             tp_dev = (deg * deg + (deg * (deg - 1) if with_triplets else 0)).sum()
             total_g, total_l, tp_hint, bad = host_ints(gptr_g[-1], lp[-1], tp_dev, flag)
-            if bad & ~CAP_BIT:
+            if bad & ~(CAP_BIT | PBC_BIT):
                 _raise_bad_inputs()
+            if bad & PBC_BIT:
+                _raise_bad_cell(cutoff_l, cutoff_g)
             capped = bool(bad & CAP_BIT)
         gp, gn, gd = radius_fill(pos, node_graph, g.gptr, cutoff_g, gptr_g, total_g, zeroed=hinted, rows_out=glob_rows,
-                                 max_neighbors=max_nb)
+                                 max_neighbors=max_nb, cell_tab=tab)
         if capped and flow != 'target_to_source':     # (stored by neighbour: see the bonded branch below)
             gp, gn, gd, glob_inv = _transpose_edges(gp, gn, gd, n, want_inverse=need_grad, q=glob_rows.pop())
         loc_rows = []
-        lp, l_src, l_dist = radius_fill(pos, node_graph, g.gptr, cutoff_l, lp, total_l, zeroed=hinted, rows_out=loc_rows)
+        lp, l_src, l_dist = radius_fill(pos, node_graph, g.gptr, cutoff_l, lp, total_l, zeroed=hinted, rows_out=loc_rows,
+                                        cell_tab=tab)
         l_dst = loc_rows[0]
         loc_radius = True
     elif dataset == 'QM9':
@@ -980,8 +1051,13 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
         tcount = bonds.tcount
     tp_idx, tp_edge, tp_kind = (_alloc_i32(tot, dev, hinted) for _ in range(3))
     tp_angle = _alloc_f32(tot, dev, hinted)
-    lib.call('pamnet_triplet_fill_f32', lib.ptr(pos), lib.ptr(lp), lib.ptr(l_src), lib.ptr(l_dst), e_l, wt,
-             lib.ptr(tp_ptr), lib.ptr(tp_idx), lib.ptr(tp_edge), lib.ptr(tp_angle), lib.ptr(tp_kind), tot, st)
+    if g.cell_tab is not None:
+        lib.call('pamnet_triplet_fill_pbc_f32', lib.ptr(pos), lib.ptr(g.cell_tab), lib.ptr(node_graph), lib.ptr(lp),
+                 lib.ptr(l_src), lib.ptr(l_dst), e_l, wt, lib.ptr(tp_ptr), lib.ptr(tp_idx), lib.ptr(tp_edge), lib.ptr(tp_angle),
+                 lib.ptr(tp_kind), tot, st)
+    else:
+        lib.call('pamnet_triplet_fill_f32', lib.ptr(pos), lib.ptr(lp), lib.ptr(l_src), lib.ptr(l_dst), e_l, wt,
+                 lib.ptr(tp_ptr), lib.ptr(tp_idx), lib.ptr(tp_edge), lib.ptr(tp_angle), lib.ptr(tp_kind), tot, st)
     if checks:                                    # one launch: size mismatches join the validity flag (PAMNet.verify)
         _check_sizes(g.check, checks, getattr(g, 'all_kept', None), getattr(g, 'loops', None))
     g.tp = CSR(tp_ptr, tp_edge, tp_idx)               # rows = target edge e, col = source edge e'
@@ -1083,6 +1159,7 @@ class _Geometry(torch.autograd.Function):
     def forward(ctx, pos, g):
         ctx.save_for_backward(pos)
         ctx.idx = _index_lists(g)
+        ctx.pbc = None if g.cell_tab is None else (g.cell_tab, g.node_graph)      # periodic graph: the image rule's inputs
         return g.dist_g.clone(), g.dist_l.clone(), g.tp_angle.clone()
 
     @staticmethod
@@ -1096,6 +1173,14 @@ class _Geometry(torch.autograd.Function):
         d_dg, d_dl, d_ang = d_dg.contiguous(), d_dl.contiguous(), d_ang.contiguous()
         work = torch.empty(3 * max(el, 1), dtype=torch.float64, device=pos.device)
         dpos = torch.empty((n, 3), dtype=torch.float32, device=pos.device)
+        if ctx.pbc is not None:
+            tab, node_graph = ctx.pbc
+            lib.call('pamnet_pos_bwd_pbc_f32', lib.ptr(pos), lib.ptr(tab), lib.ptr(node_graph), n, lib.ptr(g_ptr), lib.ptr(g_row),
+                     lib.ptr(g_col), lib.ptr(gt_ptr), lib.ptr(gt_perm), lib.ptr(d_dg), eg, lib.ptr(l_ptr), lib.ptr(l_row),
+                     lib.ptr(l_col), lib.ptr(lt_ptr), lib.ptr(lt_perm), lib.ptr(d_dl), el, lib.ptr(t_ptr), lib.ptr(t_row),
+                     lib.ptr(t_col), lib.ptr(t_kind), lib.ptr(tt_ptr), lib.ptr(tt_perm), lib.ptr(d_ang), tp, lib.ptr(work),
+                     lib.ptr(dpos), lib.stream_of(pos))
+            return dpos, None
         lib.call('pamnet_pos_bwd_f32', lib.ptr(pos), n, lib.ptr(g_ptr), lib.ptr(g_row), lib.ptr(g_col), lib.ptr(gt_ptr),
                  lib.ptr(gt_perm), lib.ptr(d_dg), eg, lib.ptr(l_ptr), lib.ptr(l_row), lib.ptr(l_col), lib.ptr(lt_ptr),
                  lib.ptr(lt_perm), lib.ptr(d_dl), el, lib.ptr(t_ptr), lib.ptr(t_row), lib.ptr(t_col), lib.ptr(t_kind),
