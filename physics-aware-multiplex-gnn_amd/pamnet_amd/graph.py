@@ -8,7 +8,9 @@ Edge storage differs from the reference on purpose: edges are kept in CSR order 
 (deterministic, atomics-free segment sums), i.e. a permutation of the reference's edge list.  Results are invariant to
 that permutation up to fp32 summation order.
 """
+import ctypes
 import os
+from collections import namedtuple
 
 import torch
 
@@ -75,22 +77,17 @@ def expand_rows(ptr, total, zeroed=False):
     return out
 
 
+_SCALAR_KINDS = {torch.int32: 0, torch.bool: 1, torch.uint8: 1, torch.int64: 2}
+
+
 def host_ints(*scalars):
     """Data-dependent sizes come back to the host in ONE round trip: every call is a stream synchronisation that drains
     the launch queue, and forward-only runs are bound by exactly these."""
-    import ctypes
     n = len(scalars)
     ts = [s.reshape(-1)[:1] for s in scalars]
-    kinds = []
-    for t in ts:
-        if t.dtype == torch.int32:
-            kinds.append(0)
-        elif t.dtype in (torch.bool, torch.uint8):
-            kinds.append(1)
-        elif t.dtype == torch.int64:
-            kinds.append(2)
-        else:
-            raise TypeError('host_ints: unsupported dtype %s' % t.dtype)
+    kinds = [_SCALAR_KINDS.get(t.dtype) for t in ts]
+    if None in kinds:
+        raise TypeError('host_ints: unsupported dtype %s' % ts[kinds.index(None)].dtype)
     out = torch.empty(n, dtype=torch.int64, device=ts[0].device)
     lib.call('pamnet_gather_scalars_i64', n, (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts]),
              (ctypes.c_int32 * n)(*kinds), lib.ptr(out), lib.stream_of(out))
@@ -134,12 +131,6 @@ def csr_filter2(ptr_in, nbr, dist, cut_a, cut_b, flag=None):
         if bad:
             _raise_bad_inputs()
     return _filter_fill(ptr_in, nbr, dist, cut_a, pa, ta), _filter_fill(ptr_in, nbr, dist, cut_b, pb, tb)
-
-
-def edge_dist(pos, a, b):
-    out = _f32(a.numel(), pos.device)
-    lib.call('pamnet_edge_dist_f32', lib.ptr(pos), lib.ptr(a), lib.ptr(b), a.numel(), lib.ptr(out), lib.stream_of(pos))
-    return out
 
 
 class CSR(object):
@@ -230,18 +221,23 @@ def cell_table(cell, cutoff, flag):
     return tab
 
 
+def _call_in_cell(open_sym, pbc_sym, pos, pbc, *rest):
+    """lib.call of a kernel that has a periodic twin.  `pbc` None: the open-space symbol; else the tensors the twin takes
+    behind `pos` -- (cell_tab,) for the searches, (cell_tab, node_graph) where the kernel has no batch vector of its own."""
+    if pbc is None:
+        return lib.call(open_sym, lib.ptr(pos), *rest)
+    return lib.call(pbc_sym, lib.ptr(pos), *[lib.ptr(t) for t in pbc], *rest)
+
+
 def radius_count(pos, node_graph, gptr, r, max_neighbors=0, cap_flag=None, cell_tab=None):
     """Scanned neighbour counts of the radius search.  max_neighbors > 0: torch_cluster's max_num_neighbors (first hits in
     index order, the query itself counted); a truncated row ORs CAP_BIT into `cap_flag` (an int32 device word).
     `cell_tab` (cell_table): the search under periodic cells, distances by the minimum image."""
     n = pos.size(0)
     count = _i32(n, pos.device)
-    if cell_tab is not None:
-        lib.call('pamnet_radius_pbc_count_i32', lib.ptr(pos), lib.ptr(cell_tab), lib.ptr(node_graph), lib.ptr(gptr), n,
-                 int(gptr.numel()) - 1, float(r), int(max_neighbors or 0), lib.ptr(count), lib.ptr(cap_flag), lib.stream_of(pos))
-    else:
-        lib.call('pamnet_radius_count_i32', lib.ptr(pos), lib.ptr(node_graph), lib.ptr(gptr), n, int(gptr.numel()) - 1,
-                 float(r), int(max_neighbors or 0), lib.ptr(count), lib.ptr(cap_flag), lib.stream_of(pos))
+    _call_in_cell('pamnet_radius_count_i32', 'pamnet_radius_pbc_count_i32', pos, None if cell_tab is None else (cell_tab,),
+                  lib.ptr(node_graph), lib.ptr(gptr), n, int(gptr.numel()) - 1, float(r), int(max_neighbors or 0),
+                  lib.ptr(count), lib.ptr(cap_flag), lib.stream_of(pos))
     return exclusive_scan(count)
 
 
@@ -251,14 +247,9 @@ def radius_fill(pos, node_graph, gptr, r, ptr, total, zeroed=False, rows_out=Non
     nbr = _alloc_i32(total, pos.device, zeroed)
     dist = _alloc_f32(total, pos.device, zeroed)
     row_of = _alloc_i32(total, pos.device, zeroed) if rows_out is not None else None
-    if cell_tab is not None:
-        lib.call('pamnet_radius_pbc_fill_i32', lib.ptr(pos), lib.ptr(cell_tab), lib.ptr(node_graph), lib.ptr(gptr), pos.size(0),
-                 int(gptr.numel()) - 1, float(r), int(max_neighbors or 0), lib.ptr(ptr), lib.ptr(nbr), lib.ptr(dist),
-                 lib.ptr(row_of), int(total), lib.stream_of(pos))
-    else:
-        lib.call('pamnet_radius_fill_i32', lib.ptr(pos), lib.ptr(node_graph), lib.ptr(gptr), pos.size(0), int(gptr.numel()) - 1,
-                 float(r), int(max_neighbors or 0), lib.ptr(ptr), lib.ptr(nbr), lib.ptr(dist), lib.ptr(row_of), int(total),
-                 lib.stream_of(pos))
+    _call_in_cell('pamnet_radius_fill_i32', 'pamnet_radius_pbc_fill_i32', pos, None if cell_tab is None else (cell_tab,),
+                  lib.ptr(node_graph), lib.ptr(gptr), pos.size(0), int(gptr.numel()) - 1, float(r), int(max_neighbors or 0),
+                  lib.ptr(ptr), lib.ptr(nbr), lib.ptr(dist), lib.ptr(row_of), int(total), lib.stream_of(pos))
     if rows_out is not None:
         rows_out.append(row_of)
     return ptr, nbr, dist
@@ -398,6 +389,24 @@ def _input_flag(node_graph, n_graphs, types=None, n_types=None, src=None, dst=No
 _KINDS = {torch.int64: 1, torch.int32: 2, torch.float32: 3}
 
 
+def _type_column(x, n):
+    """`x` as the flat column of `n` atom types that the ingest launch and the graph engine read, or None."""
+    xcol = x.reshape(-1) if (x.dim() == 1 or (x.dim() == 2 and x.size(1) == 1)) else None
+    return None if (xcol is None or xcol.dtype not in _KINDS or xcol.numel() != n) else xcol
+
+
+def _edge_rows(edge_index):
+    """The two rows of `edge_index` as the ingest launch and the graph engine read them (contiguous each), or None."""
+    if edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_index.dtype not in _KINDS:
+        return None
+    es, ed = edge_index[0], edge_index[1]
+    return (es, ed) if (es.is_contiguous() and ed.is_contiguous()) else None
+
+
+# totals: four zeroed words behind the flags (the molecule-local builder's counters)
+Ingested = namedtuple('Ingested', 'node_graph gptr types src dst flag loops totals')
+
+
 def ingest(batch, n_graphs, x=None, n_types=None, edge_index=None):
     """The reference's index tensors as the kernels want them, in one launch (pamnet_ingest_indices_i32): int32 batch
     vector, per-graph node pointer, int32 atom types, int32 bond endpoints, and a two-word flag (invalid index / self
@@ -408,19 +417,18 @@ def ingest(batch, n_graphs, x=None, n_types=None, edge_index=None):
         return None
     xk, xs, xcol = 0, 1, None
     if x is not None and n_types is not None:
-        xcol = x.reshape(-1) if (x.dim() == 1 or (x.dim() == 2 and x.size(1) == 1)) else None
-        if xcol is None or xcol.dtype not in _KINDS or xcol.numel() != n:
+        xcol = _type_column(x, n)
+        if xcol is None:
             return None
         xk, xs = _KINDS[xcol.dtype], (xcol.stride(0) if n > 1 else 1)
         if xs < 1:
             return None
     ne, ek, es, ed = 0, 0, None, None
     if edge_index is not None:
-        if edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_index.dtype not in _KINDS:
+        rows = _edge_rows(edge_index)
+        if rows is None:
             return None
-        es, ed = edge_index[0], edge_index[1]
-        if not (es.is_contiguous() and ed.is_contiguous()):
-            return None
+        es, ed = rows
         ne, ek = int(es.numel()), _KINDS[edge_index.dtype]
     dev = batch.device
     na, ea = (n + 3) // 4 * 4, (ne + 3) // 4 * 4          # 16-byte aligned sections of one allocation
@@ -433,13 +441,12 @@ def ingest(batch, n_graphs, x=None, n_types=None, edge_index=None):
              ed.data_ptr() if ne else None, ek, ne, node_graph.data_ptr() if n else None, gf.data_ptr(),
              types.data_ptr() if n else None, src.data_ptr() if ne else None, dst.data_ptr() if ne else None,
              lib.stream_of(batch))
-    return node_graph, gf[:n_graphs + 1], (types if xk else None), src, dst, gf[n_graphs + 1:n_graphs + 2], \
-        gf[n_graphs + 2:n_graphs + 3], gf[n_graphs + 3:n_graphs + 7]
+    return Ingested(node_graph, gf[:n_graphs + 1], (types if xk else None), src, dst, gf[n_graphs + 1:n_graphs + 2],
+                    gf[n_graphs + 2:n_graphs + 3], gf[n_graphs + 3:n_graphs + 7])
 
 
 def _check_sizes(flag, checks, all_kept=None, loops=None):
     """One launch: OR the size-mismatch bits into the validity flag word (pamnet_check_sizes_i32)."""
-    import ctypes
     n = len(checks)
     actual = (ctypes.c_void_p * n)(*[lib.ptr(t) for t, _ in checks])
     expected = (ctypes.c_int64 * n)(*[int(v) for _, v in checks])
@@ -533,7 +540,7 @@ def raise_for_flag(bits):
                               + ', '.join(what) + ' -- results of this batch are invalid')
 
 
-ENGINE = __import__('os').environ.get('PAMNET_GRAPH_ENGINE', '1') != '0'    # measurement aid: 0 = the step-by-step path
+ENGINE = os.environ.get('PAMNET_GRAPH_ENGINE', '1') != '0'    # measurement aid: 0 = the step-by-step path
 # QM9 schema, small molecules: the molecule-local builder (csrc/graph_mol.hip, two launches); False = the step-by-step
 # launches (the tests compare the two bit by bit)
 MOL_LOCAL = True
@@ -582,14 +589,10 @@ class EngineGraph(Graph):
         return v
 
 
-_SCHEMA = {'QM9': 0, 'PDBbind': 1, 'rna': 2}
-
-
 def _engine_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos, edge_index, n_graphs, need_grad, knn_k,
                   with_triplets, n_types, sizes, default_basis=True, mol_local=False, max_nb=0, aux_tables=True):
     """The zero-host-sync graph as one engine call, or None when this batch does not qualify (empty lists, layouts the
     ingest launch does not read): the step-by-step path below then builds it."""
-    import ctypes
     rna = dataset[:3].lower() == 'rna'
     n = int(batch.numel())
     eg, el, tp = (int(v) for v in sizes)
@@ -608,14 +611,10 @@ def _engine_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos, edge_ind
     if dataset == 'QM9':
         if pos is None or edge_index is None or n_types is None:
             return None
-        xcol = x_raw.reshape(-1) if (x_raw.dim() == 1 or (x_raw.dim() == 2 and x_raw.size(1) == 1)) else None
-        if xcol is None or xcol.dtype not in _KINDS or xcol.numel() != n:
+        xcol, rows = _type_column(x_raw, n), _edge_rows(edge_index)
+        if xcol is None or rows is None or int(rows[0].numel()) != el:
             return None
-        if edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_index.dtype not in _KINDS:
-            return None
-        es, ed = edge_index[0], edge_index[1]
-        if not (es.is_contiguous() and ed.is_contiguous()) or int(es.numel()) != el:
-            return None
+        es, ed = rows
         pos = pos if (pos.dtype == torch.float32 and pos.is_contiguous()) else pos.to(torch.float32).contiguous()
         d.schema, d.n_bonds = 0, el
         d.mol_local = 1 if (mol_local and MOL_LOCAL and not 0 < max_nb <= MOL_ATOMS) else 0
@@ -693,20 +692,16 @@ def _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=N
     (a molecule over the builder's limits, bonds not grouped by molecule, self loops): nothing of `g` was touched.
     `cutoff_l`: the bond-free form -- `ing` carries no bonds, the local graph is the radius graph at cutoff_l and its size
     comes back with the other totals."""
-    import ctypes
-    node_graph, gptr, _, src0, dst0, flag, loops, totals = ing       # totals: four zeroed words behind the flags
+    gptr, src0, dst0, flag, loops, totals = ing.gptr, ing.src, ing.dst, ing.flag, ing.loops, ing.totals
     dev = pos.device
     free = cutoff_l is not None
     n, ng, m = g.n, g.n_graphs, int(src0.numel())
     st = lib.stream_of(pos)
     mol_tot = _i32(4 * ng, dev)
     wt = 1 if with_triplets else 0
-    if free:
-        lib.call('pamnet_mol_graph_free_count_i32', lib.ptr(pos), lib.ptr(gptr), n, ng, float(cutoff_l), float(cutoff_g), wt,
-                 lib.ptr(mol_tot), lib.ptr(totals), st)
-    else:
-        lib.call('pamnet_mol_graph_count_i32', lib.ptr(pos), lib.ptr(gptr), n, ng, lib.ptr(src0), lib.ptr(dst0), m,
-                 float(cutoff_g), wt, lib.ptr(mol_tot), lib.ptr(totals), st)
+    local = (float(cutoff_l),) if free else (lib.ptr(src0), lib.ptr(dst0), m)      # what defines the local graph
+    lib.call('pamnet_mol_graph_free_count_i32' if free else 'pamnet_mol_graph_count_i32', lib.ptr(pos), lib.ptr(gptr), n, ng,
+             *local, float(cutoff_g), wt, lib.ptr(mol_tot), lib.ptr(totals), st)
     eg, tp, viol, counted, bad, lp_ = host_ints(totals[0], totals[1], totals[2], totals[3], flag, loops)
     if bad:
         _raise_bad_inputs()
@@ -733,12 +728,9 @@ def _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=N
     if need_grad:
         o.gT_perm, o.lT_ptr, o.lT_perm = gT_perm.data_ptr(), lT_ptr.data_ptr(), lT_perm.data_ptr()
         o.tT_ptr, o.tT_perm = tT_ptr.data_ptr(), tT_perm.data_ptr()
-    if free:
-        lib.call('pamnet_mol_graph_free_fill_i32', lib.ptr(pos), lib.ptr(gptr), n, ng, m, float(cutoff_l), float(cutoff_g), wt,
-                 1 if need_grad else 0, lib.ptr(mol_tot), eg, tp, ctypes.addressof(o), st)
-    else:
-        lib.call('pamnet_mol_graph_fill_i32', lib.ptr(pos), lib.ptr(gptr), n, ng, lib.ptr(src0), lib.ptr(dst0), m,
-                 float(cutoff_g), wt, 1 if need_grad else 0, lib.ptr(mol_tot), eg, tp, ctypes.addressof(o), st)
+    local = (m, float(cutoff_l)) if free else (lib.ptr(src0), lib.ptr(dst0), m)
+    lib.call('pamnet_mol_graph_free_fill_i32' if free else 'pamnet_mol_graph_fill_i32', lib.ptr(pos), lib.ptr(gptr), n, ng,
+             *local, float(cutoff_g), wt, 1 if need_grad else 0, lib.ptr(mol_tot), eg, tp, ctypes.addressof(o), st)
     g.loops = loops
     g.pos = pos
     g.glob, g.dist_g = CSR(g_ptr, g_row, g_col), g_dist
@@ -751,6 +743,319 @@ def _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=N
         g.loc_T = _Given(lT_ptr, lT_perm, n)
         g.tp_T = _Given(tT_ptr, tT_perm, max(m, 1))
     return True
+
+
+class _Sizes(object):
+    """Where the data-dependent sizes of one build come from (build_graph, `sizes`).  None: from the device, in host round
+    trips that carry the validity flag word along (read).  Host numbers: the buffers come zero-filled out of `arena` (what the
+    `zeroed=` parameters take), every device total is expected to be its host number (expect), one launch checks them at the end."""
+    __slots__ = ('flag', 'known', 'arena', 'checks')
+
+    def __init__(self, flag, sizes):
+        self.flag, self.arena = flag, False
+        self.known = None if sizes is None else tuple(int(v) for v in sizes)
+        self.checks = []                          # (device total, value the host assumed)
+
+    def reserve(self, ints, dev):
+        self.arena = _ZeroArena(ints, dev)
+
+    def expect(self, ptr, k, clamp=True):
+        """The scanned pointer `ptr` is expected to end at `k`.  Returns it capped at k, what the buffers hold: with sizes that
+        turn out too small every kernel that walks it still stays inside its arrays (such a batch is invalid and flagged)."""
+        self.checks.append((ptr[-1:], k))
+        return torch.clamp(ptr, max=k) if clamp else ptr
+
+    def read(self, *scalars, allow=0, cutoffs=None):
+        """The device scalars and the flag word in ONE host round trip: (integers, capped).  Raises for a flag bit outside
+        `allow` (CAP_BIT: the neighbour cap bound, no error; PBC_BIT: a bad cell, raised second, with `cutoffs`)."""
+        got = host_ints(*scalars, self.flag)
+        bad = got.pop()
+        if bad & ~allow:
+            _raise_bad_inputs()
+        if bad & PBC_BIT:
+            _raise_bad_cell(*cutoffs)
+        return got, bool(bad & CAP_BIT)
+
+
+class _Lists(object):
+    """What a schema's list builder hands to the common tail (_finish): the global list by aggregation row (gp, gn, gd; g_rows
+    = the expanded row ids when the fill wrote them), the local one (lp, l_src, l_dst, l_dist), and what the builder happens
+    to know already."""
+    sign = cell_tab = None                        # PDBbind: +1 pocket / -1 ligand per node; periodic batch: cell_table
+    gp = gn = gd = g_rows = lp = l_src = l_dst = l_dist = None
+    tp_ptr = tp_total = tcount = None             # triplet / pair pointer, total and triplet counts, if made already
+    tp_hint = None                                # triplet + pair rows already known on the host
+    capped = False                                # max_num_neighbors cut a row: the global list is not symmetric
+    glob_inv = loc_inv = None                     # InverseTranspose of a list that was stored by query and then transposed
+    loc_radius = False                            # the local list is an uncapped radius graph (symmetric)
+    loops = all_kept = None                       # bonded QM9: the self-loop words the size check folds in
+
+    def __init__(self, pos, sz):
+        self.pos, self.sz = pos, sz
+
+    def global_by_neighbour(self, n, need_grad, zeroed=False):
+        """edge_index_g = (query, neighbour) and the layer aggregates at edge_index[1] = the NEIGHBOUR
+        (global_message_passing.py:38 with flow = source_to_target): a symmetric list can be read either way, a capped or
+        kNN one has to be stored by neighbour."""
+        self.gp, self.gn, self.gd, self.glob_inv = _transpose_edges(self.gp, self.gn, self.gd, n, zeroed=zeroed,
+                                                                    want_inverse=need_grad, q=self.g_rows)
+        self.g_rows = None
+
+
+_Args = namedtuple('_Args', 'cutoff_l cutoff_g flow x_raw pos edge_index need_grad knn_k with_triplets n_types sizes mol_local '
+                            'max_nb cell')
+_Bonds = namedtuple('_Bonds', 'ptr src dst dist tp_ptr tcount raw')
+
+
+def _flag(g, ing, types=None, n_types=None, src=None, dst=None):
+    """The validity flag word of the batch: the ingest launch's, or a validation launch of its own (tensor-op route)."""
+    if ing is not None:
+        return ing.flag
+    if types is not None:
+        types = types.to(torch.float32).reshape(-1)
+    return _input_flag(g.node_graph, g.n_graphs, types, n_types, src, dst)
+
+
+def _builder_applies(g, ing, a):
+    """Plain QM9-schema tensors that the molecule-local builder may take: the ingest launch's outputs, no host sizes, and
+    small molecules on average unless the caller vouches for every one."""
+    return (a.sizes is None and ing is not None and MOL_LOCAL and a.mol_local is not False
+            and not 0 < a.max_nb <= MOL_ATOMS            # (a molecule of <= MOL_ATOMS atoms cannot reach a larger cap)
+            and (a.mol_local is True or g.n <= MOL_ATOMS * g.n_graphs // 2))
+
+
+def _symmetric_tp_total(ptr, with_triplets):
+    """Triplet + pair rows of a symmetric graph from its degrees alone (a device scalar): every edge (j -> i) has deg(j) - 1
+    triplets (edges k -> j, k != i) and deg(i) pairs (edges j' -> i, itself included; models.py:68-98)."""
+    deg = (ptr[1:] - ptr[:-1]).long()
+    return (deg * deg + (deg * (deg - 1) if with_triplets else 0)).sum()
+
+
+def _bond_lists(pos, n, with_triplets, ei=None, raw=None):
+    """The bond graph by target with its lengths and its triplet / pair pointer; j, i = edge_index (models.py:64)."""
+    src0, dst0 = raw if raw is not None else (ei[0].to(I32).contiguous(), ei[1].to(I32).contiguous())
+    ptr, perm = csr_from_keys(dst0, n)
+    m, dev = int(src0.numel()), pos.device
+    src, dst, dist = _i32(m, dev), _i32(m, dev), _f32(m, dev)
+    lib.call('pamnet_gather2_i32', lib.ptr(perm), lib.ptr(src0), lib.ptr(dst0), m, lib.ptr(src), lib.ptr(dst),
+             lib.ptr(pos), lib.ptr(dist), lib.stream_of(src0))                    # + the bond lengths (models.py:65)
+    tp_ptr, tcount = _triplet_ptr(ptr, src, dst, with_triplets)
+    return _Bonds(ptr, src, dst, dist, tp_ptr, tcount, (src0, dst0))
+
+
+def _qm9_bond_free(g, ing, a):
+    """Bond-free molecules: the local graph is the radius graph at cutoff_l inside every molecule (what the reference's
+    forward, models.py:104-115, computes when handed edge_index = radius(pos, pos, cutoff_l, batch, batch): get_edge_info
+    strips the self loops) -- a search of its own, without a neighbour cap, so cutoff_l may lie on either side of cutoff_g
+    and a cap that binds in the global search leaves it alone.  Returns None when the molecule-local builder has filled `g`."""
+    pos = a.pos.to(torch.float32).contiguous()
+    flag = _flag(g, ing, a.x_raw, a.n_types)
+    if a.cell is None and _builder_applies(g, ing, a):
+        if _mol_local_graph(g, pos, ing, a.cutoff_g, a.with_triplets, a.need_grad, cutoff_l=a.cutoff_l):
+            return None
+    r = _Lists(pos, _Sizes(flag, a.sizes))
+    sz, r.loc_radius = r.sz, True
+    # Periodic cells: the same sequence with the minimum-image forms of the two searches and of the angle fill.  The table is
+    # prepared first; its verdict (PBC_BIT) travels in the validity word with the sizes' round trip.
+    tab = r.cell_tab = None if a.cell is None else cell_table(a.cell, max(float(a.cutoff_l), float(a.cutoff_g)), flag)
+    gptr_g = radius_count(pos, g.node_graph, g.gptr, a.cutoff_g, a.max_nb, flag, cell_tab=tab)
+    lp = radius_count(pos, g.node_graph, g.gptr, a.cutoff_l, cell_tab=tab)
+    if sz.known is not None:
+        total_g, total_l, r.tp_hint = sz.known
+        sz.reserve(3 * total_g + 3 * total_l + 5 * r.tp_hint + 64, pos.device)
+        gptr_g, lp = sz.expect(gptr_g, total_g), sz.expect(lp, total_l)
+    else:
+        (total_g, total_l, r.tp_hint), r.capped = sz.read(gptr_g[-1], lp[-1], _symmetric_tp_total(lp, a.with_triplets),
+                                                          allow=CAP_BIT | PBC_BIT, cutoffs=(a.cutoff_l, a.cutoff_g))
+    rows = []
+    r.gp, r.gn, r.gd = radius_fill(pos, g.node_graph, g.gptr, a.cutoff_g, gptr_g, total_g, zeroed=sz.arena, rows_out=rows,
+                                   max_neighbors=a.max_nb, cell_tab=tab)
+    r.g_rows = rows.pop()
+    if r.capped and a.flow != 'target_to_source':
+        r.global_by_neighbour(g.n, a.need_grad)
+    r.lp, r.l_src, r.l_dist = radius_fill(pos, g.node_graph, g.gptr, a.cutoff_l, lp, total_l, zeroed=sz.arena, rows_out=rows,
+                                          cell_tab=tab)
+    r.l_dst = rows.pop()
+    return r
+
+
+def _qm9_bonded(g, ing, a):
+    """One host round trip for all three data-dependent sizes: the bond graph's CSR and its triplet / pair counts do not
+    depend on the radius graph, so they are computed first, on the assumption that the bond list has no self loops
+    (remove_self_loops, models.py:63, is a no-op for QM9 bond graphs); the flag that verifies it comes back with the sizes,
+    and a batch that does have self loops is redone the slow way.  Returns None when the molecule-local builder has filled `g`."""
+    pos = a.pos.to(torch.float32).contiguous()
+    n, ei = g.n, a.edge_index
+    if ei.size(1) > 0 and _builder_applies(g, ing, a):
+        if _mol_local_graph(g, pos, ing, a.cutoff_g, a.with_triplets, a.need_grad):
+            return None
+    b = _bond_lists(pos, n, a.with_triplets, ei, None if ing is None else (ing.src, ing.dst))
+    flag = _flag(g, ing, a.x_raw, a.n_types, *b.raw)
+    r = _Lists(pos, _Sizes(flag, a.sizes))
+    sz = r.sz
+    if ing is not None:                           # self loops were noted by the ingest launch: non-zero = NOT all kept
+        kept = r.loops = ing.loops
+    else:
+        kept = (ei[0] != ei[1]).all()
+    gptr_g = radius_count(pos, g.node_graph, g.gptr, a.cutoff_g, a.max_nb, flag)    # symmetric (unless the cap binds): agg = query
+    tp_ptr = b.tp_ptr
+    if sz.known is not None:
+        total_g, total_l, tp_total = sz.known
+        if ing is None:
+            r.all_kept = kept
+        sz.reserve(3 * total_g + 5 * tp_total + 64, pos.device)
+        gptr_g = sz.expect(gptr_g, total_g)
+        sz.expect(b.ptr, total_l, clamp=False)    # (the bond count is an input size: nothing is sized by it)
+        tp_ptr = sz.expect(tp_ptr, tp_total)
+    else:
+        (total_g, k, tp_total), r.capped = sz.read(gptr_g[-1], kept, tp_ptr[-1], allow=CAP_BIT)
+        if (k != 0) if ing is not None else (not k):                            # the bond list has self loops
+            b = _bond_lists(pos, n, a.with_triplets, ei[:, ei[0] != ei[1]])
+            tp_ptr, tp_total = b.tp_ptr, int(b.tp_ptr[-1])
+    rows = []
+    r.gp, r.gn, r.gd = radius_fill(pos, g.node_graph, g.gptr, a.cutoff_g, gptr_g, total_g, zeroed=sz.arena, rows_out=rows,
+                                   max_neighbors=a.max_nb)
+    r.g_rows = rows.pop()
+    if r.capped and a.flow != 'target_to_source':
+        r.global_by_neighbour(n, a.need_grad)
+    r.lp, r.l_src, r.l_dst, r.l_dist = b.ptr, b.src, b.dst, b.dist
+    r.tp_ptr, r.tp_total, r.tcount = tp_ptr, tp_total, b.tcount
+    return r
+
+
+def _pdbbind(g, ing, a):
+    """ONE host round trip for all three data-dependent sizes.  The local graph (global edges with dist <= cutoff_l,
+    models.py:131-134) is the radius graph at cutoff_l, so its per-node degrees come from a second count pass over the
+    positions instead of from the filled global graph; and because a radius graph is symmetric, the number of triplet / pair
+    rows follows from the degrees alone (_symmetric_tp_total)."""
+    xr = a.x_raw.unsqueeze(-1) if a.x_raw.dim() == 1 else a.x_raw
+    pos = xr[:, :3].to(torch.float32).contiguous()
+    n, ng, gptr = g.n, g.node_graph, g.gptr
+    sign = torch.where(pos[:, 0] > 40.0, -torch.ones_like(pos[:, 0]), torch.ones_like(pos[:, 0])).contiguous()
+    flag = _flag(g, ing)
+    gptr_g = radius_count(pos, ng, gptr, a.cutoff_g, a.max_nb, flag)
+    local = a.cutoff_l <= a.cutoff_g
+    r = _Lists(pos, _Sizes(flag, a.sizes if local else None))
+    sz, r.sign = r.sz, sign
+    fill_nb = a.max_nb
+    if local:
+        lp = radius_count(pos, ng, gptr, a.cutoff_l)
+    if sz.known is not None:
+        total_g, total_l, r.tp_hint = sz.known
+        sz.reserve(3 * total_g + 3 * total_l + 5 * r.tp_hint + 64, pos.device)
+        gptr_g, lp = sz.expect(gptr_g, total_g), sz.expect(lp, total_l)
+        fill_nb = 0                               # (a cap that binds is flagged by the count pass, the batch invalid: see raise_for_flag)
+    elif local:
+        (total_g, total_l, tp_total), r.capped = sz.read(gptr_g[-1], lp[-1], _symmetric_tp_total(lp, a.with_triplets),
+                                                         allow=CAP_BIT)
+        r.tp_hint = None if r.capped else tp_total
+    else:                                         # (a local cutoff above the global one: the general, dependent order)
+        (total_g,), r.capped = sz.read(gptr_g[-1], allow=CAP_BIT)
+    rows = [] if local else None
+    r.gp, r.gn, r.gd = radius_fill(pos, ng, gptr, a.cutoff_g, gptr_g, total_g, zeroed=sz.arena, rows_out=rows,
+                                   max_neighbors=fill_nb)
+    if local and not r.capped:
+        r.lp, r.l_src, r.l_dist = _filter_fill(r.gp, r.gn, r.gd, a.cutoff_l, lp, total_l, zeroed=sz.arena)
+    else:                  # a cut of the filled global graph, sized by a read-back of its own (models.py:131-134): the degrees of
+        r.lp, r.l_src, r.l_dist = csr_filter(r.gp, r.gn, r.gd, a.cutoff_l)        # a CAPPED graph's cut are not the radius degrees
+    r.g_rows = rows.pop() if rows else None
+    r.loc_radius = not r.capped
+    if r.capped:
+        # (query, neighbour) lists, as the RNA kNN cuts: the local layer aggregates at the neighbour
+        # (local_message_passing.py:39,54), the global one too unless flow = target_to_source
+        r.lp, r.l_src, r.l_dist, r.loc_inv = _transpose_edges(r.lp, r.l_src, r.l_dist, n, want_inverse=a.need_grad)
+        if a.flow != 'target_to_source':
+            r.global_by_neighbour(n, a.need_grad)
+        r.g_rows = None                           # (a capped list's row ids only ever serve as that transposition's queries)
+    r.l_dst = expand_rows(r.lp, r.l_src.numel(), zeroed=sz.arena)
+    return r
+
+
+def _rna(g, ing, a):
+    """The kNN graph with both its cuts, models.py:147-150 (global) and 153-156 (local: j = query, i = nbr)."""
+    xr = a.x_raw.unsqueeze(-1) if a.x_raw.dim() == 1 else a.x_raw
+    pos = xr[:, :3].to(torch.float32).contiguous()
+    n, ng, gptr = g.n, g.node_graph, g.gptr
+    flag = _flag(g, ing, xr[:, -1], a.n_types)
+    r = _Lists(pos, _Sizes(flag, a.sizes))
+    sz = r.sz
+    gq = qq = None                                # query ids of the entries, when the launch that wrote the lists gave them
+    if sz.known is not None:
+        kp, kn, kd = knn_table(pos, ng, gptr, a.knn_k, float('inf'))             # (query, neighbour) rows, self dropped
+        total_g, total_l, r.tp_hint = sz.known
+        pa, pb = _filter_count(kp, kn, kd, a.cutoff_g), _filter_count(kp, kn, kd, a.cutoff_l)
+        sz.reserve(4 * total_g + 4 * total_l + 5 * r.tp_hint + 64, pos.device)
+        pa, pb = sz.expect(pa, total_g), sz.expect(pb, total_l)
+        r.gp, r.gn, r.gd = _filter_fill(kp, kn, kd, a.cutoff_g, pa, total_g, zeroed=sz.arena)
+        qp, qn, qd = _filter_fill(kp, kn, kd, a.cutoff_l, pb, total_l, zeroed=sz.arena)
+    elif n > 0 and a.knn_k <= 64:                 # one search, both cuts, one host round trip
+        if KNN_TP_TOTAL:                          # ... and the triplet / pair total of the local cut with them
+            (r.gp, r.gn, r.gd, gq), (qp, qn, qd, qq), r.tp_hint = knn_cuts(pos, ng, gptr, a.knn_k, a.cutoff_g, a.cutoff_l, flag,
+                                                                           tp_of_b=bool(a.with_triplets))
+        else:
+            (r.gp, r.gn, r.gd, gq), (qp, qn, qd, qq) = knn_cuts(pos, ng, gptr, a.knn_k, a.cutoff_g, a.cutoff_l, flag)
+    else:
+        kp, kn, kd = knn_table(pos, ng, gptr, a.knn_k, float('inf'))
+        (r.gp, r.gn, r.gd), (qp, qn, qd) = csr_filter2(kp, kn, kd, a.cutoff_g, a.cutoff_l, flag)
+    r.g_rows = gq                                 # rows = queries: the expanded row ids are the query ids
+    if a.flow != 'target_to_source':              # aggregate at edge_index[1] = neighbour
+        r.global_by_neighbour(n, a.need_grad, zeroed=sz.arena)
+    # (the local layer always aggregates at i)
+    r.lp, r.l_src, r.l_dist, r.loc_inv = _transpose_edges(qp, qn, qd, n, zeroed=sz.arena, want_inverse=a.need_grad, q=qq)
+    r.l_dst = expand_rows(r.lp, r.l_src.numel(), zeroed=sz.arena)
+    return r
+
+
+def _finish(g, r, dataset, a):
+    """The common tail: the CSR objects of the lists `r`, the triplet / pair rows with their angles (models.py:68-98,
+    165-177; combined rows grouped by target edge), the deferred size check and the backward's transposed lists."""
+    sz, pos, n, dev = r.sz, r.pos, g.n, r.pos.device
+    zeroed = sz.arena
+    g.pos, g.sign, g.capped = pos, r.sign, r.capped
+    if r.cell_tab is not None:
+        g.cell_tab = r.cell_tab
+    if sz.known is not None:
+        g.check = sz.flag
+    if r.loops is not None:
+        g.loops = r.loops
+    if r.all_kept is not None:
+        g.all_kept = r.all_kept
+    g.glob = CSR(r.gp, r.g_rows if r.g_rows is not None else expand_rows(r.gp, r.gn.numel(), zeroed=zeroed), r.gn)
+    g.dist_g = r.gd
+    g.loc = CSR(r.lp, r.l_dst, r.l_src)
+    g.dist_l = r.l_dist
+    e_l = g.loc.m
+    wt = 1 if a.with_triplets else 0
+    tp_ptr, tot, tcount = r.tp_ptr, r.tp_total, r.tcount
+    if tp_ptr is None:
+        tp_ptr, tcount = _triplet_ptr(r.lp, r.l_src, r.l_dst, a.with_triplets)
+        tot = r.tp_hint if r.tp_hint is not None else int(tp_ptr[-1])
+        if zeroed:
+            tp_ptr = sz.expect(tp_ptr, tot)
+    tp_idx, tp_edge, tp_kind = (_alloc_i32(tot, dev, zeroed) for _ in range(3))
+    tp_angle = _alloc_f32(tot, dev, zeroed)
+    _call_in_cell('pamnet_triplet_fill_f32', 'pamnet_triplet_fill_pbc_f32', pos,
+                  None if r.cell_tab is None else (r.cell_tab, g.node_graph), lib.ptr(r.lp), lib.ptr(r.l_src), lib.ptr(r.l_dst),
+                  e_l, wt, lib.ptr(tp_ptr), lib.ptr(tp_idx), lib.ptr(tp_edge), lib.ptr(tp_angle), lib.ptr(tp_kind), tot,
+                  lib.stream_of(pos))
+    if sz.checks:                                 # one launch: size mismatches join the validity flag (PAMNet.verify)
+        _check_sizes(sz.flag, sz.checks, r.all_kept, r.loops)
+    g.tp = CSR(tp_ptr, tp_edge, tp_idx)           # rows = target edge e, col = source edge e'
+    g.tp_angle, g.tp_kind = tp_angle, tp_kind
+    g.glob_T = g.loc_T = g.tp_T = _NoTranspose    # forward-only: backward index structures are not built
+    if a.need_grad:
+        # d x[j] of the global gather: the reverse-edge index of a radius graph (symmetric by construction, unless the
+        # neighbour cap cut it); for a list stored by neighbour the inverse of that transposition; a counting sort otherwise
+        radius_g = dataset in ('QM9', 'PDBbind') and not r.capped
+        g.glob_T = SymmetricTranspose(g.glob) if radius_g else (r.glob_inv if r.glob_inv is not None
+                                                               else Transpose(g.glob.col, n))
+        # d x[j] of the local gather: a radius graph for PDBbind and bond-free QM9, the inverse transposition for RNA;
+        # user-supplied bonds (QM9) take the counting sort
+        g.loc_T = SymmetricTranspose(g.loc) if r.loc_radius else (r.loc_inv if r.loc_inv is not None
+                                                                  else Transpose(g.loc.col, n))
+        # d m_neighbor[e'] of the triplet/pair gather
+        g.tp_T = (TripletTranspose(g.loc, g.loc_T, tp_ptr, tcount, tot, a.with_triplets, zeroed=zeroed)
+                  if (e_l > 0 and tot > 0) else Transpose(tp_idx, max(e_l, 1)))
 
 
 def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_index=None, num_graphs=None,
@@ -785,300 +1090,49 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
 
     `aux_tables`: also make what only the dim = 128 layer engine reads (the node-aligned work split of its fused global-edge
     kernels, the two index hops of its local aggregation's backward); a model of a narrow width passes False."""
-    dev = batch.device
+    n_graphs = None if num_graphs is None else int(num_graphs)
     if cell is not None:                          # (before anything is built: every refusal of a periodic batch)
-        cell = _checked_cell(cell, dataset, edge_index, sizes, num_graphs if num_graphs is not None else int(batch[-1]) + 1, pos)
+        if n_graphs is None:
+            n_graphs = int(batch[-1]) + 1
+        cell = _checked_cell(cell, dataset, edge_index, sizes, n_graphs, pos)
     max_nb = int(max_num_neighbors or 0)
-    capped = False
     knn_k = KNN_K if knn_k is None else int(knn_k)
     if sizes is not None and knn_k != KNN_K:
         raise ValueError('host-side sizes (store.MoleculeStore) are counted for k = %d neighbours; got knn_k = %d' % (KNN_K, knn_k))
     if sizes is not None and num_graphs is not None:
-        eng = _engine_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos, edge_index, num_graphs, need_grad, knn_k,
+        eng = _engine_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos, edge_index, n_graphs, need_grad, knn_k,
                             with_triplets, n_types, sizes, default_basis, mol_local=bool(mol_local), max_nb=max_nb,
                             aux_tables=aux_tables)
         if eng is not None:
             return eng
     g = Graph()
-    n = int(batch.numel())
-    g.n = n
-    g.n_graphs = int(num_graphs) if num_graphs is not None else int(batch[-1]) + 1
-    g.types = None                                # int32 atom types (QM9), by-product of the ingest launch
+    g.sign = g.check = None                       # (check: device flag word of the zero-host-sync path, see `sizes`)
+    n = g.n = int(batch.numel())
+    g.n_graphs = n_graphs if n_graphs is not None else int(batch[-1]) + 1
     rna = dataset[:3].lower() == 'rna'
     ing = None
     if batch.is_cuda and n > 0:
         if dataset == 'QM9':
-            if n_types is not None:                   # (edge_index None: the bond-free batch, validated without edges)
+            if n_types is not None:               # (edge_index None: the bond-free batch, validated without edges)
                 ing = ingest(batch, g.n_graphs, x_raw, n_types, edge_index)
-        elif rna and n_types is not None and x_raw.dim() == 2:                      # the type id is x's last column
+        elif rna and n_types is not None and x_raw.dim() == 2:                  # the type id is x's last column
             ing = ingest(batch, g.n_graphs, x_raw[:, -1], n_types)
         elif rna or dataset == 'PDBbind':
             ing = ingest(batch, g.n_graphs)
-    if ing is not None:
-        node_graph, g.gptr, g.types = ing[0], ing[1], ing[2]
+    if ing is not None:                           # (types: int32 atom types, QM9 / RNA, a by-product of the ingest launch)
+        g.node_graph, g.gptr, g.types = ing.node_graph, ing.gptr, ing.types
     else:
-        node_graph = batch.to(I32).contiguous()
-        g.gptr, _ = csr_from_keys(node_graph, g.n_graphs)
-    g.node_graph = node_graph
-    g.sign = None
-    g.check = None                                # device flag word of the zero-host-sync path (see `sizes`)
-    tp_pre = None
-    tp_hint = None                                # triplet + pair rows already known on the host (PDBbind)
-    hinted = False
-    checks = []                                   # (device total, value the host assumed), verified by one launch at the end
-    glob_rows = []                                # row ids of the global edges when the launch that fills them writes them
-    glob_inv = loc_inv = None                     # InverseTranspose of a list that was stored by query and then transposed
-    loc_radius = False                            # the local graph is an uncapped radius graph of its own (symmetric)
-
-    if dataset == 'QM9' and edge_index is None:
-        # Bond-free molecules: the local graph is the radius graph at cutoff_l inside every molecule (what the reference's
-        # forward, models.py:104-115, computes when handed edge_index = radius(pos, pos, cutoff_l, batch, batch): get_edge_info
-        # strips the self loops) -- a search of its own, without a neighbour cap, so cutoff_l may lie on either side of cutoff_g
-        # and a cap that binds in the global search leaves it alone.
-        pos = pos.to(torch.float32).contiguous()
-        if ing is not None:
-            flag = ing[5]
-        else:
-            flag = _input_flag(node_graph, g.n_graphs, x_raw.to(torch.float32).reshape(-1), n_types)
-        if (sizes is None and ing is not None and MOL_LOCAL and mol_local is not False and cell is None
-                and not 0 < max_nb <= MOL_ATOMS
-                and (mol_local is True or n <= MOL_ATOMS * g.n_graphs // 2)):
-            if _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=cutoff_l):
-                return _with_seg_cuts(g, dataset) if aux_tables else g
-        # Periodic cells: the same sequence with the minimum-image forms of the two searches and of the angle fill (the index
-        # kernels do not know: under the cell condition the graph is still a simple symmetric one).  The table is prepared
-        # first; its verdict (PBC_BIT) travels in the validity word with the sizes' round trip.
-        tab = g.cell_tab = None if cell is None else cell_table(cell, max(float(cutoff_l), float(cutoff_g)), flag)
-        gptr_g = radius_count(pos, node_graph, g.gptr, cutoff_g, max_nb, flag, cell_tab=tab)
-        lp = radius_count(pos, node_graph, g.gptr, cutoff_l, cell_tab=tab)
-        if sizes is not None:                     # zero host round trips (see `sizes`)
-            total_g, total_l, tp_hint = (int(v) for v in sizes)
-            g.check = flag
-            checks += [(gptr_g[-1:], total_g), (lp[-1:], total_l)]
-            hinted = _ZeroArena(3 * total_g + 3 * total_l + 5 * tp_hint + 64, dev)
-            gptr_g, lp = torch.clamp(gptr_g, max=total_g), torch.clamp(lp, max=total_l)
-        else:
-            # ONE host round trip: the triplet / pair total of a symmetric graph follows from its degrees (see PDBbind below)
-            deg = (lp[1:] - lp[:-1]).long()
-            tp_dev = (deg * deg + (deg * (deg - 1) if with_triplets else 0)).sum()
-            total_g, total_l, tp_hint, bad = host_ints(gptr_g[-1], lp[-1], tp_dev, flag)
-            if bad & ~(CAP_BIT | PBC_BIT):
-                _raise_bad_inputs()
-            if bad & PBC_BIT:
-                _raise_bad_cell(cutoff_l, cutoff_g)
-            capped = bool(bad & CAP_BIT)
-        gp, gn, gd = radius_fill(pos, node_graph, g.gptr, cutoff_g, gptr_g, total_g, zeroed=hinted, rows_out=glob_rows,
-                                 max_neighbors=max_nb, cell_tab=tab)
-        if capped and flow != 'target_to_source':     # (stored by neighbour: see the bonded branch below)
-            gp, gn, gd, glob_inv = _transpose_edges(gp, gn, gd, n, want_inverse=need_grad, q=glob_rows.pop())
-        loc_rows = []
-        lp, l_src, l_dist = radius_fill(pos, node_graph, g.gptr, cutoff_l, lp, total_l, zeroed=hinted, rows_out=loc_rows,
-                                        cell_tab=tab)
-        l_dst = loc_rows[0]
-        loc_radius = True
-    elif dataset == 'QM9':
-        pos = pos.to(torch.float32).contiguous()
-        # One host round trip for all three data-dependent sizes: the bond graph's CSR and its triplet / pair counts do
-        # not depend on the radius graph, so they are computed first, on the assumption that the bond list has no self
-        # loops (remove_self_loops, models.py:63, is a no-op for QM9 bond graphs); the flag that verifies it comes back
-        # with the sizes, and a batch that does have self loops is redone the slow way.
-        def bonds(ei, raw=None):
-            # j, i = edge_index (models.py:64)
-            src0, dst0 = raw if raw is not None else (ei[0].to(I32).contiguous(), ei[1].to(I32).contiguous())
-            bonds.raw = (src0, dst0)
-            lp_, perm = csr_from_keys(dst0, n)
-            m = int(src0.numel())
-            src_, dst_, bonds.dist = _i32(m, dev), _i32(m, dev), _f32(m, dev)
-            lib.call('pamnet_gather2_i32', lib.ptr(perm), lib.ptr(src0), lib.ptr(dst0), m, lib.ptr(src_), lib.ptr(dst_),
-                     lib.ptr(pos), lib.ptr(bonds.dist), lib.stream_of(src0))      # + the bond lengths (models.py:65)
-            tp_, bonds.tcount = _triplet_ptr(lp_, src_, dst_, with_triplets)
-            return lp_, src_, dst_, tp_
-
-        ei = edge_index
-        if (sizes is None and ing is not None and MOL_LOCAL and mol_local is not False and ei.size(1) > 0
-                and not 0 < max_nb <= MOL_ATOMS          # (a molecule of <= MOL_ATOMS atoms cannot reach a larger cap)
-                and (mol_local is True or n <= MOL_ATOMS * g.n_graphs // 2)):
-            done = _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad)
-            if done:
-                return _with_seg_cuts(g, dataset) if aux_tables else g
-        lp, l_src, l_dst, tp_ptr = bonds(ei, None if ing is None else (ing[3], ing[4]))
-        if ing is not None:                       # validity and self loops were noted by the ingest launch
-            flag, kept = ing[5], ing[6]           # (`kept`: non-zero = NOT all kept; read through _kept below)
-            g.loops = kept
-        else:
-            types = x_raw.to(torch.float32).reshape(-1)
-            flag = _input_flag(node_graph, g.n_graphs, types, n_types, *bonds.raw)
-            kept = (ei[0] != ei[1]).all()
-        gptr_g = radius_count(pos, node_graph, g.gptr, cutoff_g, max_nb, flag)  # symmetric (unless the cap binds): agg = query
-        if sizes is not None:                     # zero host round trips: sizes from the host, verified on the device
-            total_g, tp_total = int(sizes[0]), int(sizes[2])
-            checks += [(gptr_g[-1:], total_g), (lp[-1:], int(sizes[1])), (tp_ptr[-1:], tp_total)]
-            g.check = flag
-            if ing is None:
-                g.all_kept = kept
-            hinted = _ZeroArena(3 * total_g + 5 * tp_total + 64, dev)
-            # the CSR pointers are capped at what the buffers hold: with sizes that turn out too small every kernel that
-            # walks a pointer still stays inside its arrays (results of such a batch are invalid and flagged)
-            gptr_g = torch.clamp(gptr_g, max=total_g)
-            tp_ptr = torch.clamp(tp_ptr, max=tp_total)
-        else:
-            total_g, k, tp_total, bad = host_ints(gptr_g[-1], kept, tp_ptr[-1], flag)
-            if bad & ~CAP_BIT:
-                _raise_bad_inputs()
-            capped = bool(bad & CAP_BIT)
-            if (k != 0) if ing is not None else (not k):                        # the bond list has self loops
-                lp, l_src, l_dst, tp_ptr = bonds(ei[:, ei[0] != ei[1]])
-                tp_total = int(tp_ptr[-1])
-        gp, gn, gd = radius_fill(pos, node_graph, g.gptr, cutoff_g, gptr_g, total_g, zeroed=hinted, rows_out=glob_rows,
-                                 max_neighbors=max_nb)
-        if capped and flow != 'target_to_source':
-            # edge_index_g = (query, neighbour) and the layer aggregates at edge_index[1] = the NEIGHBOUR
-            # (global_message_passing.py:38 with flow = source_to_target): a symmetric list can be read either way, a
-            # capped one has to be stored by neighbour
-            gp, gn, gd, glob_inv = _transpose_edges(gp, gn, gd, n, want_inverse=need_grad, q=glob_rows.pop())
-        l_dist = bonds.dist
-        tp_pre = (tp_ptr, tp_total)
-    elif dataset == 'PDBbind':
-        xr = x_raw.unsqueeze(-1) if x_raw.dim() == 1 else x_raw
-        pos = xr[:, :3].to(torch.float32).contiguous()
-        g.sign = torch.where(pos[:, 0] > 40.0, -torch.ones_like(pos[:, 0]), torch.ones_like(pos[:, 0])).contiguous()
-        # ONE host round trip for all three data-dependent sizes.  The local graph (global edges with dist <= cutoff_l,
-        # models.py:131-134) is the radius graph at cutoff_l, so its per-node degrees come from a second count pass over
-        # the positions instead of from the filled global graph; and because a radius graph is symmetric, the number of
-        # triplet / pair rows follows from the degrees alone: every edge (j -> i) has deg(j) - 1 triplets (edges k -> j,
-        # k != i) and deg(i) pairs (edges j' -> i, itself included; models.py:68-98).
-        pflag = ing[5] if ing is not None else _input_flag(node_graph, g.n_graphs)
-        gptr_g = radius_count(pos, node_graph, g.gptr, cutoff_g, max_nb, pflag)
-        local = cutoff_l <= cutoff_g
-        if local and sizes is not None:           # zero host round trips (see `sizes`)
-            lp = radius_count(pos, node_graph, g.gptr, cutoff_l)
-            total_g, total_l, tp_hint = (int(v) for v in sizes)
-            g.check = pflag
-            checks += [(gptr_g[-1:], total_g), (lp[-1:], total_l)]
-            hinted = _ZeroArena(3 * total_g + 3 * total_l + 5 * tp_hint + 64, dev)
-            gptr_g, lp = torch.clamp(gptr_g, max=total_g), torch.clamp(lp, max=total_l)
-            gp, gn, gd = radius_fill(pos, node_graph, g.gptr, cutoff_g, gptr_g, total_g, zeroed=hinted, rows_out=glob_rows)
-            lp, l_src, l_dist = _filter_fill(gp, gn, gd, cutoff_l, lp, total_l, zeroed=hinted)
-        elif local:
-            lp = radius_count(pos, node_graph, g.gptr, cutoff_l)
-            deg = (lp[1:] - lp[:-1]).long()
-            tp_dev = (deg * deg + (deg * (deg - 1) if with_triplets else 0)).sum()
-            total_g, total_l, tp_total, bad = host_ints(gptr_g[-1], lp[-1], tp_dev, pflag)
-            if bad & ~CAP_BIT:
-                _raise_bad_inputs()
-            capped = bool(bad & CAP_BIT)
-            gp, gn, gd = radius_fill(pos, node_graph, g.gptr, cutoff_g, gptr_g, total_g, rows_out=glob_rows,
-                                     max_neighbors=max_nb)
-            if capped:                            # the local graph is a cut of the CAPPED global one (models.py:131-134): its
-                lp, l_src, l_dist = csr_filter(gp, gn, gd, cutoff_l)      # degrees are not the plain radius degrees any more
-                tp_hint = None
-                cap_rows = glob_rows.pop()
-            else:
-                lp, l_src, l_dist = _filter_fill(gp, gn, gd, cutoff_l, lp, total_l)
-                tp_hint = tp_total
-        else:                                     # (a local cutoff above the global one: the general, dependent order)
-            total_g, bad = host_ints(gptr_g[-1], pflag)
-            if bad & ~CAP_BIT:
-                _raise_bad_inputs()
-            capped = bool(bad & CAP_BIT)
-            gp, gn, gd = radius_fill(pos, node_graph, g.gptr, cutoff_g, gptr_g, total_g, max_neighbors=max_nb)
-            lp, l_src, l_dist = csr_filter(gp, gn, gd, cutoff_l)
-            tp_hint = None
-            cap_rows = None
-        if capped:
-            # (query, neighbour) lists, as the RNA branch below: the local layer aggregates at the neighbour
-            # (local_message_passing.py:39,54), the global one too unless flow = target_to_source
-            lp, l_src, l_dist, loc_inv = _transpose_edges(lp, l_src, l_dist, n, want_inverse=need_grad)
-            if flow != 'target_to_source':
-                gp, gn, gd, glob_inv = _transpose_edges(gp, gn, gd, n, want_inverse=need_grad, q=cap_rows)
-        l_dst = expand_rows(lp, l_src.numel(), zeroed=hinted)
-    elif rna:
-        xr = x_raw.unsqueeze(-1) if x_raw.dim() == 1 else x_raw
-        pos = xr[:, :3].to(torch.float32).contiguous()
-        # models.py:147-150 (global) and 153-156 (local: j = query, i = nbr)
-        flag = ing[5] if ing is not None else _input_flag(node_graph, g.n_graphs, xr[:, -1].to(torch.float32), n_types)
-        gq = qq = None                            # query ids of the entries, when the launch that wrote the lists gave them
-        if sizes is not None:                     # zero host round trips (see `sizes`)
-            kp, kn, kd = knn_table(pos, node_graph, g.gptr, knn_k, float('inf'))   # (query, neighbour) rows, self dropped
-            total_g, total_l, tp_hint = (int(v) for v in sizes)
-            pa, pb = _filter_count(kp, kn, kd, cutoff_g), _filter_count(kp, kn, kd, cutoff_l)
-            g.check = flag
-            checks += [(pa[-1:], total_g), (pb[-1:], total_l)]
-            hinted = _ZeroArena(4 * total_g + 4 * total_l + 5 * tp_hint + 64, dev)
-            pa, pb = torch.clamp(pa, max=total_g), torch.clamp(pb, max=total_l)
-            gp, gn, gd = _filter_fill(kp, kn, kd, cutoff_g, pa, total_g, zeroed=hinted)
-            qp, qn, qd = _filter_fill(kp, kn, kd, cutoff_l, pb, total_l, zeroed=hinted)
-        elif n > 0 and knn_k <= 64:               # one search, both cuts, one host round trip
-            # ... and the triplet / pair total of the local cut with them: the second read-back (of the scanned row counts) goes
-            if KNN_TP_TOTAL:
-                (gp, gn, gd, gq), (qp, qn, qd, qq), tp_hint = knn_cuts(pos, node_graph, g.gptr, knn_k, cutoff_g, cutoff_l, flag,
-                                                                        tp_of_b=bool(with_triplets))
-            else:
-                (gp, gn, gd, gq), (qp, qn, qd, qq) = knn_cuts(pos, node_graph, g.gptr, knn_k, cutoff_g, cutoff_l, flag)
-        else:
-            kp, kn, kd = knn_table(pos, node_graph, g.gptr, knn_k, float('inf'))
-            (gp, gn, gd), (qp, qn, qd) = csr_filter2(kp, kn, kd, cutoff_g, cutoff_l, flag)
-        if flow != 'target_to_source':                                          # aggregate at edge_index[1] = neighbour
-            gp, gn, gd, glob_inv = _transpose_edges(gp, gn, gd, n, zeroed=hinted, want_inverse=need_grad, q=gq)
-            gq = None
-        elif gq is not None:
-            glob_rows.append(gq)                  # rows = queries: the expanded row ids are the query ids
-        lp, l_src, l_dist, loc_inv = _transpose_edges(qp, qn, qd, n, zeroed=hinted, want_inverse=need_grad, q=qq)
-        # (the local layer always aggregates at i)
-        l_dst = expand_rows(lp, l_src.numel(), zeroed=hinted)
-    else:
+        g.node_graph, g.types = batch.to(I32).contiguous(), None
+        g.gptr, _ = csr_from_keys(g.node_graph, g.n_graphs)
+    lists = _rna if rna else {'QM9': _qm9_bond_free if edge_index is None else _qm9_bonded, 'PDBbind': _pdbbind}.get(dataset)
+    if lists is None:
         raise ValueError("Invalid dataset. If you are using any dataset related to RNA 3D structure prediction, "
                          "be sure to use 'rna' as the first 3 characters of the dataset name.")
-
-    g.pos = pos
-    g.glob = CSR(gp, glob_rows[0] if glob_rows else expand_rows(gp, gn.numel(), zeroed=hinted), gn)
-    g.dist_g = gd
-    g.loc = CSR(lp, l_dst, l_src)
-    g.dist_l = l_dist
-
-    # triplets / pairs + angles (models.py:68-98, 165-177); combined rows grouped by target edge
-    e_l = g.loc.m
-    st = lib.stream_of(pos)
-    wt = 1 if with_triplets else 0
-    if tp_pre is None:
-        tp_ptr, tcount = _triplet_ptr(lp, l_src, l_dst, with_triplets)
-        tot = tp_hint if tp_hint is not None else int(tp_ptr[-1])
-        if hinted:
-            checks.append((tp_ptr[-1:], tot))
-            tp_ptr = torch.clamp(tp_ptr, max=tot)
-    else:
-        tp_ptr, tot = tp_pre
-        tcount = bonds.tcount
-    tp_idx, tp_edge, tp_kind = (_alloc_i32(tot, dev, hinted) for _ in range(3))
-    tp_angle = _alloc_f32(tot, dev, hinted)
-    if g.cell_tab is not None:
-        lib.call('pamnet_triplet_fill_pbc_f32', lib.ptr(pos), lib.ptr(g.cell_tab), lib.ptr(node_graph), lib.ptr(lp),
-                 lib.ptr(l_src), lib.ptr(l_dst), e_l, wt, lib.ptr(tp_ptr), lib.ptr(tp_idx), lib.ptr(tp_edge), lib.ptr(tp_angle),
-                 lib.ptr(tp_kind), tot, st)
-    else:
-        lib.call('pamnet_triplet_fill_f32', lib.ptr(pos), lib.ptr(lp), lib.ptr(l_src), lib.ptr(l_dst), e_l, wt,
-                 lib.ptr(tp_ptr), lib.ptr(tp_idx), lib.ptr(tp_edge), lib.ptr(tp_angle), lib.ptr(tp_kind), tot, st)
-    if checks:                                    # one launch: size mismatches join the validity flag (PAMNet.verify)
-        _check_sizes(g.check, checks, getattr(g, 'all_kept', None), getattr(g, 'loops', None))
-    g.tp = CSR(tp_ptr, tp_edge, tp_idx)               # rows = target edge e, col = source edge e'
-    g.tp_angle, g.tp_kind = tp_angle, tp_kind
-
-    g.capped = capped
-    g.glob_T = g.loc_T = g.tp_T = _NoTranspose    # forward-only: backward index structures are not built
-    if need_grad:
-        # symmetric by construction (the kNN graphs of the RNA path are not, nor is a radius graph the neighbour cap cut)
-        radius_g = dataset in ('QM9', 'PDBbind') and not capped
-        # d x[j] of the global gather: the reverse-edge index of a radius graph; for the RNA kNN cut the inverse of the
-        # transposition that stored it by neighbour; a counting sort otherwise
-        g.glob_T = SymmetricTranspose(g.glob) if radius_g else (glob_inv if glob_inv is not None
-                                                               else Transpose(g.glob.col, n))
-        # d x[j] of the local gather: a radius graph for PDBbind and bond-free QM9, the inverse transposition for RNA;
-        # user-supplied bonds (QM9) take the counting sort
-        g.loc_T = SymmetricTranspose(g.loc) if ((dataset == 'PDBbind' and not capped) or loc_radius) else (
-            loc_inv if loc_inv is not None else Transpose(g.loc.col, n))
-        # d m_neighbor[e'] of the triplet/pair gather
-        g.tp_T = (TripletTranspose(g.loc, g.loc_T, tp_ptr, tcount, tot, with_triplets, zeroed=hinted) if (e_l > 0 and tot > 0)
-                  else Transpose(tp_idx, max(e_l, 1)))
+    a = _Args(cutoff_l, cutoff_g, flow, x_raw, pos, edge_index, need_grad, knn_k, with_triplets, n_types, sizes, mol_local,
+              max_nb, cell)
+    r = lists(g, ing, a)
+    if r is not None:                             # (None: the molecule-local builder has made everything)
+        _finish(g, r, dataset, a)
     return _with_seg_cuts(g, dataset) if aux_tables else g
 
 
@@ -1145,8 +1199,9 @@ def _index_lists(g):
     """The index tensors of `g` that pamnet_pos_bwd_f32 reads, with the sizes.  The geometry Functions keep these on ctx, not
     the graph: the graph object is where their outputs end up, and ctx -> graph -> output -> node would be a cycle."""
     glob, loc, tp = g.glob, g.loc, g.tp
-    return (g.n, glob.ptr, glob.row_of, glob.col, g.glob_T.ptr, g.glob_T.perm, glob.m, loc.ptr, loc.row_of, loc.col,
-            g.loc_T.ptr, g.loc_T.perm, loc.m, tp.ptr, tp.row_of, tp.col, g.tp_kind, g.tp_T.ptr, g.tp_T.perm, tp.m)
+    return (g.n, (glob.ptr, glob.row_of, glob.col, g.glob_T.ptr, g.glob_T.perm), glob.m,
+            (loc.ptr, loc.row_of, loc.col, g.loc_T.ptr, g.loc_T.perm), loc.m,
+            (tp.ptr, tp.row_of, tp.col, g.tp_kind, g.tp_T.ptr, g.tp_T.perm), tp.m)
 
 
 class _Geometry(torch.autograd.Function):
@@ -1167,24 +1222,14 @@ class _Geometry(torch.autograd.Function):
         if torch.is_grad_enabled():
             raise RuntimeError(_SECOND_ORDER)
         pos, = ctx.saved_tensors
-        (n, g_ptr, g_row, g_col, gt_ptr, gt_perm, eg, l_ptr, l_row, l_col, lt_ptr, lt_perm, el, t_ptr, t_row, t_col, t_kind,
-         tt_ptr, tt_perm, tp) = ctx.idx
+        n, glob, eg, loc, el, trip, tp = ctx.idx      # (each list: ptr, row, col, [kind,] transposed ptr, perm)
         pos = pos.contiguous()
         d_dg, d_dl, d_ang = d_dg.contiguous(), d_dl.contiguous(), d_ang.contiguous()
         work = torch.empty(3 * max(el, 1), dtype=torch.float64, device=pos.device)
         dpos = torch.empty((n, 3), dtype=torch.float32, device=pos.device)
-        if ctx.pbc is not None:
-            tab, node_graph = ctx.pbc
-            lib.call('pamnet_pos_bwd_pbc_f32', lib.ptr(pos), lib.ptr(tab), lib.ptr(node_graph), n, lib.ptr(g_ptr), lib.ptr(g_row),
-                     lib.ptr(g_col), lib.ptr(gt_ptr), lib.ptr(gt_perm), lib.ptr(d_dg), eg, lib.ptr(l_ptr), lib.ptr(l_row),
-                     lib.ptr(l_col), lib.ptr(lt_ptr), lib.ptr(lt_perm), lib.ptr(d_dl), el, lib.ptr(t_ptr), lib.ptr(t_row),
-                     lib.ptr(t_col), lib.ptr(t_kind), lib.ptr(tt_ptr), lib.ptr(tt_perm), lib.ptr(d_ang), tp, lib.ptr(work),
-                     lib.ptr(dpos), lib.stream_of(pos))
-            return dpos, None
-        lib.call('pamnet_pos_bwd_f32', lib.ptr(pos), n, lib.ptr(g_ptr), lib.ptr(g_row), lib.ptr(g_col), lib.ptr(gt_ptr),
-                 lib.ptr(gt_perm), lib.ptr(d_dg), eg, lib.ptr(l_ptr), lib.ptr(l_row), lib.ptr(l_col), lib.ptr(lt_ptr),
-                 lib.ptr(lt_perm), lib.ptr(d_dl), el, lib.ptr(t_ptr), lib.ptr(t_row), lib.ptr(t_col), lib.ptr(t_kind),
-                 lib.ptr(tt_ptr), lib.ptr(tt_perm), lib.ptr(d_ang), tp, lib.ptr(work), lib.ptr(dpos), lib.stream_of(pos))
+        P = lib.ptr
+        _call_in_cell('pamnet_pos_bwd_f32', 'pamnet_pos_bwd_pbc_f32', pos, ctx.pbc, n, *map(P, glob), P(d_dg), eg, *map(P, loc),
+                      P(d_dl), el, *map(P, trip), P(d_ang), tp, P(work), P(dpos), lib.stream_of(pos))
         return dpos, None
 
 
