@@ -167,13 +167,36 @@ class _FlatView(object):
         self.param = nn.Parameter(self.fp.flat)           # shares the buffer's storage
         self.param.grad = self.fp.grad
         self._pending = None
+        self.epoch = model.__dict__.get('_param_epoch')   # (FlatParams has just walked the tree: the cache is current)
 
-    def valid(self):
-        """Every parameter is still a view of the buffer (model.to(...) / .cpu() re-allocate them: rebuilt on next use)."""
+    def valid(self, model):
+        """The model still holds exactly the parameters that were re-homed, each still a view of the buffer (model.to(...) /
+        .cpu() re-allocate them, a replaced module or Parameter brings tensors of its own: rebuilt on next use).  The full
+        comparison runs only when the model has dropped its cached parameter walk since the last look."""
         fp = self.fp
+        ep = model.__dict__.get('_param_epoch')
+        if ep != self.epoch:
+            if fp.mismatch(model) is not None:
+                return False
+            self.epoch = ep
         first, last = fp.params[0], fp.params[-1]
         return (first.is_cuda and first.data_ptr() == fp.flat.data_ptr() + 4 * fp.offsets[fp.names[0]]
                 and last.data_ptr() == fp.flat.data_ptr() + 4 * fp.offsets[fp.names[-1]])
+
+    def sync(self):
+        """The ONE parameter must alias the buffer the kernels read.  `param.data = t` (an EMA that swaps its shadow in and
+        the saved weights back by assignment rather than by copy) re-points it at another storage: `t` is what the caller
+        wants the weights to be, so it is copied into the buffer and the parameter is pointed back at the buffer -- the next
+        optimizer.step() then updates what the kernels read.  Called on a view valid() has accepted."""
+        p, flat = self.param, self.fp.flat
+        if p.data_ptr() == flat.data_ptr() and p.device == flat.device:
+            return
+        src = p.data
+        if src.numel() != flat.numel() or src.dtype != flat.dtype:
+            raise RuntimeError('PAMNET_FLAT_PARAMS=1: the data assigned to the flat parameter (%d x %s) does not have the '
+                               'layout of the flat buffer (%d x %s)' % (src.numel(), src.dtype, flat.numel(), flat.dtype))
+        flat.copy_(src.reshape(-1))
+        p.data = flat
 
     def before_forward(self):
         """The kernels OVERWRITE their gradients and a backward starts from a zeroed buffer.  optimizer.zero_grad() (torch
@@ -318,6 +341,11 @@ class _PAMNetBase(nn.Module):
         return all(o._parameters.get(leaf) is p for (o, leaf), (_, p) in zip(owners, cache))
 
     def _drop_param_cache(self):
+        """Forget everything derived from a walk of the module tree: the cached walk, its derived lists and the layer-stack
+        engine's plan (stack.StackPlan lists the Parameter objects of both stacks).  `_param_epoch` counts the drops: holders
+        of the parameters outside the model (train.Trainer, the flat view) compare it to know when to look again."""
+        self.__dict__['_param_epoch'] = self.__dict__.get('_param_epoch', 0) + 1
+        stack.drop_plan(self.__dict__.get('_modules', {}).get('global_layer'))
         self.__dict__.pop('_named_param_cache', None)
         self.__dict__.pop('_named_param_owners', None)
         self.__dict__.pop('_named_param_links', None)
@@ -358,7 +386,8 @@ class _PAMNetBase(nn.Module):
         if os.environ.get('PAMNET_FLAT_PARAMS', '0') != '1' or self.__dict__.get('_flat_view_off'):
             return None
         st = self.__dict__.get('_flat_view_state')
-        if st is not None and st.valid():
+        if st is not None and st.valid(self):
+            st.sync()
             return st
         self.__dict__.pop('_flat_view_state', None)
         real = [p for _, p in self._real_named_parameters()]
@@ -369,6 +398,19 @@ class _PAMNetBase(nn.Module):
         st = self.__dict__['_flat_view_state'] = _FlatView(self)
         return st
 
+    def _sync_flat_view(self):
+        st = self.__dict__.get('_flat_view_state')
+        if st is not None and st.valid(self):             # (a view that is no longer valid is rebuilt on next use instead)
+            st.sync()
+
+    def state_dict(self, *args, **kwargs):
+        self._sync_flat_view()                            # (data assigned to the flat parameter is what the model holds)
+        return super().state_dict(*args, **kwargs)
+
+    def load_state_dict(self, *args, **kwargs):
+        self._sync_flat_view()
+        return super().load_state_dict(*args, **kwargs)
+
     def _disable_flat_view(self):
         """pamnet_amd.train.Trainer re-homes the parameters in flat buffers of its own."""
         self.__dict__['_flat_view_off'] = True
@@ -377,7 +419,7 @@ class _PAMNetBase(nn.Module):
     def _run_one_node(self, run):
         """The forward as ONE autograd node (ops.run_whole) on the flat-view parameter when there is one."""
         st = self.__dict__.get('_flat_view_state')
-        if st is None or not st.valid():
+        if st is None or not st.valid(self):
             return ops.run_whole(self.rbf_g.freq, run)
         return ops.run_whole(st.param, run, before=st.before_forward, after=st.after_backward)
 
@@ -611,7 +653,8 @@ class _PAMNetBase(nn.Module):
 
     def _run_layers(self, x, e_l, e_g, e_sbf, g, tape=None):
         if stack.engine_supported(x, g):           # dim 128 / 16 / 32 / 64 on an MI355X: the whole loop is one engine call
-            outs, atts, saved = stack.layer_stack(self.global_layer, self.local_layer, x, e_g, e_l, e_sbf, g, tape=tape)
+            outs, atts, saved = stack.layer_stack(self.global_layer, self.local_layer, x, e_g, e_l, e_sbf, g, tape=tape,
+                                                  checked=bool(self.__dict__.get('_params_checked')))
             self._x_layers = _LazyLayers(saved, g, self.n_layer, x.size(1))
             return outs, atts
         outs, atts = [], []
@@ -674,12 +717,17 @@ class _PAMNetBase(nn.Module):
         params = self._top_params() if self.dim == fused.D else self._all_params()
         if not all(getattr(p, '_pamnet_direct', False) and p.grad is not None for p in params):
             return False
-        return stack.stack_plan(self.global_layer, self.local_layer).direct()
+        return stack.stack_plan(self.global_layer, self.local_layer, bool(self.__dict__.get('_params_checked'))).direct()
 
     def _checked_forward(self, data):
-        """The dtype check just walked the cache against the live tree (~0.05 ms of host time); nothing re-hangs parameters
-        during a forward, so the other users of the cached lists inside it (the one-node test, the engine plan) take that
-        result instead of repeating the walk -- three walks per training step were 5 % of the host-bound RNA step."""
+        """The dtype check just walked the cache against the live tree (_param_cache_valid) and, where the tree had
+        changed, dropped the cache together with the engine plan (_drop_param_cache); nothing re-hangs parameters during a
+        forward, so the users of the cached lists inside it (the one-node test) take that result instead of repeating the
+        walk, and the engine takes its plan without walking the two stacks (stack.stack_plan(checked=True)) -- three walks
+        per training step were 5 % of the host-bound RNA step.  What the check cannot see -- a tensor moved under an
+        unchanged Parameter object (`p.data = t`) -- is the plan's own business: its pointer tables are keyed by every
+        address."""
+        self._sync_flat_view()
         self.__dict__['_params_checked'] = True
         try:
             return self._on_own_device(self._forward, data)

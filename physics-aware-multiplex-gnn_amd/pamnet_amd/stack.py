@@ -78,10 +78,19 @@ def _graph_tables(graph):
     return sizes, idx
 
 
+_data_ptr = torch.Tensor.data_ptr
+_grad_of = torch.Tensor.grad.__get__
+
+
 class StackPlan(object):
-    """Parameter tables of a layer stack, built once per model: walking the nn.Module tree (~400 attribute / Sequential
-    lookups) and re-creating the pointer arrays cost ~0.5 ms of host time per step, comparable to enqueueing the kernels.
-    The pointer arrays are rebuilt only when a parameter (or, in direct-gradient mode, a .grad) has moved."""
+    """Parameter tables of a layer stack: walking the nn.Module tree (~400 attribute / Sequential lookups) costs ~0.5 ms of
+    host time per step, comparable to enqueueing the kernels, so the Parameter OBJECTS are listed once and the list is kept
+    for as long as the module tree holds exactly these objects (stack_plan).  What an object points at may change under the
+    list (`p.data = t`, `model.to(...)`, a .grad set to None or replaced): the pointer arrays are keyed by the address of
+    EVERY tensor they hold -- data_ptr() of each, once per engine call -- and rebuilt when any of them has moved (host cost
+    against the three-tensor key this replaces: profiles/live_params_ab.txt).  `table_calls` counts param_tables() calls:
+    a holder of the parameters (train.Trainer) tells from it whether a forward went through the engine and so refreshed
+    `_pkey`."""
 
     def __init__(self, global_layers, local_layers):
         self.gl = [global_params(l) for l in global_layers]
@@ -91,8 +100,9 @@ class StackPlan(object):
         self.gflat = [p for lay in self.gl for p in lay]
         self.lflat = [p for lay in self.ll for p in lay]
         self.flat = self.gflat + self.lflat
-        self._probe = [self.flat[0], self.flat[len(self.flat) // 2], self.flat[-1]]
+        self._flag_probe = [self.flat[0], self.flat[len(self.flat) // 2], self.flat[-1]]
         self._pkey = self._gkey = None
+        self.table_calls = 0
         self._shape_groups = None           # {(shape, dtype, device): [indices into self.flat]} for grouped gradient allocation
         self._pack = self._temp = None
         self.ctx = stack_ctx(global_layers)
@@ -114,26 +124,41 @@ class StackPlan(object):
             self._pack = torch.empty(int(need.value), dtype=torch.float32, device=dev)
         return self._pack
 
+    def matches(self, global_layers, local_layers):
+        """True when the two stacks hold, slot by slot, exactly the Parameter objects listed here (a full walk)."""
+        if len(global_layers) != self.L or len(local_layers) != len(self.ll):
+            return False
+        try:
+            live = [p for l in global_layers for p in global_params(l)] + [p for l in local_layers for p in local_params(l)]
+        except (AttributeError, IndexError, TypeError):     # a layer of another kind was hung in
+            return False
+        return len(live) == len(self.flat) and all(a is b for a, b in zip(live, self.flat))
+
     def param_tables(self):
-        key = tuple(p.data_ptr() for p in self._probe)
+        self.table_calls += 1
+        key = tuple(map(_data_ptr, self.flat))
         if key != self._pkey:
-            self._gtab, self._ltab, self._pkey = _parr(self.gflat), _parr(self.lflat), key
+            ng = len(self.gflat)
+            self._gtab, self._ltab = _parr(key[:ng]), _parr(key[ng:])
+            self._pkey = key
         return self._gtab, self._ltab
 
     def direct(self):
         """True when every parameter owns a preallocated contiguous .grad handed out by train.FlatParams (which zeroes
-        it every step: direct writes overwrite, they do not accumulate) with direct writes allowed."""
-        if not all(getattr(p, '_pamnet_direct', False) for p in self._probe):
+        it every step: direct writes overwrite, they do not accumulate) with direct writes allowed.  The gradient tables
+        are keyed by the address of every .grad: one that was dropped or replaced since they were built is seen."""
+        # (FlatParams.set_direct flips the permission of all parameters at once: three of them tell)
+        if not all(getattr(p, '_pamnet_direct', False) for p in self._flag_probe):
             return False
-        grads = [p.grad for p in self._probe]
-        if any(g is None for g in grads):
+        try:
+            key = tuple(map(_data_ptr, map(_grad_of, self.flat)))
+        except TypeError:                                   # a .grad is None
             return False
-        key = tuple(g.data_ptr() for g in grads)
         if key != self._gkey:
-            if not all(getattr(p, '_pamnet_direct', False) and getattr(p, 'grad', None) is not None
-                       and p.grad.is_contiguous() for p in self.flat):
+            if not all(getattr(p, '_pamnet_direct', False) and p.grad.is_contiguous() for p in self.flat):
                 return False
-            self._ggrad, self._lgrad = _parr([p.grad for p in self.gflat]), _parr([p.grad for p in self.lflat])
+            ng = len(self.gflat)
+            self._ggrad, self._lgrad = _parr(key[:ng]), _parr(key[ng:])
             self._gkey = key
         return True
 
@@ -161,6 +186,7 @@ class _Stack(torch.autograd.Function):
                  1 if save else 0, lib.ptr(plan.pack_arena(x0.device)), aux, evs, lib.stream_of(x0))
         ctx.save_for_backward(x0, e_g, rbf_e, e_sbf, saved)
         ctx.graph, ctx.plan, ctx.direct, ctx.temp_floats = graph, plan, direct, int(need[1])
+        ctx.pkey, ctx.gkey = plan._pkey, plan._gkey if direct else None
         ctx.mark_non_differentiable(saved)
         ctx.set_materialize_grads(False)       # else autograd zero-fills a gradient the size of `saved` every step
         return outs, atts, saved
@@ -174,6 +200,14 @@ class _Stack(torch.autograd.Function):
         temp = plan.temp_arena(ctx.temp_floats, x0.device)
         d_x0, d_eg, d_rbf, d_sbf = (torch.empty_like(t) for t in (x0, e_g, rbf_e, e_sbf))
         gtab, ltab = plan.param_tables()
+        # The saved activations belong to the weights the forward read, and in direct mode the gradients go where the
+        # forward's table says: a tensor re-pointed (`p.data = t`, a device move) or a .grad replaced between a forward
+        # and its backward would mix the two silently -- refused before anything is launched.  (Keys are rebuilt only
+        # when an address changed: identity is enough.)
+        if plan._pkey is not ctx.pkey or (direct and plan._gkey is not ctx.gkey):
+            raise RuntimeError('PAMNet layer stack: a parameter tensor (or, with direct gradient writes, a .grad) was '
+                               're-pointed or moved between this forward and its backward; the backward cannot '
+                               'differentiate the forward that ran. Run the forward again after the edit.')
         evs = None
         if direct:
             ggrad, lgrad, g = plan._ggrad, plan._lgrad, ()
@@ -198,12 +232,26 @@ class _Stack(torch.autograd.Function):
         return (d_x0, d_eg, d_rbf, d_sbf, None, None, None, None) + tuple(g)
 
 
-def stack_plan(global_layers, local_layers):
+def stack_plan(global_layers, local_layers, checked=False):
+    """The StackPlan of a model's layer stack (stored on the global_layer ModuleList).  It lists Parameter objects, so it
+    holds only while the two stacks hold exactly those objects: a replaced head module, a Parameter assigned over another,
+    `load_state_dict(..., assign=True)` or a replaced layer make it stale.  `checked=True`: the caller vouches for that --
+    models.PAMNet validates its cached parameter walk against the live module tree once per forward and drops the plan
+    together with the walk (drop_plan), so the engine call inside that forward repeats nothing.  Every other caller
+    pays the walk here."""
     plan = getattr(global_layers, '_pamnet_plan', None)
+    if plan is not None and not checked and not plan.matches(global_layers, local_layers):
+        plan = None
     if plan is None or plan.L != len(global_layers):
         plan = StackPlan(global_layers, local_layers)
         global_layers._pamnet_plan = plan
     return plan
+
+
+def drop_plan(global_layers):
+    """Forget the plan of a layer stack whose owner has seen (or made) a change to the module tree."""
+    if global_layers is not None:
+        global_layers.__dict__.pop('_pamnet_plan', None)
 
 
 def engine_supported(x, graph):
@@ -211,9 +259,9 @@ def engine_supported(x, graph):
     return (x.is_cuda and x.size(-1) == D) or narrow.engine_supported(x, graph)
 
 
-def layer_stack(global_layers, local_layers, x0, e_g, rbf_e, e_sbf, graph, tape=None):
-    """Returns outs [2L,N], atts [2L,N] and the saved-activation arena (see stack_x_layers)."""
-    plan = stack_plan(global_layers, local_layers)
+def layer_stack(global_layers, local_layers, x0, e_g, rbf_e, e_sbf, graph, tape=None, checked=False):
+    """Returns outs [2L,N], atts [2L,N] and the saved-activation arena (see stack_x_layers).  `checked`: see stack_plan."""
+    plan = stack_plan(global_layers, local_layers, checked)
     # inference (no gradient mode): the engine skips every store only the backward would read
     save = torch.is_grad_enabled()
     if tape is not None:                       # direct-gradient mode on the model's own tape (ops.Tape)

@@ -82,6 +82,30 @@ class FlatParams(object):
     def zero_grad(self):
         self.grad.zero_()
 
+    def mismatch(self, module):
+        """None while `module` holds exactly the parameters re-homed here, each still the view of the flat buffer it was
+        given; else a sentence naming the first parameter (in the module's own order) for which that no longer holds."""
+        base, es = self.flat.data_ptr(), self.flat.element_size()
+        own = dict(zip(self.names, self.params))
+        seen = 0
+        for n, q in getattr(module, '_real_named_parameters', module.named_parameters)():
+            p = own.get(n)
+            if p is None:
+                if q.requires_grad:
+                    return "parameter '%s' was added to the model after its parameters were moved into the flat buffer" % n
+                continue
+            seen += 1
+            if q is not p:
+                return ("parameter '%s' of the model is no longer the tensor that was moved into the flat buffer (a module "
+                        "or Parameter was assigned over it, or load_state_dict(assign=True) replaced it)" % n)
+            if q.data_ptr() != base + es * self.offsets[n] or q.device != self.flat.device:
+                return ("parameter '%s' no longer views the flat buffer (its .data was re-pointed, or the model was moved "
+                        "or cast)" % n)
+        if seen != len(own):
+            live = set(n for n, _ in getattr(module, '_real_named_parameters', module.named_parameters)())
+            return "parameter '%s' is no longer part of the model" % next(n for n in self.names if n not in live)
+        return None
+
     # Per-operator autograd paths (widths other than 128) would add every parameter's gradient into its view with one
     # small kernel each (~150 launches per step); instead autograd hands the gradient tensors over (p.grad = None
     # before the backward) and one multi-tensor add packs them into the flat buffer.
@@ -297,6 +321,9 @@ class Trainer(object):
         if hasattr(model, '_disable_flat_view'):
             model._disable_flat_view()                     # (this class owns the flat buffers; no second interface on top)
         self.fp = FlatParams(model, direct=True)           # fused layers write gradients straight into fp.grad
+        self._seen_epoch = getattr(model, '__dict__', {}).get('_param_epoch')
+        self._seen_pkey = self._seen_plan = self._loose = None
+        self._before = (None, -1)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         if int(accumulate) != accumulate or int(accumulate) < 1:
             raise ValueError('accumulate must be an integer >= 1 (got %r)' % (accumulate,))
@@ -428,7 +455,19 @@ class Trainer(object):
             self._stack_ctx.recorded = False
         if self._pack:
             self.fp.release_grads()
+        plan = self._stack_plan_of_model()
+        self._before = (plan, -1 if plan is None else plan.table_calls)
         out = self.model(data)
+        try:
+            self._check_ownership()
+        except RuntimeError:
+            # refused before the backward: the recorded forward is dropped with `out`, the flat gradient is still zero
+            # (the next call finds it clean), and gradients released to autograd go back to being views of the buffer
+            del out
+            if self._pack:
+                self.fp.pack_grads()
+            self._grad_clean = True
+            raise
         # local mean -> contribution to the global-batch mean
         split = self.world_size > 1 or self.accumulate > 1             # this call sees a part of what one update averages over
         if split and global_graphs is None:                           # equal parts unless the caller says otherwise
@@ -445,6 +484,37 @@ class Trainer(object):
         if self._pack:
             self.fp.pack_grads()
         return loss
+
+    def _stack_plan_of_model(self):
+        return getattr(getattr(self.model, 'global_layer', None), '__dict__', {}).get('_pamnet_plan')
+
+    def _check_ownership(self):
+        """The update writes the flat buffers: it must be the model's own parameters that view them.  Runs behind the
+        forward, whose one validation of the cached parameter walk against the live module tree it relies on (asking before
+        the forward would repeat that walk every step), and before anything is differentiated or updated.  Per step: the
+        model's count of dropped walks, the identity of the layer-stack plan's pointer key -- re-keyed by the forward's
+        engine call when any tensor under it has moved; refreshed here when that forward did not go through the engine --
+        and the addresses of the few parameters outside the plan.  The full comparison (FlatParams.mismatch) runs only when
+        one of these says so.  A module without those hooks (the CPU / gloo tests' plain modules) is taken as it is."""
+        model = self.model
+        ep = getattr(model, '__dict__', {}).get('_param_epoch')
+        if ep is None:
+            return
+        plan = self._stack_plan_of_model()
+        if plan is not None and (plan is not self._before[0] or plan.table_calls == self._before[1]):
+            plan.param_tables()                                # (this forward did not: per-operator path, no engine)
+        pkey = None if plan is None else plan._pkey
+        if ep == self._seen_epoch and plan is self._seen_plan and pkey is self._seen_pkey and self._loose is not None \
+                and all(p.data_ptr() == a for p, a in self._loose):
+            return
+        msg = self.fp.mismatch(model)
+        if msg is not None:
+            raise RuntimeError('Trainer: %s -- the optimiser would update a buffer the model does not read. Build a new '
+                               'Trainer on the edited model (load_state_dict without assign=True copies in place and needs '
+                               'none).' % msg)
+        inside = set() if plan is None else set(id(p) for p in plan.flat)
+        self._loose = [(p, p.data_ptr()) for p in self.fp.params if id(p) not in inside]
+        self._seen_epoch, self._seen_plan, self._seen_pkey = ep, plan, pkey
 
     # -- gradient all-reduce -------------------------------------------------------------------------------------------
     def _setup_buckets(self, n_buckets):
