@@ -457,6 +457,23 @@ int pamnet_pos_bwd_pbc_f32(const float* pos, const double* cell_table, const int
                            const int32_t* tt_ptr, const int32_t* tt_perm, const float* dangle, int64_t tp, double* bond_work,
                            float* dpos, pamnet_stream_t stream);
 
+/* pamnet_pos_bwd_pbc_f32 that also returns the virial of every graph: dstrain[g][a][b] = sum over the directed global edges
+ * and local bonds of graph g of v_e[a] * (d prediction / d v_e)[b], v_e the minimum-image vector -- the derivative under the
+ * homogeneous deformation pos -> pos (I + eps_g), cell[g] -> cell[g] (I + eps_g) at eps = 0 with the image integers held fixed.
+ * The argument list of pamnet_pos_bwd_pbc_f32, then gptr [n_graphs + 1] (first atom of every graph), n_graphs, atom_work
+ * [n, 9] doubles of scratch and dstrain [n_graphs, 9] fp32.  dpos is bitwise what pamnet_pos_bwd_pbc_f32 writes.  Three
+ * launches (bond gradients, positions + per-atom virial rows, one workgroup per graph adding them in a fixed order), no
+ * atomics; a graph without edges gets exact zeros; n == 0 zero-fills dstrain.  Same return codes (part of ABI 18: nothing
+ * existing changed). */
+int pamnet_pos_bwd_pbc_virial_f32(const float* pos, const double* cell_table, const int32_t* node_graph, int64_t n,
+                                  const int32_t* g_ptr, const int32_t* g_row, const int32_t* g_col, const int32_t* gt_ptr,
+                                  const int32_t* gt_perm, const float* ddist_g, int64_t eg, const int32_t* l_ptr,
+                                  const int32_t* l_row, const int32_t* l_col, const int32_t* lt_ptr, const int32_t* lt_perm,
+                                  const float* ddist_l, int64_t el, const int32_t* t_ptr, const int32_t* t_row,
+                                  const int32_t* t_col, const int32_t* t_kind, const int32_t* tt_ptr, const int32_t* tt_perm,
+                                  const float* dangle, int64_t tp, double* bond_work, float* dpos, const int32_t* gptr,
+                                  int64_t n_graphs, double* atom_work, float* dstrain, pamnet_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Attention fusion + per-graph pooling  (models.py:206-224)
  * outs/atts: [2L, n] rows ordered (global_0, local_0, global_1, local_1, ...).

@@ -7,6 +7,13 @@
 // resp. p_j' - p_i): the forward's own operands (graph.hip triplet_fill_kernel).  So the angle gradients fold into one
 // 3-vector per local edge, and the positions gather those per atom.  No atomics: every sum runs over a CSR row or a
 // transposed row list in a fixed order, so the result is bitwise the same from run to run.  Arithmetic in fp64.
+//
+// Periodic cells also give the virial W[g] = d prediction / d strain at zero strain (pamnet_pos_bwd_pbc_virial_f32): the sum over
+// every directed edge of (minimum-image vector) (x) (gradient with respect to that vector).  Both factors exist only here, in
+// fp64 and per wavefront, so the atom's wavefront of the position backward forms its rows' share beside dpos (the VIRIAL
+// instantiation of pos_grad) and one workgroup per graph adds the atoms' shares in a fixed-order tree (virial_reduce_kernel).
+// pos^T dE/dpos + cell^T dE/dcell is the same number but cancels: its terms grow with every lattice vector an atom is
+// displaced by, the edge form does not see where an atom was wrapped to.
 #include "common.h"
 #include "geom_core.h"
 
@@ -159,24 +166,38 @@ __global__ __launch_bounds__(256) void bond_grad_pbc_kernel(const float* __restr
 
 // One wavefront per atom a, the lanes striding over: the global edges of row a and of column a (transposed list), then the
 // bond gradients of the local edges leaving a (+G) and arriving at a (-G).
-template <class GEOM>
+// VIRIAL: the wavefront also sums v (x) dE/dv over the edges of ROW a alone (each directed edge belongs to one row, so each is
+// counted once): w (x) (ddist_g / r) w of its global edges -- symmetric, six products -- and u_e (x) G_e of its local edges, and
+// writes the nine sums to atom_work[a].  dpos comes from the same statements in the same order either way.
+template <class GEOM, bool VIRIAL>
 __device__ __forceinline__ void pos_grad(GEOM geom, const int32_t* __restrict__ node_graph, const float* __restrict__ pos,
                                          int64_t n, const int32_t* __restrict__ g_ptr, const int32_t* __restrict__ g_row,
                                          const int32_t* __restrict__ g_col, const int32_t* __restrict__ gt_ptr,
                                          const int32_t* __restrict__ gt_perm, const float* __restrict__ ddist_g,
                                          const int32_t* __restrict__ l_ptr, const int32_t* __restrict__ lt_ptr,
                                          const int32_t* __restrict__ lt_perm, const double* __restrict__ G,
-                                         float* __restrict__ dpos) {
+                                         float* __restrict__ dpos, const int32_t* __restrict__ l_col = nullptr,
+                                         double* __restrict__ atom_work = nullptr) {
     const int64_t a = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (a >= n) return;                                           // (uniform over the wavefront)
     geom.bind(node_graph, a);
     const V3 pa = load_pos(pos, a);
     V3 acc = v3(0.0, 0.0, 0.0);
+    V3 vx = v3(0.0, 0.0, 0.0), vy = vx, vz = vx;                  // VIRIAL: rows of the 3 x 3 sum
     for (int q = g_ptr[a] + lane; q < g_ptr[a + 1]; q += 64) {
         const V3 w = geom.from(pa, pos, g_col[q]);
         const double r = sqrt(dot(w, w));
-        if (r > 0.0) acc = acc + ((double)ddist_g[q] / r) * w;
+        if (r > 0.0) {
+            const V3 f = ((double)ddist_g[q] / r) * w;
+            acc = acc + f;
+            if constexpr (VIRIAL) {
+                const double xy = w.x * f.y, xz = w.x * f.z, yz = w.y * f.z;
+                vx = vx + v3(w.x * f.x, xy, xz);
+                vy = vy + v3(xy, w.y * f.y, yz);
+                vz = vz + v3(xz, yz, w.z * f.z);
+            }
+        }
     }
     for (int k = gt_ptr[a] + lane; k < gt_ptr[a + 1]; k += 64) {
         const int64_t q = gt_perm[k];
@@ -188,12 +209,30 @@ __device__ __forceinline__ void pos_grad(GEOM geom, const int32_t* __restrict__ 
         const int64_t e = lt_perm[k];
         acc = acc + v3(G[3 * e], G[3 * e + 1], G[3 * e + 2]);
     }
-    for (int e = l_ptr[a] + lane; e < l_ptr[a + 1]; e += 64) acc = acc - v3(G[3 * e], G[3 * e + 1], G[3 * e + 2]);
+    for (int e = l_ptr[a] + lane; e < l_ptr[a + 1]; e += 64) {
+        const V3 ge = v3(G[3 * e], G[3 * e + 1], G[3 * e + 2]);
+        acc = acc - ge;
+        if constexpr (VIRIAL) {
+            const V3 u = geom.diff(pos, l_col[e], a);             // u_e = p[src] - p[dst], dst = a
+            vx = vx + u.x * ge;
+            vy = vy + u.y * ge;
+            vz = vz + u.z * ge;
+        }
+    }
     acc = wave_sum(acc);
     if (lane == 0) {
         dpos[3 * a] = (float)acc.x;
         dpos[3 * a + 1] = (float)acc.y;
         dpos[3 * a + 2] = (float)acc.z;
+    }
+    if constexpr (VIRIAL) {
+        vx = wave_sum(vx), vy = wave_sum(vy), vz = wave_sum(vz);
+        if (lane == 0) {
+            double* __restrict__ o = atom_work + 9 * a;
+            o[0] = vx.x, o[1] = vx.y, o[2] = vx.z;
+            o[3] = vy.x, o[4] = vy.y, o[5] = vy.z;
+            o[6] = vz.x, o[7] = vz.y, o[8] = vz.z;
+        }
     }
 }
 
@@ -204,7 +243,8 @@ __global__ __launch_bounds__(256) void pos_grad_kernel(const float* __restrict__
                                                        const int32_t* __restrict__ l_ptr, const int32_t* __restrict__ lt_ptr,
                                                        const int32_t* __restrict__ lt_perm, const double* __restrict__ G,
                                                        float* __restrict__ dpos) {
-    pos_grad(OpenDiff{}, nullptr, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm, G, dpos);
+    pos_grad<OpenDiff, false>(OpenDiff{}, nullptr, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm, G,
+                              dpos);
 }
 
 __global__ __launch_bounds__(256) void pos_grad_pbc_kernel(const float* __restrict__ pos, const double* __restrict__ cells,
@@ -218,7 +258,54 @@ __global__ __launch_bounds__(256) void pos_grad_pbc_kernel(const float* __restri
                                                            float* __restrict__ dpos) {
     PeriodicDiff geom;
     geom.table = cells;
-    pos_grad(geom, node_graph, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm, G, dpos);
+    pos_grad<PeriodicDiff, false>(geom, node_graph, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm,
+                                  G, dpos);
+}
+
+__global__ __launch_bounds__(256) void pos_grad_pbc_virial_kernel(
+    const float* __restrict__ pos, const double* __restrict__ cells, const int32_t* __restrict__ node_graph, int64_t n,
+    const int32_t* __restrict__ g_ptr, const int32_t* __restrict__ g_row, const int32_t* __restrict__ g_col,
+    const int32_t* __restrict__ gt_ptr, const int32_t* __restrict__ gt_perm, const float* __restrict__ ddist_g,
+    const int32_t* __restrict__ l_ptr, const int32_t* __restrict__ l_col, const int32_t* __restrict__ lt_ptr,
+    const int32_t* __restrict__ lt_perm, const double* __restrict__ G, float* __restrict__ dpos,
+    double* __restrict__ atom_work) {
+    PeriodicDiff geom;
+    geom.table = cells;
+    pos_grad<PeriodicDiff, true>(geom, node_graph, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm,
+                                 G, dpos, l_col, atom_work);
+}
+
+// One workgroup of 256 threads per graph g: the threads stride over the atoms gptr[g] .. gptr[g + 1] of atom_work (kept inside
+// [0, n]) with nine fp64 sums each, then a fixed-order tree -- the wavefront butterfly, the four wavefronts through LDS -- and
+// thread 0 rounds the nine values once to fp32.  A graph without atoms or without edges gets exact zeros.
+__global__ __launch_bounds__(256) void virial_reduce_kernel(const double* __restrict__ atom_work,
+                                                            const int32_t* __restrict__ gptr, int64_t n,
+                                                            float* __restrict__ dstrain) {
+    __shared__ double part[4][9];
+    const int64_t g = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int64_t lo = gptr[g], hi = gptr[g + 1];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > n ? n : hi;
+    V3 vx = v3(0.0, 0.0, 0.0), vy = vx, vz = vx;
+    for (int64_t a = lo + tid; a < hi; a += 256) {
+        const double* __restrict__ w = atom_work + 9 * a;
+        vx = vx + v3(w[0], w[1], w[2]);
+        vy = vy + v3(w[3], w[4], w[5]);
+        vz = vz + v3(w[6], w[7], w[8]);
+    }
+    vx = wave_sum(vx), vy = wave_sum(vy), vz = wave_sum(vz);
+    if (lane == 0) {
+        double* o = part[wave];
+        o[0] = vx.x, o[1] = vx.y, o[2] = vx.z;
+        o[3] = vy.x, o[4] = vy.y, o[5] = vy.z;
+        o[6] = vz.x, o[7] = vz.y, o[8] = vz.z;
+    }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) dstrain[9 * g + k] = (float)((part[0][k] + part[1][k]) + (part[2][k] + part[3][k]));
+    }
 }
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)(n > 0 ? ceil_div(n, 256) : 1); }
@@ -271,5 +358,38 @@ extern "C" int pamnet_pos_bwd_pbc_f32(const float* pos, const double* cell_table
     hipLaunchKernelGGL(pos_grad_pbc_kernel, dim3(blocks_for(n * 64)), dim3(256), 0, st, pos, cell_table, node_graph, n, g_ptr,
                        g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm, bond_work, dpos);
     PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
+extern "C" int pamnet_pos_bwd_pbc_virial_f32(const float* pos, const double* cell_table, const int32_t* node_graph, int64_t n,
+                                             const int32_t* g_ptr, const int32_t* g_row, const int32_t* g_col,
+                                             const int32_t* gt_ptr, const int32_t* gt_perm, const float* ddist_g, int64_t eg,
+                                             const int32_t* l_ptr, const int32_t* l_row, const int32_t* l_col,
+                                             const int32_t* lt_ptr, const int32_t* lt_perm, const float* ddist_l, int64_t el,
+                                             const int32_t* t_ptr, const int32_t* t_row, const int32_t* t_col,
+                                             const int32_t* t_kind, const int32_t* tt_ptr, const int32_t* tt_perm,
+                                             const float* dangle, int64_t tp, double* bond_work, float* dpos, const int32_t* gptr,
+                                             int64_t n_graphs, double* atom_work, float* dstrain, pamnet_stream_t stream) {
+    if (n < 0 || eg < 0 || el < 0 || tp < 0 || n_graphs < 0) return PAMNET_EINVAL;
+    if (!pos || !cell_table || !node_graph || !g_ptr || !g_row || !g_col || !gt_ptr || !gt_perm || !ddist_g || !l_ptr ||
+        !l_row || !l_col || !lt_ptr || !lt_perm || !ddist_l || !t_ptr || !t_row || !t_col || !t_kind || !tt_ptr || !tt_perm ||
+        !dangle || !bond_work || !dpos || !gptr || !atom_work || !dstrain)
+        return PAMNET_EINVAL;
+    hipStream_t st = as_stream(stream);
+    if (n > 0) {
+        if (el > 0) {
+            hipLaunchKernelGGL(bond_grad_pbc_kernel, dim3(blocks_for(el * 64)), dim3(256), 0, st, pos, cell_table, node_graph,
+                               l_row, l_col, ddist_l, el, t_ptr, t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, bond_work);
+            PAMNET_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(pos_grad_pbc_virial_kernel, dim3(blocks_for(n * 64)), dim3(256), 0, st, pos, cell_table, node_graph, n,
+                           g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, l_col, lt_ptr, lt_perm, bond_work, dpos,
+                           atom_work);
+        PAMNET_LAUNCH_CHECK();
+    }
+    if (n_graphs > 0) {                               // (n == 0: every graph's atom range is empty, dstrain becomes zeros)
+        hipLaunchKernelGGL(virial_reduce_kernel, dim3((unsigned)n_graphs), dim3(256), 0, st, atom_work, gptr, n, dstrain);
+        PAMNET_LAUNCH_CHECK();
+    }
     return PAMNET_OK;
 }

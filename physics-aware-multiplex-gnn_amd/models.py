@@ -8,7 +8,8 @@ Same constructor arguments, attribute names, `state_dict()` keys/shapes and `for
 forward(data): duck-typed `data` with `.x`, `.batch` (sorted) and, for QM9, `.pos` [N,3] and `.edge_index` [2,E]
 (optionally `.num_graphs`).  QM9 without `.edge_index` (absent or None): bond-free molecules, the local graph is the radius
 graph at cutoff_l; such a batch may carry `.cell` (fp32 [num_graphs, 3, 3], row k = lattice vector a_k): periodic boundaries, every
-displacement the model uses is then the minimum-image one (graph.build_graph).  Returns fp32 [num_graphs], differentiable w.r.t. every parameter.  MI355X only: tensors must
+displacement the model uses is then the minimum-image one (graph.build_graph), and with `.strain` (fp32 zeros [num_graphs, 3, 3]
+that require grad) the gradient with respect to it is the virial per cell (graph.differentiable_geometry).  Returns fp32 [num_graphs], differentiable w.r.t. every parameter.  MI355X only: tensors must
 live on a HIP device -- there is no CPU path (the CPU oracle in oracle/ is test infrastructure and is never imported
 from here).
 """
@@ -515,7 +516,8 @@ class _PAMNetBase(nn.Module):
                           n_types=self.embeddings.size(0) if hasattr(self, 'embeddings') else None,
                           sizes=self._sizes_of(data), default_basis=self.sbf.default, mol_local=self._mol_local_of(data),
                           max_num_neighbors=self.max_num_neighbors, aux_tables=self.dim == fused.D,
-                          cell=getattr(data, 'cell', None))
+                          cell=getattr(data, 'cell', None), strain=getattr(data, 'strain', None))
+        g.strain_checked = getattr(data, 'strain', None) is not None
         if g.check is not None:                          # zero-host-sync path: the flag word waits for verify()
             self._pending_checks.append(g.check)
         g.need_grad = torch.is_grad_enabled()
@@ -692,12 +694,31 @@ class _PAMNetBase(nn.Module):
                                       % (self.sbf.num_spherical, self.sbf.num_radial, self.sbf.envelope_exponent))
         return src.to(torch.float32).contiguous()
 
-    def _forward_geometry(self, data, g, pos):
-        """Forward with the geometry linked to `pos` (graph.differentiable_geometry): plain autograd, the unfused input
-        route (explicit Bessel rows, embeddings that return their input gradient), and no direct gradient writes -- so that
-        torch.autograd.grad(E, pos) leaves every p.grad as it was (ops.no_direct_writes)."""
+    def _geometry_inputs(self, data, g):
+        """(pos, strain) when the forward takes the geometry route -- the positions require grad, or `data.strain` (periodic
+        batches: the variable of the virial, graph.differentiable_geometry) does, in grad mode; else None.  With the strain
+        alone the positions go in detached."""
+        pos = self._positions_with_grad(data)
+        strain = getattr(data, 'strain', None) if torch.is_grad_enabled() else None
+        if strain is None or not strain.requires_grad:
+            return None if pos is None else (pos, None)
+        if not self.sbf.default:
+            raise NotImplementedError('PAMNet: gradients with respect to the strain are implemented for the default basis '
+                                      '(num_spherical=7, num_radial=6, envelope_exponent=5) only; this model has (%d, %d, %d)'
+                                      % (self.sbf.num_spherical, self.sbf.num_radial, self.sbf.envelope_exponent))
+        if not getattr(g, 'strain_checked', False):
+            raise ValueError('`data.strain` was attached after model.prepare(data): attach it first (the graph built ahead of '
+                             'time validates it), or call model(data) without prepare')
+        if pos is None:
+            pos = data.pos.detach().to(torch.float32).contiguous()
+        return pos, strain
+
+    def _forward_geometry(self, data, g, pos, strain=None):
+        """Forward with the geometry linked to `pos` (and `strain`; graph.differentiable_geometry): plain autograd, the unfused
+        input route (explicit Bessel rows, embeddings that return their input gradient), and no direct gradient writes -- so
+        that torch.autograd.grad(E, pos) leaves every p.grad as it was (ops.no_direct_writes)."""
         with ops.no_direct_writes():
-            out = self._forward_on(data, G.differentiable_geometry(g, pos, self.cutoff_l), None)
+            out = self._forward_on(data, G.differentiable_geometry(g, pos, self.cutoff_l, strain), None)
         # the inspection hooks keep the plain graph and detached layer outputs: a dropped E frees its autograd graph
         self._graph_cache = g
         if isinstance(self._x_layers, _LazyLayers):
@@ -834,9 +855,9 @@ class PAMNet(_PAMNetBase):
     def _forward(self, data):
         self._release_inspection()
         g = self._graph(data)
-        pos = self._positions_with_grad(data)
-        if pos is not None:
-            return self._forward_geometry(data, g, pos)
+        geometry = self._geometry_inputs(data, g)
+        if geometry is not None:
+            return self._forward_geometry(data, g, *geometry)
         if self._one_node():
             return self._run_one_node(lambda tape: self._forward_on(data, g, tape))
         return self._forward_on(data, g, None)
@@ -884,9 +905,9 @@ class PAMNet_s(_PAMNetBase):
     def _forward(self, data):
         self._release_inspection()
         g = self._graph(data)
-        pos = self._positions_with_grad(data)
-        if pos is not None:
-            return self._forward_geometry(data, g, pos)
+        geometry = self._geometry_inputs(data, g)
+        if geometry is not None:
+            return self._forward_geometry(data, g, *geometry)
         if self._one_node():
             return self._run_one_node(lambda tape: self._forward_on(data, g, tape))
         return self._forward_on(data, g, None)

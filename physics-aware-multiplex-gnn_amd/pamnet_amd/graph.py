@@ -490,9 +490,35 @@ def _checked_cell(cell, dataset, edge_index, sizes, n_graphs, pos):
         raise ValueError('`cell` must live on the device of `pos` (%s); it is on %s -- move it with cell.to(pos.device)'
                          % (pos.device, cell.device))
     if cell.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError('gradients with respect to `cell` (stress, virial) are not implemented: detach the cell '
-                                  '(cell.detach()); forces with respect to `pos` are available')
+        raise NotImplementedError('a raw gradient with respect to `cell` is not implemented: detach the cell (cell.detach()) '
+                                  'and, for the stress / virial, attach `data.strain = torch.zeros(num_graphs, 3, 3, device=..., '
+                                  'requires_grad=True)` and differentiate with respect to it (torch.autograd.grad(E.sum(), '
+                                  '[data.pos, data.strain])); forces with respect to `pos` are available')
     return cell.detach().contiguous().view(int(n_graphs), 9)
+
+
+def _checked_strain(strain, cell, n_graphs, pos):
+    """`data.strain` names the variable of the virial: fp32 zeros [num_graphs, 3, 3] on the device of `pos`, on a periodic batch.
+    Returns its count of non-zero entries as a device scalar (it travels with the sizes' round trip, _Sizes.read), or raises the
+    refusal that says what to do instead."""
+    if cell is None:
+        raise ValueError('`strain` belongs to periodic batches (`cell`): drop it -- for an isolated molecule the virial is '
+                         'sum_a pos_a (x) dE/dpos_a, from the forces alone -- or hand the structure over with its `cell`')
+    if not isinstance(strain, torch.Tensor) or strain.dtype != torch.float32 or tuple(strain.shape) != (int(n_graphs), 3, 3):
+        raise ValueError('`strain` must be a float32 tensor of zeros of shape [num_graphs, 3, 3] = [%d, 3, 3] (one strain tensor '
+                         'per cell); got %s %s' % (int(n_graphs), getattr(strain, 'dtype', type(strain)),
+                                                   tuple(getattr(strain, 'shape', ()))))
+    if strain.device != pos.device:
+        raise ValueError('`strain` must be a float32 tensor [num_graphs, 3, 3] on the device of `pos` (%s); it is on %s -- create '
+                         'it there (torch.zeros(num_graphs, 3, 3, device=pos.device, requires_grad=True))'
+                         % (pos.device, strain.device))
+    return strain.detach().count_nonzero()
+
+
+def _raise_nonzero_strain(count):
+    raise ValueError('`strain` has %d non-zero entries: it only names the variable of differentiation.  The derivative is taken '
+                     'at the geometry given: deform `pos` and `cell` yourself (pos @ (I + eps), cell @ (I + eps)) and pass zeros'
+                     % count)
 
 
 class GraphCheckError(IndexError):
@@ -765,15 +791,22 @@ class _Sizes(object):
         self.checks.append((ptr[-1:], k))
         return torch.clamp(ptr, max=k) if clamp else ptr
 
-    def read(self, *scalars, allow=0, cutoffs=None):
+    def read(self, *scalars, allow=0, cutoffs=None, strain_nz=None):
         """The device scalars and the flag word in ONE host round trip: (integers, capped).  Raises for a flag bit outside
-        `allow` (CAP_BIT: the neighbour cap bound, no error; PBC_BIT: a bad cell, raised second, with `cutoffs`)."""
-        got = host_ints(*scalars, self.flag)
+        `allow` (CAP_BIT: the neighbour cap bound, no error; PBC_BIT: a bad cell, raised second, with `cutoffs`).  `strain_nz`
+        (_checked_strain): one more device scalar of the same read, raised last when it is not zero."""
+        if strain_nz is None:
+            got, nz = host_ints(*scalars, self.flag), 0
+        else:
+            got = host_ints(*scalars, self.flag, strain_nz)
+            nz = got.pop()
         bad = got.pop()
         if bad & ~allow:
             _raise_bad_inputs()
         if bad & PBC_BIT:
             _raise_bad_cell(*cutoffs)
+        if nz:
+            _raise_nonzero_strain(nz)
         return got, bool(bad & CAP_BIT)
 
 
@@ -803,7 +836,7 @@ class _Lists(object):
 
 
 _Args = namedtuple('_Args', 'cutoff_l cutoff_g flow x_raw pos edge_index need_grad knn_k with_triplets n_types sizes mol_local '
-                            'max_nb cell')
+                            'max_nb cell strain_nz')
 _Bonds = namedtuple('_Bonds', 'ptr src dst dist tp_ptr tcount raw')
 
 
@@ -866,7 +899,8 @@ def _qm9_bond_free(g, ing, a):
         gptr_g, lp = sz.expect(gptr_g, total_g), sz.expect(lp, total_l)
     else:
         (total_g, total_l, r.tp_hint), r.capped = sz.read(gptr_g[-1], lp[-1], _symmetric_tp_total(lp, a.with_triplets),
-                                                          allow=CAP_BIT | PBC_BIT, cutoffs=(a.cutoff_l, a.cutoff_g))
+                                                          allow=CAP_BIT | PBC_BIT, cutoffs=(a.cutoff_l, a.cutoff_g),
+                                                          strain_nz=a.strain_nz)
     rows = []
     r.gp, r.gn, r.gd = radius_fill(pos, g.node_graph, g.gptr, a.cutoff_g, gptr_g, total_g, zeroed=sz.arena, rows_out=rows,
                                    max_neighbors=a.max_nb, cell_tab=tab)
@@ -1060,7 +1094,7 @@ def _finish(g, r, dataset, a):
 
 def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_index=None, num_graphs=None,
                 need_grad=True, knn_k=None, with_triplets=True, n_types=None, sizes=None, default_basis=True, mol_local=None,
-                max_num_neighbors=None, aux_tables=True, cell=None):
+                max_num_neighbors=None, aux_tables=True, cell=None, strain=None):
     """Graph-construction part of PAMNet.forward (models.py:104-177).  Returns a Graph.
 
     `cell` (QM9 schema, bond-free, no `sizes`): fp32 [num_graphs, 3, 3] on the device, row k of cell[g] = lattice vector a_k of
@@ -1068,6 +1102,9 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
     radius searches, the bond lengths, both angle kinds and the position backward.  Positions need not be wrapped.  Each cell
     must be non-singular with all three perpendicular heights above 2 * max(cutoff_l, cutoff_g) (ValueError otherwise, with the
     sizes' round trip).  Always the step-by-step launches.
+
+    `strain` (periodic batches): the tensor that names the variable of the virial (differentiable_geometry) -- fp32 zeros
+    [num_graphs, 3, 3] on the device.  Only validated here; its count of non-zero entries rides in the sizes' round trip.
 
     `sizes`: (global edges, local edges, triplet + pair rows) of this batch as host integers -- what a batch collated by
     pamnet_amd.store.MoleculeStore carries.  With them no value is read back from the device: buffers are sized from
@@ -1095,6 +1132,7 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
         if n_graphs is None:
             n_graphs = int(batch[-1]) + 1
         cell = _checked_cell(cell, dataset, edge_index, sizes, n_graphs, pos)
+    strain_nz = None if strain is None else _checked_strain(strain, cell, n_graphs, pos)
     max_nb = int(max_num_neighbors or 0)
     knn_k = KNN_K if knn_k is None else int(knn_k)
     if sizes is not None and knn_k != KNN_K:
@@ -1129,7 +1167,7 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
         raise ValueError("Invalid dataset. If you are using any dataset related to RNA 3D structure prediction, "
                          "be sure to use 'rna' as the first 3 characters of the dataset name.")
     a = _Args(cutoff_l, cutoff_g, flow, x_raw, pos, edge_index, need_grad, knn_k, with_triplets, n_types, sizes, mol_local,
-              max_nb, cell)
+              max_nb, cell, strain_nz)
     r = lists(g, ing, a)
     if r is not None:                             # (None: the molecule-local builder has made everything)
         _finish(g, r, dataset, a)
@@ -1205,16 +1243,18 @@ def _index_lists(g):
 
 
 class _Geometry(torch.autograd.Function):
-    """pos [N, 3] -> (dist_g, dist_l, tp_angle) of a graph built from these positions (models.py:62-66,165-177).  The
-    forward hands out the values graph construction already computed; the backward is pamnet_pos_bwd_f32.  Everything
-    the backward reads is kept (pos through save_for_backward, so an in-place change of it is caught): a graph that is
-    retained can be walked again."""
+    """pos [N, 3] (, strain [G, 3, 3] of zeros, periodic graphs) -> (dist_g, dist_l, tp_angle) of a graph built from these
+    positions (models.py:62-66,165-177).  The forward hands out the values graph construction already computed; the backward is
+    pamnet_pos_bwd_f32 -- or, when the gradient with respect to the strain is asked for, pamnet_pos_bwd_pbc_virial_f32, which
+    writes the same dpos and the virial of every graph.  Everything the backward reads is kept (pos through save_for_backward,
+    so an in-place change of it is caught): a graph that is retained can be walked again."""
 
     @staticmethod
-    def forward(ctx, pos, g):
+    def forward(ctx, pos, strain, g):
         ctx.save_for_backward(pos)
         ctx.idx = _index_lists(g)
         ctx.pbc = None if g.cell_tab is None else (g.cell_tab, g.node_graph)      # periodic graph: the image rule's inputs
+        ctx.graphs = None if strain is None else (g.gptr, int(g.n_graphs))        # what the virial's reduction reads
         return g.dist_g.clone(), g.dist_l.clone(), g.tp_angle.clone()
 
     @staticmethod
@@ -1228,9 +1268,17 @@ class _Geometry(torch.autograd.Function):
         work = torch.empty(3 * max(el, 1), dtype=torch.float64, device=pos.device)
         dpos = torch.empty((n, 3), dtype=torch.float32, device=pos.device)
         P = lib.ptr
-        _call_in_cell('pamnet_pos_bwd_f32', 'pamnet_pos_bwd_pbc_f32', pos, ctx.pbc, n, *map(P, glob), P(d_dg), eg, *map(P, loc),
-                      P(d_dl), el, *map(P, trip), P(d_ang), tp, P(work), P(dpos), lib.stream_of(pos))
-        return dpos, None
+        if not (ctx.graphs is not None and ctx.needs_input_grad[1]):
+            _call_in_cell('pamnet_pos_bwd_f32', 'pamnet_pos_bwd_pbc_f32', pos, ctx.pbc, n, *map(P, glob), P(d_dg), eg,
+                          *map(P, loc), P(d_dl), el, *map(P, trip), P(d_ang), tp, P(work), P(dpos), lib.stream_of(pos))
+            return dpos, None, None
+        gptr, n_graphs = ctx.graphs
+        atom_work = torch.empty(9 * max(n, 1), dtype=torch.float64, device=pos.device)
+        dstrain = torch.empty((max(n_graphs, 1), 9), dtype=torch.float32, device=pos.device)[:n_graphs]
+        lib.call('pamnet_pos_bwd_pbc_virial_f32', P(pos), *map(P, ctx.pbc), n, *map(P, glob), P(d_dg), eg, *map(P, loc), P(d_dl),
+                 el, *map(P, trip), P(d_ang), tp, P(work), P(dpos), P(gptr), n_graphs, P(atom_work), P(dstrain),
+                 lib.stream_of(pos))
+        return (dpos if ctx.needs_input_grad[0] else None), dstrain.view(n_graphs, 3, 3), None
 
 
 class _SphericalBasis(torch.autograd.Function):
@@ -1274,12 +1322,19 @@ class _DiffGraph(object):
         return getattr(self.__dict__['_plain'], name)
 
 
-def differentiable_geometry(g, pos, cutoff_l):
+def differentiable_geometry(g, pos, cutoff_l, strain=None):
     """Graph `g` (built from `pos`, fp32 [N, 3], with the backward index lists: need_grad) seen with its geometry linked to
     `pos`: dist_g, dist_l, tp_angle and the default-basis rows sbf are outputs of autograd Functions whose backward passes
-    are HIP kernels.  Values are unchanged (the same tensors' contents); `g` itself is not modified."""
+    are HIP kernels.  Values are unchanged (the same tensors' contents); `g` itself is not modified.
+
+    `strain` (a periodic graph; fp32 zeros [num_graphs, 3, 3], validated by build_graph(strain=)): the geometry is linked to it
+    as well.  Its gradient is the virial per cell, W[g][a][b] = sum over the directed global edges and local bonds of graph g of
+    v_e[a] * (dE / dv_e)[b] with v_e the minimum-image vector: the derivative under pos -> pos @ (I + eps_g), cell[g] -> cell[g]
+    @ (I + eps_g) at eps = 0, image integers held fixed.  Sign, volume, symmetrisation and Voigt order are the caller's."""
     if g.glob_T is _NoTranspose or g.loc_T is _NoTranspose or g.tp_T is _NoTranspose:
         raise RuntimeError('differentiable geometry needs a graph built with need_grad=True')
-    dist_g, dist_l, angle = _Geometry.apply(pos, g)
+    if strain is not None and g.cell_tab is None:
+        raise ValueError('`strain` belongs to periodic graphs (build_graph(cell=)): this graph was built in open space')
+    dist_g, dist_l, angle = _Geometry.apply(pos, strain, g)
     sbf = _SphericalBasis.apply(dist_l, angle, g, cutoff_l, g.sbf)
     return _DiffGraph(g, dist_g=dist_g, dist_l=dist_l, tp_angle=angle, sbf=sbf)
