@@ -60,6 +60,27 @@ int bwd(const int64_t* sizes, const int32_t* const* graph_idx, int64_t n_layer, 
         float* const* ggrads, float* const* lgrads, float* d_x0, float* d_eg, float* d_rbf, float* d_sbf,
         void* const* layer_done, pamnet_stream_t stream);
 }  // namespace narrow_stack
+
+// Launchers of the narrow-width row kernels (narrow_core.h) that both the pamnet_narrow_* entry points and the narrow engine
+// use, defined in narrow.hip.  Each owns its kernel's grid, block and LDS bytes; the arguments are the kernel's, with the
+// width first and the stream last.  A backward kernel leaves bwd_row_grid(m, d) partial rows of n*_bwd_stride(d) floats in
+// `partial` (nlinear_bwd: of `stride` floats, so that several blocks can share a row); the caller reduces them.  Not exported.
+namespace narrow_rows {
+int global_fwd(int d, const float* e, int64_t m, const int32_t* tgt, const int32_t* src, const float* P, const float* We,
+               int ldwe, const float* bias, const float* Wea, int ldwea, float* msg, hipStream_t st);
+int global_bwd(int d, const float* e, int64_t m, const int32_t* tgt, const int32_t* src, const float* P, const float* We,
+               int ldwe, const float* bias, const float* Wea, int ldwea, const float* dagg, float* dz, float* de,
+               float* partial, int acc_de, hipStream_t st);
+int mlp2_fwd(int d, const float* x, int64_t m, const float* W1, const float* b1, const float* W2, const float* b2, int res_x,
+             const float* res, float* y, hipStream_t st);
+int mlp2_bwd(int d, const float* x, int64_t m, const float* W1, const float* b1, const float* W2, const float* b2,
+             const float* dy, int res_x, float* dx, float* partial, int acc_dx, hipStream_t st);
+int linear_bwd(int d, const float* x, int64_t m, const float* W, int ldw, const float* b, int act, const float* dy,
+               int64_t lddy, float* dx, int accumulate, float* partial, int stride, hipStream_t st);
+int local_gate_bwd(int d, const float* P, const float* Q, const int32_t* tgt, const int32_t* src, const float* b_ji,
+                   const float* b_kj, int64_t m, const float* g_ji, const float* g_nb, float* dz, float* dQ, int zero_q3,
+                   hipStream_t st);
+}  // namespace narrow_rows
 #pragma GCC visibility pop
 
 __device__ __forceinline__ float silu_f(float z) { return z * __builtin_amdgcn_rcpf(1.0f + __expf(-z)); }

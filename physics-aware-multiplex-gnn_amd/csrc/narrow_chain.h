@@ -764,6 +764,7 @@ constexpr size_t ntail_bwd_lds() {
 }
 template <int D>
 constexpr size_t npre_fwd_lds() { return (1 + NPB) * (size_t)D * D * 4 + 4 * 16 * (D + 4) * 4; }
+constexpr int npre_bwd_stride(int d, int nb) { return (nb + 1) * d * d + d; }     // partial row: [dWp_0 .. dWp_{nb-1}][dW1][db1]
 template <int D>
 constexpr size_t npre_bwd_lds() {
     return (2 + NPB) * (size_t)D * D * 4 + CHW * 16 * (D + 4) * 4 + (tail_resident(D) ? CHW : 1) * ((size_t)D * D + D) * 4;

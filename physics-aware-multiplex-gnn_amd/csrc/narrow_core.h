@@ -18,6 +18,7 @@
 // (mlp_sbf), models.py:185-188 (edge-embedding MLPs).
 #pragma once
 #include <stdlib.h>
+#include <type_traits>
 #include "common.h"
 #include "gemm_core.h"
 
@@ -446,6 +447,8 @@ __global__ __launch_bounds__(NWG, D == 64 ? NGF_CAP : 1) void nglobal_fwd_kernel
         }
     }
 }
+template <int D>
+constexpr size_t nglobal_fwd_lds() { return 2 * wimg_bytes(D); }
 
 // backward: dmsg[row] = dagg[tgt[row]].  Outputs dz [m, D] (for the two node-side segment sums), de [m, D],
 // and per-workgroup partials of dWe, dWea (fragment order) and db.
@@ -578,6 +581,9 @@ __global__ __launch_bounds__(64 * bwd_waves(D)) void nglobal_bwd_kernel(const fl
         red_add_bias<NT>(r + 2 * MAT, dbs, lane, first);
     });
 }
+template <int D>
+constexpr size_t nglobal_bwd_lds() { return 4 * wimg_bytes(D) + bwd_waves(D) * 16 * (D + 4) * sizeof(float); }
+constexpr int nglobal_bwd_stride(int d) { return 2 * d * d + d; }            // partial row: [dWe][dWea][db]
 
 // ====================================================================================================================
 // Two-layer SiLU MLP on rows (mlp_sbf of the local layer, layers/local_message_passing.py:24,49):
@@ -643,6 +649,8 @@ __global__ __launch_bounds__(NWG) void nmlp2_fwd_kernel(const float* __restrict_
         store_d<D>(o, y, row0, m, lane);
     }
 }
+template <int D>
+constexpr size_t nmlp2_fwd_lds() { return 2 * wimg_bytes(D) + 4 * 16 * (D + 4) * sizeof(float); }
 
 template <int D>
 __global__ __launch_bounds__(64 * bwd_waves(D)) void nmlp2_bwd_kernel(const float* __restrict__ x, int64_t m,
@@ -766,6 +774,9 @@ __global__ __launch_bounds__(64 * bwd_waves(D)) void nmlp2_bwd_kernel(const floa
         red_add_bias<NT>(r + 2 * MAT + D, db2, lane, first);
     });
 }
+template <int D>
+constexpr size_t nmlp2_bwd_lds() { return 4 * wimg_bytes(D) + bwd_waves(D) * 16 * (D + 4) * sizeof(float); }
+constexpr int nmlp2_bwd_stride(int d) { return 2 * d * d + 2 * d; }          // partial row: [dW1][dW2][db1][db2]
 
 // ====================================================================================================================
 // One dense layer on rows: y = act(x W^T + b), W a [D, D] block with row stride ldw (slices of the 3d-wide message
@@ -802,6 +813,8 @@ __global__ __launch_bounds__(NWG) void nlinear_fwd_kernel(const float* __restric
         store_d<D>(o, y, row0, m, lane, ldy);
     }
 }
+template <int D>
+constexpr size_t nlinear_fwd_lds() { return wimg_bytes(D); }
 
 // dx (+)= dz W;  partial = [dW fragments (D x D)][db (D)]
 template <int D>
@@ -895,6 +908,9 @@ __global__ __launch_bounds__(64 * lin_bwd_waves(D)) void nlinear_bwd_kernel(cons
         red_add_bias<NT>(r + MAT, dbs, lane, first);
     });
 }
+template <int D>
+constexpr size_t nlinear_bwd_lds() { return 2 * wimg_bytes(D) + lin_bwd_waves(D) * 16 * (D + 4) * sizeof(float); }
+constexpr int nlinear_bwd_stride(int d) { return d * d + d; }                // partial row: [dW][db]
 
 // The four bias-free projection blocks of the edge-side Q = rbf [W_0 | W_1 | W_2 | W_3]^T in ONE pass over the rows
 // (d <= 32: four D x D accumulator sets fit the registers): per 16-row tile x is read once, d rbf (+)= sum_k dQ_k W_k is
@@ -963,6 +979,13 @@ __global__ __launch_bounds__(64 * lin_bwd_waves(D)) void nqblock4_bwd_kernel(con
             red_add_bias<NT>(r + k * QS + MAT, dbs[k], lane, first);
         }
     });
+}
+constexpr int nqblock4_bwd_stride(int d) { return 4 * nlinear_bwd_stride(d); }
+template <int D>
+constexpr size_t nqblock4_bwd_lds() {                        // the layout, or the four blocks' partial row where that is larger
+    constexpr size_t lds = 4 * wimg_bytes(D) + lin_bwd_waves(D) * 16 * (D + 4) * sizeof(float);
+    constexpr size_t need = nqblock4_bwd_stride(D) * sizeof(float);
+    return lds > need ? lds : need;
 }
 
 // ====================================================================================================================
@@ -1034,6 +1057,7 @@ __global__ __launch_bounds__(256) void nheads_bwd_kernel(const float* __restrict
         partial[(size_t)blockIdx.x * (2 * D + 1) + p] = s;
     }
 }
+constexpr int nheads_bwd_stride(int d) { return 2 * d + 1; }
 
 // ====================================================================================================================
 // Local-edge gates (layers/local_message_passing.py:46-48 after the W[x_i | x_j | rbf] split): per local edge q = (j -> i)
@@ -1237,6 +1261,8 @@ __global__ __launch_bounds__(NWG) void nembed_fwd_kernel(const float* __restrict
         store_d<D>(acc, y, row0, m, lane);
     }
 }
+template <int D, int K, bool TWO>
+constexpr size_t nembed_fwd_lds() { return (TWO ? 2 : 1) * (size_t)D * ((K + 15) / 16 * 16) * sizeof(float); }
 
 // backward: partial = [dWa fragments (D x KP)][dWb fragments if TWO][dba (D)][dbb (D) if TWO]; df [m, K] only for
 // the single-set K = 16 case (the Bessel frequencies are trainable, layers/basic.py:65-72).
@@ -1427,21 +1453,47 @@ __global__ __launch_bounds__(64 * bwd_waves(D)) void nembed_bwd_kernel(const flo
         }
     });
 }
+template <int D, int K, bool TWO, bool DX>
+constexpr size_t nembed_bwd_lds() {
+    constexpr int KP = (K + 15) / 16 * 16;
+    constexpr size_t scratch = bwd_waves(D) * 16 * ((KP > D ? KP : D) + 4) * sizeof(float);
+    return ((TWO ? 2 : 1) + (DX ? 1 : 0)) * (size_t)D * KP * sizeof(float) + scratch;
+}
+// partial row: `sets` x ([dW (d x kp)] ... [db (d)] ...), then the 16 frequency gradients of the Bessel form
+constexpr int nembed_bwd_stride(int d, int kp, int sets, bool rbf = false) { return sets * (d * kp + d) + (rbf ? 16 : 0); }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
-inline int grid_for(int64_t m, int per_cu, int waves = 4) {
+inline bool width_ok(int64_t d) { return d == 16 || d == 32 || d == 64; }
+
+// Workgroups of a backward row kernel at most (one per CU), each leaving one partial row.  Three users rely on
+//   backward grid <= blocks reported to the caller = blocks the engine's arena is sized for:
+// bwd_row_grid below, pamnet_narrow_blocks (narrow.hip) and make_layout (narrow_engine.hip) all take it from here.
+constexpr int NARROW_BLOCKS = 256;
+
+constexpr int grid_for(int64_t m, int per_cu, int waves = 4) {
     const int64_t tiles = (m + 15) / 16;
     const int64_t want = (tiles + waves - 1) / waves;        // one tile per wave
-    const int64_t cap = 256 * (int64_t)per_cu;
+    const int64_t cap = NARROW_BLOCKS * (int64_t)per_cu;
     return (int)(want < cap ? (want > 0 ? want : 1) : cap);
 }
 
-inline bool width_ok(int64_t d) { return d == 16 || d == 32 || d == 64; }
-
 // Workgroups that are co-resident per CU: the backward kernels at d = 64 hold ~350 registers per lane and ~80 KB of
 // weight images, so one 4-wave workgroup fills a CU; a grid beyond that only adds a second, nearly empty round.
-inline int fwd_per_cu(int64_t d) { return d == 64 ? 2 : (d == 16 ? 8 : 4); }
+constexpr int fwd_per_cu(int64_t d) { return d == 64 ? 2 : (d == 16 ? 8 : 4); }
 
+// The grids of the row kernels.  A backward grid is also the number of partial rows: whoever sizes or reduces them calls
+// bwd_row_grid with the launcher's (m, d).
+constexpr int fwd_row_grid(int64_t m, int64_t d) { return grid_for(m, fwd_per_cu(d)); }
+constexpr int bwd_row_grid(int64_t m, int64_t d) { return grid_for(m, 1, bwd_waves((int)d)); }
+static_assert(bwd_row_grid(INT64_MAX / 2, 16) == NARROW_BLOCKS && bwd_row_grid(INT64_MAX / 2, 64) == NARROW_BLOCKS,
+              "a backward grid never exceeds the partial rows callers provide");
+static_assert(lin_bwd_waves(16) == bwd_waves(16) && lin_bwd_waves(32) == bwd_waves(32) && lin_bwd_waves(64) == bwd_waves(64),
+              "bwd_row_grid serves the single-layer backward kernels too");
+// element-wise kernels: 256 threads, one float4 each, grid-stride beyond 4096 workgroups
+constexpr int ew_grid(int64_t total) {
+    const int64_t want = (total + 255) / 256;
+    return (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
+}
 
 template <typename Kern>
 inline hipError_t allow_lds(Kern k, size_t bytes) {
@@ -1449,11 +1501,25 @@ inline hipError_t allow_lds(Kern k, size_t bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-#define NARROW_DISPATCH(d, CALL)     \
-    switch ((int)(d)) {              \
-        case 16: { CALL(16); } break; \
-        case 32: { CALL(32); } break; \
-        default: { CALL(64); } break; \
+// f(D) with the width as a compile-time constant: D converts to int in template arguments and `if constexpr`
+template <typename F>
+inline int narrow_dispatch(int64_t d, F&& f) {
+    switch ((int)d) {
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        default: return f(std::integral_constant<int, 64>{});
     }
+}
+
+// Every launch of the narrow-width kernels: the request for more than 64 KB of dynamic LDS where `lds` needs it, the launch,
+// the launch check.  Arguments convert to the kernel's parameter types (a literal nullptr or 0 needs no cast).
+template <typename... Params, typename... Args>
+inline int narrow_launch(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    const hipError_t e = allow_lds(kern, lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kern, grid, block, lds, st, static_cast<Params>(args)...);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
 
 }  // namespace

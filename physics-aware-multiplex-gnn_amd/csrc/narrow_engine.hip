@@ -61,25 +61,12 @@ __global__ __launch_bounds__(256) void nlocal_msg_bwd_kernel(const float4* __res
     }
 }
 
-inline int ew_grid(int64_t total) {
-    const int64_t want = (total + 255) / 256;
-    return (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
-}
-
-// ---- launches --------------------------------------------------------------------------------------------------------
+// ---- launches: take the kernel's partial rows from the Reducer, launch, register where the rows' segments are summed to ----
 int launch_tail_fwd(int d, const NTailFwd& p, hipStream_t st) {
     if (p.m == 0) return PAMNET_OK;
-    const int grid = chain_grid(p.m);
-#define CALL(DD)                                                                                          \
-    {                                                                                                     \
-        const hipError_t e_ = allow_lds(ntail_fwd_kernel<DD>, ntail_fwd_lds<DD>());                       \
-        if (e_ != hipSuccess) return (int)e_;                                                             \
-        hipLaunchKernelGGL((ntail_fwd_kernel<DD>), dim3(grid), dim3(64 * CHW), ntail_fwd_lds<DD>(), st, p); \
-    }
-    NARROW_DISPATCH(d, CALL)
-#undef CALL
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
+    return narrow_dispatch(d, [&](auto D) {
+        return narrow_launch(ntail_fwd_kernel<D>, chain_grid(p.m), 64 * CHW, ntail_fwd_lds<D>(), st, p);
+    });
 }
 
 inline int tail_stride(int d) { return d == 16 ? TailRow<16>::STRIDE : (d == 32 ? TailRow<32>::STRIDE : TailRow<64>::STRIDE); }
@@ -90,19 +77,10 @@ int launch_tail_bwd(int d, NTailBwd p, float* const* gW, float* const* gb, float
     if (p.m == 0) return PAMNET_EINVAL;
     const int grid = chain_grid(p.m);
     p.stride = tail_stride(d);
-    {
-        const int rc = R.take(grid, p.stride, 23, &p.partial);
-        if (rc) return rc;
-    }
-#define CALL(DD)                                                                                          \
-    {                                                                                                     \
-        const hipError_t e_ = allow_lds(ntail_bwd_kernel<DD>, ntail_bwd_lds<DD>());                       \
-        if (e_ != hipSuccess) return (int)e_;                                                             \
-        hipLaunchKernelGGL((ntail_bwd_kernel<DD>), dim3(grid), dim3(64 * CHW), ntail_bwd_lds<DD>(), st, p); \
-    }
-    NARROW_DISPATCH(d, CALL)
-#undef CALL
-    PAMNET_LAUNCH_CHECK();
+    TRY(R.take(grid, p.stride, 23, &p.partial));
+    TRY(narrow_dispatch(d, [&](auto D) {
+        return narrow_launch(ntail_bwd_kernel<D>, grid, 64 * CHW, ntail_bwd_lds<D>(), st, p);
+    }));
     const int MAT = d * d, LIN = MAT + d, MLP = 2 * MAT + 2 * d;
     SegTable& T = R.T;
     T.mat(gW[0], 0, d, d, d, d);
@@ -126,17 +104,9 @@ int launch_tail_bwd(int d, NTailBwd p, float* const* gW, float* const* gb, float
 
 int launch_pre_fwd(int d, const NPreFwd& p, hipStream_t st) {
     if (p.m == 0) return PAMNET_OK;
-    const int grid = grid_for(p.m, fwd_per_cu(d));
-#define CALL(DD)                                                                                      \
-    {                                                                                                 \
-        const hipError_t e_ = allow_lds(npre_fwd_kernel<DD>, npre_fwd_lds<DD>());                     \
-        if (e_ != hipSuccess) return (int)e_;                                                         \
-        hipLaunchKernelGGL((npre_fwd_kernel<DD>), dim3(grid), dim3(NWG), npre_fwd_lds<DD>(), st, p);  \
-    }
-    NARROW_DISPATCH(d, CALL)
-#undef CALL
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
+    return narrow_dispatch(d, [&](auto D) {
+        return narrow_launch(npre_fwd_kernel<D>, fwd_row_grid(p.m, D), NWG, npre_fwd_lds<D>(), st, p);
+    });
 }
 
 // gWp[k]: gradient destination of projection block k (row stride ldg[k]); gW1 [d, d], gb1 [d]
@@ -144,20 +114,11 @@ int launch_pre_bwd(int d, NPreBwd p, float* const* gWp, const int* ldg, float* g
     if (p.m == 0) return PAMNET_EINVAL;
     const int grid = chain_grid(p.m);
     const int MAT = d * d;
-    p.stride = (p.nb + 1) * MAT + d;
-    {
-        const int rc = R.take(grid, p.stride, p.nb + 2, &p.partial);
-        if (rc) return rc;
-    }
-#define CALL(DD)                                                                                         \
-    {                                                                                                    \
-        const hipError_t e_ = allow_lds(npre_bwd_kernel<DD>, npre_bwd_lds<DD>());                        \
-        if (e_ != hipSuccess) return (int)e_;                                                            \
-        hipLaunchKernelGGL((npre_bwd_kernel<DD>), dim3(grid), dim3(64 * CHW), npre_bwd_lds<DD>(), st, p); \
-    }
-    NARROW_DISPATCH(d, CALL)
-#undef CALL
-    PAMNET_LAUNCH_CHECK();
+    p.stride = npre_bwd_stride(d, p.nb);
+    TRY(R.take(grid, p.stride, p.nb + 2, &p.partial));
+    TRY(narrow_dispatch(d, [&](auto D) {
+        return narrow_launch(npre_bwd_kernel<D>, grid, 64 * CHW, npre_bwd_lds<D>(), st, p);
+    }));
     SegTable& T = R.T;
     for (int k = 0; k < p.nb; ++k) T.mat(gWp[k], k * MAT, d, d, d, ldg[k]);
     T.mat(gW1, p.nb * MAT, d, d, d, d);
@@ -165,44 +126,13 @@ int launch_pre_bwd(int d, NPreBwd p, float* const* gWp, const int* ldg, float* g
     return PAMNET_OK;
 }
 
-constexpr int EROW_BLOCKS = 256;            // backward row kernels: at most one workgroup per CU (narrow_core.h)
-
-int launch_global_fwd(int d, const float* e, int64_t m, const int32_t* tgt, const int32_t* src, const float* P,
-                      const float* We, int ldwe, const float* bias, const float* Wea, int ldwea, float* msg,
-                      hipStream_t st) {
-    if (m == 0) return PAMNET_OK;
-    const int grid = grid_for(m, fwd_per_cu(d));
-#define CALL(DD)                                                                                                       \
-    hipLaunchKernelGGL((nglobal_fwd_kernel<DD>), dim3(grid), dim3(NWG), 2 * wimg_bytes(DD), st, e, m, tgt, \
-                       src, P, We, ldwe, bias, Wea, ldwea, msg);
-    NARROW_DISPATCH(d, CALL)
-#undef CALL
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
-}
-
 int launch_global_bwd(int d, const float* e, int64_t m, const int32_t* tgt, const int32_t* src, const float* P,
                       const float* We, int ldwe, const float* bias, const float* Wea, int ldwea, const float* dagg,
                       float* dz, float* de, int acc_de, Reducer& R, float* gWe, int ldgwe, float* gWea, float* gb,
                       hipStream_t st) {
-    const int grid = grid_for(m, 1, bwd_waves(d));
-    const int stride = 2 * d * d + d;
     float* partial = nullptr;
-    {
-        const int rc = R.take(grid, stride, 3, &partial);
-        if (rc) return rc;
-    }
-#define CALL(DD)                                                                                                     \
-    {                                                                                                                \
-        const size_t lds = 4 * wimg_bytes(DD) + bwd_waves(DD) * 16 * (DD + 4) * sizeof(float);      \
-        const hipError_t e_ = allow_lds(nglobal_bwd_kernel<DD>, lds);                                                \
-        if (e_ != hipSuccess) return (int)e_;                                                                        \
-        hipLaunchKernelGGL((nglobal_bwd_kernel<DD>), dim3(grid), dim3(64 * bwd_waves(DD)), lds, st, e, m, tgt, src, P, We, \
-                           ldwe, bias, Wea, ldwea, dagg, dz, de, partial, stride, acc_de);                           \
-    }
-    NARROW_DISPATCH(d, CALL)
-#undef CALL
-    PAMNET_LAUNCH_CHECK();
+    TRY(R.take(bwd_row_grid(m, d), nglobal_bwd_stride(d), 3, &partial));
+    TRY(narrow_rows::global_bwd(d, e, m, tgt, src, P, We, ldwe, bias, Wea, ldwea, dagg, dz, de, partial, acc_de, st));
     SegTable& T = R.T;
     T.mat(gWe, 0, d, d, d, ldgwe);
     T.mat(gWea, d * d, d, d, d, d);
@@ -210,43 +140,12 @@ int launch_global_bwd(int d, const float* e, int64_t m, const int32_t* tgt, cons
     return PAMNET_OK;
 }
 
-int launch_mlp2_fwd(int d, const float* x, int64_t m, const float* W1, const float* b1, const float* W2, const float* b2,
-                    float* y, hipStream_t st) {
-    if (m == 0) return PAMNET_OK;
-    const int grid = grid_for(m, fwd_per_cu(d));
-#define CALL(DD)                                                                                                  \
-    {                                                                                                             \
-        const size_t lds = 2 * wimg_bytes(DD) + 4 * 16 * (DD + 4) * sizeof(float);               \
-        hipLaunchKernelGGL((nmlp2_fwd_kernel<DD>), dim3(grid), dim3(NWG), lds, st, x, m, W1, b1, W2, b2, 0,       \
-                           (const float*)nullptr, y);                                                             \
-    }
-    NARROW_DISPATCH(d, CALL)
-#undef CALL
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
-}
-
 int launch_mlp2_bwd(int d, const float* x, int64_t m, const float* W1, const float* b1, const float* W2, const float* b2,
                     const float* dy, float* dx, int acc_dx, Reducer& R, float* gW1, float* gb1, float* gW2, float* gb2,
                     hipStream_t st) {
-    const int grid = grid_for(m, 1, bwd_waves(d));
-    const int stride = 2 * d * d + 2 * d;
     float* partial = nullptr;
-    {
-        const int rc = R.take(grid, stride, 4, &partial);
-        if (rc) return rc;
-    }
-#define CALL(DD)                                                                                                       \
-    {                                                                                                                  \
-        const size_t lds = 4 * wimg_bytes(DD) + bwd_waves(DD) * 16 * (DD + 4) * sizeof(float);        \
-        const hipError_t e_ = allow_lds(nmlp2_bwd_kernel<DD>, lds);                                                    \
-        if (e_ != hipSuccess) return (int)e_;                                                                          \
-        hipLaunchKernelGGL((nmlp2_bwd_kernel<DD>), dim3(grid), dim3(64 * bwd_waves(DD)), lds, st, x, m, W1, b1, W2, b2, dy, 0, \
-                           dx, partial, stride, acc_dx);                                                               \
-    }
-    NARROW_DISPATCH(d, CALL)
-#undef CALL
-    PAMNET_LAUNCH_CHECK();
+    TRY(R.take(bwd_row_grid(m, d), nmlp2_bwd_stride(d), 4, &partial));
+    TRY(narrow_rows::mlp2_bwd(d, x, m, W1, b1, W2, b2, dy, 0, dx, partial, acc_dx, st));
     SegTable& T = R.T;
     T.mat(gW1, 0, d, d, d, d);
     T.mat(gW2, d * d, d, d, d, d);
@@ -255,31 +154,32 @@ int launch_mlp2_bwd(int d, const float* x, int64_t m, const float* W1, const flo
     return PAMNET_OK;
 }
 
-// one bias-free projection block of the edge-side Q = rbf [W_0 | W_1 | W_2 | W_3]^T: dW_k and (blocks whose gradient is the
-// pre-activation gradient of a biased layer) the bias gradient = column sums of dQ_k; d rbf accumulated
-int launch_qblock_bwd(int d, const float* x, int64_t m, const float* W, int ldw, const float* dy, int64_t lddy, float* dx,
-                      int accumulate, float* partial, int stride, hipStream_t st) {
-    const int grid = grid_for(m, 1, lin_bwd_waves(d));
-#define CALL(DD)                                                                                                        \
-    {                                                                                                                   \
-        const size_t lds = 2 * wimg_bytes(DD) + lin_bwd_waves(DD) * 16 * (DD + 4) * sizeof(float);     \
-        hipLaunchKernelGGL((nlinear_bwd_kernel<DD>), dim3(grid), dim3(64 * lin_bwd_waves(DD)), lds, st, x, m, W, ldw,   \
-                           (const float*)nullptr, 0, dy, lddy, dx, accumulate, partial, stride);                        \
+// The four bias-free projection blocks of the edge-side Q = rbf [W_0 | W_1 | W_2 | W_3]^T: dW_k and (blocks whose gradient
+// is the pre-activation gradient of a biased layer) the bias gradient = column sums of dQ_k; d rbf accumulated unless
+// `overwrite`.  The blocks' partial rows interleave so that one reduce serves all: gW[k] (row stride ldg[k]), gb[k] nullable.
+int launch_qblocks_bwd(int d, const float* rbf, int64_t m, const float* const* W, const int* ldw, const float* dQ,
+                       float* d_rbf, bool overwrite, Reducer& R, float* const* gW, const int* ldg, float* const* gb,
+                       hipStream_t st) {
+    const int qs = nlinear_bwd_stride(d), stride = nqblock4_bwd_stride(d);
+    float* partial = nullptr;
+    TRY(R.take(bwd_row_grid(m, d), stride, 6, &partial));
+    TRY(narrow_dispatch(d, [&](auto D) {
+        if constexpr (D <= 32) {                              // one pass over the rows for the four blocks (narrow_core.h)
+            return narrow_launch(nqblock4_bwd_kernel<D>, bwd_row_grid(m, D), 64 * lin_bwd_waves(D), nqblock4_bwd_lds<D>(), st,
+                                 rbf, m, W[0], W[1], W[2], W[3], ldw[0], ldw[1], ldw[2], ldw[3], dQ, 4 * D, d_rbf,
+                                 overwrite ? 0 : 1, partial, stride);
+        } else {
+            for (int b = 0; b < 4; ++b)
+                TRY(narrow_rows::linear_bwd(D, rbf, m, W[b], ldw[b], nullptr, 0, dQ + b * D, 4 * D, d_rbf,
+                                            (overwrite && b == 0) ? 0 : 1, partial + b * qs, stride, st));
+            return PAMNET_OK;
+        }
+    }));
+    SegTable& T = R.T;
+    for (int b = 0; b < 4; ++b) {
+        T.mat(gW[b], b * qs, d, d, d, ldg[b]);
+        T.vec(gb[b], b * qs + d * d, d);
     }
-    NARROW_DISPATCH(d, CALL)
-#undef CALL
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
-}
-
-int launch_gate_bwd(int d, const float* P, const float* Q, const int32_t* tgt, const int32_t* src, const float* bji,
-                    const float* bkj, int64_t m, const float* g_ji, const float* g_nb, float* dz, float* dQ, hipStream_t st) {
-    const int grid = ew_grid(m * (d / 4));
-#define CALL(DD) \
-    hipLaunchKernelGGL((nlocal_gate_bwd_kernel<DD>), dim3(grid), dim3(256), 0, st, P, Q, tgt, src, bji, bkj, m, g_ji, g_nb, dz, dQ, 0);
-    NARROW_DISPATCH(d, CALL)
-#undef CALL
-    PAMNET_LAUNCH_CHECK();
     return PAMNET_OK;
 }
 
@@ -288,9 +188,12 @@ inline int64_t up64(int64_t v) { return (v + 63) & ~(int64_t)63; }
 
 struct Lay {
     int64_t n, eg, el, tp, d;
-    // saved, per layer pair
-    int64_t g_x1, g_P, g_x2, g_H0, g_R1, g_R2, g_R3, g_T, g_O;
-    int64_t l_x1, l_P, l_x2, l_H0, l_R1, l_R2, l_R3, l_T, l_O, l_Q, l_mji, l_mnb, l_mother, l_s;
+    // saved, per layer pair (g_t / l_t: what the tail chain of the global / local layer reads and saves)
+    struct Tail {
+        int64_t x2, H0, R1, R2, R3, T, O;
+    };
+    int64_t g_x1, g_P, l_x1, l_P, l_Q, l_mji, l_mnb, l_mother, l_s;
+    Tail g_t, l_t;
     int64_t pair;
     // temp
     int64_t t_msg, t_dz, t_ds, t_dQ, t_dzl, t_dmm, t_dmnb, t_dpi, t_dpj, t_dx2, t_dresx, t_gx0, t_gx1, t_partial, t_pack, temp;
@@ -307,10 +210,11 @@ Lay make_layout(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t d, int64_
         return at;
     };
     const int64_t nd = n * d;
-    L.g_x1 = take(nd), L.g_P = take(2 * nd), L.g_x2 = take(nd), L.g_H0 = take(nd), L.g_R1 = take(nd), L.g_R2 = take(nd);
-    L.g_R3 = take(nd), L.g_T = take(nd), L.g_O = take(nd);
-    L.l_x1 = take(nd), L.l_P = take(4 * nd), L.l_x2 = take(nd), L.l_H0 = take(nd), L.l_R1 = take(nd), L.l_R2 = take(nd);
-    L.l_R3 = take(nd), L.l_T = take(nd), L.l_O = take(nd);
+    auto take_tail = [&](Lay::Tail& t) {
+        t.x2 = take(nd), t.H0 = take(nd), t.R1 = take(nd), t.R2 = take(nd), t.R3 = take(nd), t.T = take(nd), t.O = take(nd);
+    };
+    L.g_x1 = take(nd), L.g_P = take(2 * nd), take_tail(L.g_t);
+    L.l_x1 = take(nd), L.l_P = take(4 * nd), take_tail(L.l_t);
     L.l_Q = take(4 * el * d), L.l_mji = take(el * d), L.l_mnb = take(el * d), L.l_mother = take(el * d), L.l_s = take(tp * d);
     L.pair = o;
     o = 0;
@@ -320,9 +224,10 @@ Lay make_layout(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t d, int64_
     L.t_dmm = take(el * d), L.t_dmnb = take(el * d), L.t_dpi = take(2 * nd), L.t_dpj = take(2 * nd);
     L.t_dx2 = take(nd), L.t_dresx = take(nd), L.t_gx0 = take(nd), L.t_gx1 = take(nd);
     const int64_t chain = (int64_t)chain_grid(n) * tail_stride((int)d);
-    const int64_t pre = (int64_t)chain_grid(n) * (5 * d * d + d);
-    const int64_t erow = (int64_t)EROW_BLOCKS * (2 * d * d + 2 * d);
-    const int64_t qb = 4 * (int64_t)EROW_BLOCKS * (d * d + d);
+    const int64_t pre = (int64_t)chain_grid(n) * npre_bwd_stride((int)d, NPB);
+    const int64_t erow = (int64_t)NARROW_BLOCKS * nmlp2_bwd_stride((int)d);
+    const int64_t qb = (int64_t)NARROW_BLOCKS * nqblock4_bwd_stride((int)d);
+    static_assert(nglobal_bwd_stride(64) <= nmlp2_bwd_stride(64), "the global row kernel's rows fit an `erow`");
     // every backward kernel of a layer pair keeps its partial rows until the pair's reductions run (Reducer): two chain
     // tails, two heads, the global row kernel, the triplet / pair MLP and the four projection blocks
     const int64_t pf = 2 * (chain + 64) + 2 * (pre + 64) + 2 * (erow + 64) + (qb + 64);
@@ -369,17 +274,28 @@ int pack_all(int d, int64_t n_layer, const float* const* gparams, const float* c
         set(L_Q, l[ps::L_WJI] + 2 * d, 3 * d), set(L_Q + 1, l[ps::L_WKJ] + 2 * d, 3 * d);
         set(L_Q + 2, l[ps::L_WLR], d), set(L_Q + 3, l[ps::L_WLO], d);
         float4* dst = reinterpret_cast<float4*>(out + k * 2 * PACK_SLOTS * (int64_t)d * d);
-#define CALL(DD) hipLaunchKernelGGL((npack_kernel<DD>), dim3(PACK_SLOTS, 2), dim3(256), 0, st, J, dst);
-        NARROW_DISPATCH(d, CALL)
-#undef CALL
-        PAMNET_LAUNCH_CHECK();
+        TRY(narrow_dispatch(d, [&](auto D) { return narrow_launch(npack_kernel<D>, dim3(PACK_SLOTS, 2), 256, 0, st, J, dst); }));
     }
     return PAMNET_OK;
 }
 
-inline void tail_fwd_params(NTailFwd& t, const float* const* tp, const Images& im, int64_t pair, int slot0) {
+// the tail chain of one layer: parameters `tp` (the table's tail block), images from slot0 on, saved tensors at S + o.*
+inline NTailFwd tail_fwd_params(const float* const* tp, const Images& im, int64_t pair, int slot0, float* S, const Lay::Tail& o) {
+    NTailFwd t = {};
     for (int i = 0; i < 10; ++i) t.img[i] = im.at(pair, slot0 + i, 0), t.b[i] = tp[ps::T_B + i];
     t.w_out = tp[ps::T_WOUT], t.b_out = tp[ps::T_BOUT], t.w_att = tp[ps::T_WATT];
+    t.x2 = S + o.x2, t.H0 = S + o.H0, t.R1 = S + o.R1, t.R2 = S + o.R2, t.R3 = S + o.R3, t.T = S + o.T, t.O = S + o.O;
+    return t;
+}
+
+inline NTailBwd tail_bwd_params(const float* const* tp, const Images& im, int64_t pair, int slot0, const float* S,
+                                const Lay::Tail& o) {
+    NTailBwd t = {};
+    for (int i = 0; i < 10; ++i)
+        t.img[i] = im.at(pair, slot0 + i, 0), t.imgt[i] = im.at(pair, slot0 + i, 1), t.b[i] = tp[ps::T_B + i];
+    t.w_out = tp[ps::T_WOUT], t.w_att = tp[ps::T_WATT];
+    t.x2 = S + o.x2, t.H0 = S + o.H0, t.R1 = S + o.R1, t.R2 = S + o.R2, t.R3 = S + o.R3, t.T = S + o.T, t.O = S + o.O;
+    return t;
 }
 
 }  // namespace
@@ -408,7 +324,7 @@ int narrow_stack::layout(int64_t n, int64_t eg, int64_t el, int64_t tp, int64_t 
     if (!width_ok(d)) return PAMNET_EINVAL;
     if (!layout) return PAMNET_ENULL;
     const Lay L = make_layout(n, eg, el, tp, d);
-    layout[0] = L.pair, layout[1] = L.g_R3, layout[2] = L.l_R3;
+    layout[0] = L.pair, layout[1] = L.g_t.R3, layout[2] = L.l_t.R3;
     return PAMNET_OK;
 }
 
@@ -438,16 +354,14 @@ int narrow_stack::fwd(const int64_t* sizes, const int32_t* const* graph_idx, int
             p.x = x, p.img1 = im.at(k, G_W1, 0), p.b1 = g[ps::G_BX1], p.nb = 2, p.imgp[0] = im.at(k, G_P, 0), p.imgp[1] = im.at(k, G_P + 1, 0);
             p.x1 = S + L.g_x1, p.P = S + L.g_P, p.m = n;
             TRY(launch_pre_fwd(D, p, st));
-            TRY(launch_global_fwd(D, e_g, eg, ix.g_row, ix.g_col, S + L.g_P, g[ps::G_WM] + 2 * D, 3 * D, g[ps::G_BM], g[ps::G_WEA], D,
-                                  temp + L.t_msg, st));
-            TRY(pamnet_segment_sum_f32(S + L.g_x2, S + L.g_x1, temp + L.t_msg, nullptr, nullptr, nullptr, nullptr, ix.g_ptr, n,
+            TRY(narrow_rows::global_fwd(D, e_g, eg, ix.g_row, ix.g_col, S + L.g_P, g[ps::G_WM] + 2 * D, 3 * D, g[ps::G_BM],
+                                        g[ps::G_WEA], D, temp + L.t_msg, st));
+            TRY(pamnet_segment_sum_f32(S + L.g_t.x2, S + L.g_x1, temp + L.t_msg, nullptr, nullptr, nullptr, nullptr, ix.g_ptr, n,
                                        d, stream));
-            NTailFwd t = {};
-            tail_fwd_params(t, g + ps::G_TAIL, im, k, G_TAIL);
-            t.x2 = S + L.g_x2, t.res_x = x, t.H0 = S + L.g_H0, t.R1 = S + L.g_R1, t.R2 = S + L.g_R2, t.R3 = S + L.g_R3;
-            t.T = S + L.g_T, t.O = S + L.g_O, t.out = outs + (2 * k) * n, t.att = atts + (2 * k) * n, t.m = n;
+            NTailFwd t = tail_fwd_params(g + ps::G_TAIL, im, k, G_TAIL, S, L.g_t);
+            t.res_x = x, t.out = outs + (2 * k) * n, t.att = atts + (2 * k) * n, t.m = n;
             TRY(launch_tail_fwd(D, t, st));
-            x = S + L.g_R3;
+            x = S + L.g_t.R3;
         }
         // ---------------- local layer
         {
@@ -461,23 +375,20 @@ int narrow_stack::fwd(const int64_t* sizes, const int32_t* const* graph_idx, int
             TRY(launch_pre_fwd(D, q, st));
             TRY(pamnet_narrow_local_gate_fwd_f32(S + L.l_P, S + L.l_Q, ix.l_row, ix.l_col, l[ps::L_BJI], l[ps::L_BKJ], el, d, S + L.l_mji,
                                                  S + L.l_mnb, stream));
-            TRY(launch_mlp2_fwd(D, e_sbf, tp, l[ps::L_WS1], l[ps::L_BS1], l[ps::L_WS2], l[ps::L_BS2], S + L.l_s, st));
+            TRY(narrow_rows::mlp2_fwd(D, e_sbf, tp, l[ps::L_WS1], l[ps::L_BS1], l[ps::L_WS2], l[ps::L_BS2], 0, nullptr, S + L.l_s,
+                                      st));
             TRY(pamnet_segment_sum_f32(S + L.l_mother, nullptr, S + L.l_mnb, ix.tp_col, S + L.l_s, nullptr, nullptr, ix.tp_ptr,
                                        el, d, stream));
-            if (el > 0) {
-                hipLaunchKernelGGL(nlocal_msg_fwd_kernel, dim3(ew_grid(el * (d / 4))), dim3(256), 0, st,
-                                   (const float4*)(S + L.l_Q), (const float4*)(S + L.l_mji), (const float4*)(S + L.l_mother),
-                                   el, (int)(d / 4), (float4*)(temp + L.t_msg));
-                PAMNET_LAUNCH_CHECK();
-            }
-            TRY(pamnet_segment_sum_f32(S + L.l_x2, S + L.l_x1, temp + L.t_msg, nullptr, nullptr, nullptr, nullptr, ix.l_ptr, n,
+            if (el > 0)
+                TRY(narrow_launch(nlocal_msg_fwd_kernel, ew_grid(el * (d / 4)), 256, 0, st, (const float4*)(S + L.l_Q),
+                                  (const float4*)(S + L.l_mji), (const float4*)(S + L.l_mother), el, d / 4,
+                                  (float4*)(temp + L.t_msg)));
+            TRY(pamnet_segment_sum_f32(S + L.l_t.x2, S + L.l_x1, temp + L.t_msg, nullptr, nullptr, nullptr, nullptr, ix.l_ptr, n,
                                        d, stream));
-            NTailFwd t = {};
-            tail_fwd_params(t, l + ps::L_TAIL, im, k, L_TAIL);
-            t.x2 = S + L.l_x2, t.res_x = x, t.H0 = S + L.l_H0, t.R1 = S + L.l_R1, t.R2 = S + L.l_R2, t.R3 = S + L.l_R3;
-            t.T = S + L.l_T, t.O = S + L.l_O, t.out = outs + (2 * k + 1) * n, t.att = atts + (2 * k + 1) * n, t.m = n;
+            NTailFwd t = tail_fwd_params(l + ps::L_TAIL, im, k, L_TAIL, S, L.l_t);
+            t.res_x = x, t.out = outs + (2 * k + 1) * n, t.att = atts + (2 * k + 1) * n, t.m = n;
             TRY(launch_tail_fwd(D, t, st));
-            x = S + L.l_R3;
+            x = S + L.l_t.R3;
         }
     }
     return PAMNET_OK;
@@ -512,25 +423,21 @@ int narrow_stack::bwd(const int64_t* sizes, const int32_t* const* graph_idx, int
         float* const* gg = ggrads + k * ps::G_COUNT;
         float* const* lg = lgrads + k * ps::L_COUNT;
         const bool first = k == n_layer - 1;                 // first layer pair to be differentiated: overwrite d e_*
-        const float* x_glob = k == 0 ? x0 : saved + (k - 1) * L.pair + L.l_R3;       // input of global layer k
-        const float* x_loc = S + L.g_R3;                                              // input of local layer k
+        const float* x_glob = k == 0 ? x0 : saved + (k - 1) * L.pair + L.l_t.R3;       // input of global layer k
+        const float* x_loc = S + L.g_t.R3;                                              // input of local layer k
         // ---------------- local layer
         {
-            NTailBwd t = {};
-            for (int i = 0; i < 10; ++i) t.img[i] = im.at(k, L_TAIL + i, 0), t.imgt[i] = im.at(k, L_TAIL + i, 1), t.b[i] = l[ps::L_TAIL + ps::T_B + i];
-            t.w_out = l[ps::L_TAIL + ps::T_WOUT], t.w_att = l[ps::L_TAIL + ps::T_WATT];
-            t.x2 = S + L.l_x2, t.H0 = S + L.l_H0, t.R1 = S + L.l_R1, t.R2 = S + L.l_R2, t.R3 = S + L.l_R3, t.T = S + L.l_T;
-            t.O = S + L.l_O, t.g_x = g_x, t.g_out = d_outs + (2 * k + 1) * n, t.g_att = d_atts + (2 * k + 1) * n;
+            NTailBwd t = tail_bwd_params(l + ps::L_TAIL, im, k, L_TAIL, S, L.l_t);
+            t.g_x = g_x, t.g_out = d_outs + (2 * k + 1) * n, t.g_att = d_atts + (2 * k + 1) * n;
             t.d_x2 = d_x2, t.d_resx = d_resx, t.m = n;
             float* const* lt = lg + ps::L_TAIL;
             TRY(launch_tail_bwd(D, t, lt, lt + ps::T_B, lt[ps::T_WOUT], lt[ps::T_BOUT], lt[ps::T_WATT], R, st));
             // x2 = x1 + sum m,  m = Q_3 (m_ji + m_other)
             float* dQ = temp + L.t_dQ;
             float* dmm = temp + L.t_dmm;
-            hipLaunchKernelGGL(nlocal_msg_bwd_kernel, dim3(ew_grid(el * (d / 4))), dim3(256), 0, st, (const float4*)d_x2,
-                               ix.l_row, (const float4*)(S + L.l_Q), (const float4*)(S + L.l_mji),
-                               (const float4*)(S + L.l_mother), el, (int)(d / 4), (float4*)dQ, (float4*)dmm);
-            PAMNET_LAUNCH_CHECK();
+            TRY(narrow_launch(nlocal_msg_bwd_kernel, ew_grid(el * (d / 4)), 256, 0, st, (const float4*)d_x2, ix.l_row,
+                              (const float4*)(S + L.l_Q), (const float4*)(S + L.l_mji), (const float4*)(S + L.l_mother), el,
+                              d / 4, (float4*)dQ, (float4*)dmm));
             // m_other[r] = sum_{q in row r} m_nb[col q] * s[q]
             float* ds = temp + L.t_ds;
             float* dmnb = temp + L.t_dmnb;
@@ -540,45 +447,19 @@ int narrow_stack::bwd(const int64_t* sizes, const int32_t* const* graph_idx, int
                                 lg[ps::L_WS1], lg[ps::L_BS1], lg[ps::L_WS2], lg[ps::L_BS2], st));
             // gates: dz_l [el, 2d] and dQ blocks 0..2 (block 3 is already there)
             float* dzl = temp + L.t_dzl;
-            TRY(launch_gate_bwd(D, S + L.l_P, S + L.l_Q, ix.l_row, ix.l_col, l[ps::L_BJI], l[ps::L_BKJ], el, dmm, dmnb, dzl, dQ, st));
+            TRY(narrow_rows::local_gate_bwd(D, S + L.l_P, S + L.l_Q, ix.l_row, ix.l_col, l[ps::L_BJI], l[ps::L_BKJ], el, dmm, dmnb,
+                                            dzl, dQ, 0, st));
             // node side: d P_i over the edges into i, d P_j over the edges out of j
             float* dpi = temp + L.t_dpi;
             float* dpj = temp + L.t_dpj;
             TRY(pamnet_segment_sum_f32(dpi, nullptr, dzl, nullptr, nullptr, nullptr, nullptr, ix.l_ptr, n, 2 * d, stream));
             TRY(pamnet_segment_sum_f32(dpj, nullptr, dzl, nullptr, nullptr, nullptr, ix.lT_perm, ix.lT_ptr, n, 2 * d, stream));
-            // edge side: the four projection blocks of Q; their partial rows interleave so that one reduce serves all
+            // edge side: the four projection blocks of Q (d b_ji, d b_kj = column sums of d z_ji, d z_kj)
             const float* Wq[4] = {l[ps::L_WJI] + 2 * D, l[ps::L_WKJ] + 2 * D, l[ps::L_WLR], l[ps::L_WLO]};
+            float* const gWq[4] = {lg[ps::L_WJI] + 2 * D, lg[ps::L_WKJ] + 2 * D, lg[ps::L_WLR], lg[ps::L_WLO]};
+            float* const gbq[4] = {lg[ps::L_BJI], lg[ps::L_BKJ], nullptr, nullptr};
             const int ldq[4] = {3 * D, 3 * D, D, D};
-            const int qs = D * D + D;
-            float* qpart = nullptr;
-            TRY(R.take(grid_for(el, 1, lin_bwd_waves(D)), 4 * qs, 6, &qpart));
-            if (D <= 32) {                                    // one pass over the rows for the four blocks (narrow_core.h)
-                const int qgrid = grid_for(el, 1, lin_bwd_waves(D));
-#define CALL(DD)                                                                                                        \
-    {                                                                                                                   \
-        const size_t lds = 4 * wimg_bytes(DD) + lin_bwd_waves(DD) * 16 * (DD + 4) * sizeof(float);                      \
-        const size_t need = 4 * (size_t)qs * sizeof(float);                                                             \
-        hipLaunchKernelGGL((nqblock4_bwd_kernel<DD>), dim3(qgrid), dim3(64 * lin_bwd_waves(DD)), lds > need ? lds : need, st, \
-                           rbf_e, el, Wq[0], Wq[1], Wq[2], Wq[3], ldq[0], ldq[1], ldq[2], ldq[3], dQ, (int64_t)(4 * D), d_rbf, \
-                           first ? 0 : 1, qpart, 4 * qs);                                                               \
-    }
-                if (D == 16) CALL(16) else CALL(32)
-#undef CALL
-                PAMNET_LAUNCH_CHECK();
-            } else {
-                for (int b = 0; b < 4; ++b)
-                    TRY(launch_qblock_bwd(D, rbf_e, el, Wq[b], ldq[b], dQ + b * D, 4 * D, d_rbf, (first && b == 0) ? 0 : 1,
-                                          qpart + b * qs, 4 * qs, st));
-            }
-            {
-                SegTable& T = R.T;
-                T.mat(lg[ps::L_WJI] + 2 * D, 0 * qs, D, D, D, 3 * D);
-                T.vec(lg[ps::L_BJI], 0 * qs + D * D, D);                 // d b_ji = column sums of d z_ji
-                T.mat(lg[ps::L_WKJ] + 2 * D, 1 * qs, D, D, D, 3 * D);
-                T.vec(lg[ps::L_BKJ], 1 * qs + D * D, D);
-                T.mat(lg[ps::L_WLR], 2 * qs, D, D, D, D);
-                T.mat(lg[ps::L_WLO], 3 * qs, D, D, D, D);
-            }
+            TRY(launch_qblocks_bwd(D, rbf_e, el, Wq, ldq, dQ, d_rbf, first, R, gWq, ldq, gbq, st));
             NPreBwd p = {};
             p.x = x_loc, p.x1 = S + L.l_x1, p.img1 = im.at(k, L_W1, 0), p.img1t = im.at(k, L_W1, 1), p.b1 = l[ps::L_BX1], p.nb = 4, p.m = n;
             for (int b = 0; b < 4; ++b) p.imgpt[b] = im.at(k, L_P + b, 1);
@@ -591,11 +472,8 @@ int narrow_stack::bwd(const int64_t* sizes, const int32_t* const* graph_idx, int
         }
         // ---------------- global layer
         {
-            NTailBwd t = {};
-            for (int i = 0; i < 10; ++i) t.img[i] = im.at(k, G_TAIL + i, 0), t.imgt[i] = im.at(k, G_TAIL + i, 1), t.b[i] = g[ps::G_TAIL + ps::T_B + i];
-            t.w_out = g[ps::G_TAIL + ps::T_WOUT], t.w_att = g[ps::G_TAIL + ps::T_WATT];
-            t.x2 = S + L.g_x2, t.H0 = S + L.g_H0, t.R1 = S + L.g_R1, t.R2 = S + L.g_R2, t.R3 = S + L.g_R3, t.T = S + L.g_T;
-            t.O = S + L.g_O, t.g_x = gx[0], t.g_out = d_outs + (2 * k) * n, t.g_att = d_atts + (2 * k) * n;
+            NTailBwd t = tail_bwd_params(g + ps::G_TAIL, im, k, G_TAIL, S, L.g_t);
+            t.g_x = gx[0], t.g_out = d_outs + (2 * k) * n, t.g_att = d_atts + (2 * k) * n;
             t.d_x2 = d_x2, t.d_resx = d_resx, t.m = n;
             float* const* gt = gg + ps::G_TAIL;
             TRY(launch_tail_bwd(D, t, gt, gt + ps::T_B, gt[ps::T_WOUT], gt[ps::T_BOUT], gt[ps::T_WATT], R, st));
