@@ -996,7 +996,8 @@ struct PreBwd {
 // by plane, four rows at a time, a local layer's four planes of degree ~2 were ~20 of them in a row ahead of the chain.  Here the
 // row ranges of all planes are one request (gather_begin: issued ahead of the tile's other loads), then every step requests U rows
 // of every plane at once, with the permutation entries of the NEXT step in flight beside them: 2 + ceil(max degree / U) round
-// trips.  The additions of a plane are in CSR order as before (same bits as pamnet_segment_sum_multi_f32).
+// trips.  The additions of a plane are in CSR order as before: the bits of pamnet_segment_sum_multi_f32, which adds a row's entries
+// in that order too (tests/test_hip_node_chain.py compares the two launches).
 constexpr int GU = 4;                          // rows in flight per plane and step
 struct GatherState {
     int q[4], q1[4];

@@ -233,46 +233,29 @@ struct MultiSeg {
     const int32_t* ptr[4];
 };
 __global__ __launch_bounds__(256) void segment_sum_multi_kernel(MultiSeg js, int64_t rows) {
-    constexpr int LPR = 32, SPLIT = 4, SLOTS = 8, RPB = 2;
-    __shared__ float4 red[SLOTS][LPR];
+    // One group of 32 lanes per row; the row's entries are added one after the other in CSR order -- the order of the chain
+    // launches that form such planes themselves (node_tail.hip gather_finish), so that a plane has the same bits whichever
+    // launch plan made it -- with U rows of A in flight: the loads of a batch are independent, only the additions are a chain.
+    constexpr int LPR = 32, RPB = 8, U = 16;
     float4* __restrict__ out = js.out[blockIdx.y];
     const float4* __restrict__ A = js.A[blockIdx.y];
     const int32_t* __restrict__ perm = js.perm[blockIdx.y];
     const int32_t* __restrict__ ptr = js.ptr[blockIdx.y];
     const int c = threadIdx.x % LPR;
-    const int slot = threadIdx.x / LPR;
-    const int part = slot % SPLIT, rsub = slot / SPLIT;
-    for (int64_t r0 = (int64_t)blockIdx.x * RPB; r0 < rows; r0 += (int64_t)gridDim.x * RPB) {
-        const int64_t r = r0 + rsub;
-        float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, s2 = s0, s3 = s0;
-        if (r < rows) {
-            const int64_t beg = ptr[r], end = ptr[r + 1];
-            const int64_t per = (end - beg + SPLIT - 1) / SPLIT;
-            int64_t q = beg + part * per;
-            const int64_t stop = q + per < end ? q + per : end;
-            if (perm) {
-                for (; q + 4 <= stop; q += 4) {
-                    const int64_t k0 = perm[q], k1 = perm[q + 1], k2 = perm[q + 2], k3 = perm[q + 3];
-                    acc4(s0, A[k0 * LPR + c]); acc4(s1, A[k1 * LPR + c]); acc4(s2, A[k2 * LPR + c]); acc4(s3, A[k3 * LPR + c]);
-                }
-                for (; q < stop; ++q) acc4(s0, A[(int64_t)perm[q] * LPR + c]);
-            } else {
-                for (; q + 4 <= stop; q += 4) {
-                    acc4(s0, A[q * LPR + c]); acc4(s1, A[(q + 1) * LPR + c]); acc4(s2, A[(q + 2) * LPR + c]); acc4(s3, A[(q + 3) * LPR + c]);
-                }
-                for (; q < stop; ++q) acc4(s0, A[q * LPR + c]);
-            }
-            acc4(s0, s1); acc4(s2, s3); acc4(s0, s2);
-        }
-        red[slot][c] = s0;
-        __syncthreads();
-        if (part == 0 && r < rows) {
-            float4 t = red[rsub * SPLIT][c];
+    const int rsub = threadIdx.x / LPR;
+    for (int64_t r = (int64_t)blockIdx.x * RPB + rsub; r < rows; r += (int64_t)gridDim.x * RPB) {
+        const int64_t end = ptr[r + 1];
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int64_t q = ptr[r]; q < end; q += U) {
+            float4 a[U];
 #pragma unroll
-            for (int p = 1; p < SPLIT; ++p) acc4(t, red[rsub * SPLIT + p][c]);
-            out[r * LPR + c] = t;
+            for (int u = 0; u < U; ++u)
+                if (q + u < end) a[u] = A[(perm ? (int64_t)perm[q + u] : q + u) * LPR + c];
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (q + u < end) acc4(s, a[u]);
         }
-        __syncthreads();
+        out[r * LPR + c] = s;
     }
 }
 
@@ -294,7 +277,8 @@ __global__ __launch_bounds__(256) void gather_mul2_kernel(float4* __restrict__ o
 }  // namespace
 
 // njobs <= 4 plain segment sums out_j[r,:] = sum_{q in [ptr_j[r], ptr_j[r+1])} A_j[perm_j ? perm_j[q] : q, :], d = 128.
-// Summation order inside a row: four contiguous quarters of the segment, added in order (deterministic).
+// Summation order inside a row: its entries one after the other, in CSR order (deterministic; the bits of the planes that
+// pamnet_node_pre_tail_bwd_gather_f32 forms inside its launch).
 extern "C" int pamnet_segment_sum_multi_f32(int64_t njobs, float* const* out, const float* const* A,
                                             const int32_t* const* perm, const int32_t* const* ptr, int64_t rows,
                                             int64_t d, pamnet_stream_t stream) {
@@ -310,7 +294,7 @@ extern "C" int pamnet_segment_sum_multi_f32(int64_t njobs, float* const* out, co
         js.perm[j] = perm[s];
         js.ptr[j] = ptr[s];
     }
-    int64_t grid = ceil_div(rows, 2);
+    int64_t grid = ceil_div(rows, 8);
     if (grid > 256 * 32) grid = 256 * 32;
     hipLaunchKernelGGL(segment_sum_multi_kernel, dim3((unsigned)grid, (unsigned)njobs), dim3(256), 0, as_stream(stream),
                        js, rows);
