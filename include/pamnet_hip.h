@@ -159,6 +159,32 @@ int pamnet_radius_pbc_fill_i32(const float* pos, const double* cell_table, const
                                int64_t n, int64_t n_graphs, float r, int64_t max_neighbors, const int32_t* ptr, int32_t* nbr,
                                float* dist, int32_t* row_of /* nullable */, int64_t cap, pamnet_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Periodic cells below twice the global cutoff: a global graph over ALL images (part of ABI 18: nothing existing changed).
+ * Row i holds every pair (j, n) -- j any atom of i's graph, i itself included, n an integer triple -- with
+ * |pos_i - pos_j - n @ cell| <= r, except the one entry j == i, n == 0; ascending (j, n0, n1, n2).  A multigraph: several edges
+ * between the same two atoms, and from an atom to its own images.  Symmetric as a multiset: (i, j, n) has the reverse (j, i, -n),
+ * with a bitwise equal length (csrc/geom_core.h image_disp: min_image with the image given instead of rounded).
+ *   pamnet_cell_images_i32: cell_table [n_graphs, 18] (pamnet_cell_prepare_f64) -> img_box [n_graphs, 3]: N_k = ceil(cutoff /
+ *     h_k), h_k the perpendicular height along lattice direction k (fp64).  The search tries, per pair, the images
+ *     rint(fractional displacement) + m with |m_k| <= N_k: a superset of those within the cutoff.  ORs 128 into *flag when some
+ *     N_k > 4 (a height below cutoff / 4) or the cell has no heights; that graph's box is then 0 0 0.
+ *   pamnet_radius_img_count/fill_i32: the argument lists of pamnet_radius_pbc_count/fill_i32 with img_box behind cell_table and,
+ *     in the fill, img [cap, 3] int32 behind row_of: the image of every entry, v = pos_row - pos_col - img @ cell (min_image's
+ *     sign).  One wavefront per atom whatever n_graphs says.  max_neighbors never cuts a row (a cut multigraph is not symmetric):
+ *     the count pass ORs 64 into *cap_flag when a row's entries, the query itself counted, exceed it.  Same cap guard and return
+ *     codes as the twins.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int pamnet_cell_images_i32(const double* cell_table, int64_t n_graphs, float cutoff, int32_t* img_box, int32_t* flag,
+                           pamnet_stream_t stream);
+int pamnet_radius_img_count_i32(const float* pos, const double* cell_table, const int32_t* img_box, const int32_t* node_graph,
+                                const int32_t* gptr, int64_t n, int64_t n_graphs, float r, int64_t max_neighbors, int32_t* count,
+                                int32_t* cap_flag, pamnet_stream_t stream);
+int pamnet_radius_img_fill_i32(const float* pos, const double* cell_table, const int32_t* img_box, const int32_t* node_graph,
+                               const int32_t* gptr, int64_t n, int64_t n_graphs, float r, int64_t max_neighbors, const int32_t* ptr,
+                               int32_t* nbr, float* dist, int32_t* row_of /* nullable */, int32_t* img, int64_t cap,
+                               pamnet_stream_t stream);
+
 /* knn: for every query node its k nearest nodes of the same graph (itself included, as torch_cluster.knn does),
  * ordered by (distance, index); then the self entry is dropped and entries with dist > cutoff are masked out:
  * nbr[i*k + s] = neighbour index or -1, dist[i*k + s] = distance.  (models.py:143-150) */
@@ -473,6 +499,29 @@ int pamnet_pos_bwd_pbc_virial_f32(const float* pos, const double* cell_table, co
                                   const int32_t* t_col, const int32_t* t_kind, const int32_t* tt_ptr, const int32_t* tt_perm,
                                   const float* dangle, int64_t tp, double* bond_work, float* dpos, const int32_t* gptr,
                                   int64_t n_graphs, double* atom_work, float* dstrain, pamnet_stream_t stream);
+
+/* The two periodic forms for a graph whose global list holds all images (pamnet_radius_img_fill_i32): the argument lists of
+ * pamnet_pos_bwd_pbc_f32 / pamnet_pos_bwd_pbc_virial_f32 with g_img [eg, 3] behind g_col.  Global edge q is the vector of its
+ * stored image, p_row - p_col - g_img[q] @ cell, in both the row and the transposed loop (there negated); gt_* is the general
+ * transposed list of g_col.  An edge from an atom to its own image cancels in dpos and enters the virial once, through its row.
+ * Local bonds and angles stay minimum-image: the same bond-gradient launch.  dpos of the virial form is bitwise the plain
+ * form's.  Same sums in a fixed order, no atomics, same return codes (part of ABI 18: nothing existing changed). */
+int pamnet_pos_bwd_img_f32(const float* pos, const double* cell_table, const int32_t* node_graph, int64_t n,
+                           const int32_t* g_ptr, const int32_t* g_row, const int32_t* g_col, const int32_t* g_img,
+                           const int32_t* gt_ptr, const int32_t* gt_perm, const float* ddist_g, int64_t eg, const int32_t* l_ptr,
+                           const int32_t* l_row, const int32_t* l_col, const int32_t* lt_ptr, const int32_t* lt_perm,
+                           const float* ddist_l, int64_t el, const int32_t* t_ptr, const int32_t* t_row, const int32_t* t_col,
+                           const int32_t* t_kind, const int32_t* tt_ptr, const int32_t* tt_perm, const float* dangle, int64_t tp,
+                           double* bond_work, float* dpos, pamnet_stream_t stream);
+int pamnet_pos_bwd_img_virial_f32(const float* pos, const double* cell_table, const int32_t* node_graph, int64_t n,
+                                  const int32_t* g_ptr, const int32_t* g_row, const int32_t* g_col, const int32_t* g_img,
+                                  const int32_t* gt_ptr, const int32_t* gt_perm, const float* ddist_g, int64_t eg,
+                                  const int32_t* l_ptr, const int32_t* l_row, const int32_t* l_col, const int32_t* lt_ptr,
+                                  const int32_t* lt_perm, const float* ddist_l, int64_t el, const int32_t* t_ptr,
+                                  const int32_t* t_row, const int32_t* t_col, const int32_t* t_kind, const int32_t* tt_ptr,
+                                  const int32_t* tt_perm, const float* dangle, int64_t tp, double* bond_work, float* dpos,
+                                  const int32_t* gptr, int64_t n_graphs, double* atom_work, float* dstrain,
+                                  pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Attention fusion + per-graph pooling  (models.py:206-224)

@@ -45,6 +45,9 @@ struct OpenDiff {
         return load_pos(pos, a) - load_pos(pos, b);
     }
     __device__ __forceinline__ V3 from(V3 pa, const float* __restrict__ pos, int64_t b) const { return pa - load_pos(pos, b); }
+    // global edge q seen from atom a: its row (towards the column b), its column (towards the row b)
+    __device__ __forceinline__ V3 row_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t) const { return from(pa, pos, b); }
+    __device__ __forceinline__ V3 col_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t) const { return from(pa, pos, b); }
 };
 struct PeriodicDiff {
     const double* __restrict__ table;
@@ -60,6 +63,22 @@ struct PeriodicDiff {
     __device__ __forceinline__ V3 from(V3 pa, const float* __restrict__ pos, int64_t b) const {
         const Disp d = min_image(t, (float)pa.x, (float)pa.y, (float)pa.z, pos[3 * b], pos[3 * b + 1], pos[3 * b + 2]);
         return v3(d.x, d.y, d.z);
+    }
+    __device__ __forceinline__ V3 row_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t) const { return from(pa, pos, b); }
+    __device__ __forceinline__ V3 col_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t) const { return from(pa, pos, b); }
+};
+// A periodic graph whose GLOBAL list holds every image within the cutoff (pamnet_radius_img_fill_i32): global edge q is the vector
+// v_q = p_row - p_col - img[q] @ cell of its stored image, not a rounded one (geom_core.h image_disp).  Seen from its column the
+// edge is -v_q.  Local edges, and so diff / from, stay minimum-image.
+struct ImageDiff : PeriodicDiff {
+    const int32_t* __restrict__ img;
+    __device__ __forceinline__ V3 row_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t q) const {
+        const Disp d = image_disp(t, (float)pa.x, (float)pa.y, (float)pa.z, pos[3 * b], pos[3 * b + 1], pos[3 * b + 2], img, q);
+        return v3(d.x, d.y, d.z);
+    }
+    __device__ __forceinline__ V3 col_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t q) const {
+        const Disp d = image_disp(t, pos[3 * b], pos[3 * b + 1], pos[3 * b + 2], (float)pa.x, (float)pa.y, (float)pa.z, img, q);
+        return v3(-d.x, -d.y, -d.z);
     }
 };
 
@@ -186,7 +205,7 @@ __device__ __forceinline__ void pos_grad(GEOM geom, const int32_t* __restrict__ 
     V3 acc = v3(0.0, 0.0, 0.0);
     V3 vx = v3(0.0, 0.0, 0.0), vy = vx, vz = vx;                  // VIRIAL: rows of the 3 x 3 sum
     for (int q = g_ptr[a] + lane; q < g_ptr[a + 1]; q += 64) {
-        const V3 w = geom.from(pa, pos, g_col[q]);
+        const V3 w = geom.row_edge(pa, pos, g_col[q], q);
         const double r = sqrt(dot(w, w));
         if (r > 0.0) {
             const V3 f = ((double)ddist_g[q] / r) * w;
@@ -201,7 +220,7 @@ __device__ __forceinline__ void pos_grad(GEOM geom, const int32_t* __restrict__ 
     }
     for (int k = gt_ptr[a] + lane; k < gt_ptr[a + 1]; k += 64) {
         const int64_t q = gt_perm[k];
-        const V3 w = geom.from(pa, pos, g_row[q]);
+        const V3 w = geom.col_edge(pa, pos, g_row[q], q);
         const double r = sqrt(dot(w, w));
         if (r > 0.0) acc = acc + ((double)ddist_g[q] / r) * w;
     }
@@ -273,6 +292,22 @@ __global__ __launch_bounds__(256) void pos_grad_pbc_virial_kernel(
     geom.table = cells;
     pos_grad<PeriodicDiff, true>(geom, node_graph, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm,
                                  G, dpos, l_col, atom_work);
+}
+
+// The two periodic forms for a global list over all images: g_img [eg, 3] is the image of every global edge.
+template <bool VIRIAL>
+__global__ __launch_bounds__(256) void pos_grad_img_kernel(
+    const float* __restrict__ pos, const double* __restrict__ cells, const int32_t* __restrict__ node_graph, int64_t n,
+    const int32_t* __restrict__ g_ptr, const int32_t* __restrict__ g_row, const int32_t* __restrict__ g_col,
+    const int32_t* __restrict__ g_img, const int32_t* __restrict__ gt_ptr, const int32_t* __restrict__ gt_perm,
+    const float* __restrict__ ddist_g, const int32_t* __restrict__ l_ptr, const int32_t* __restrict__ l_col,
+    const int32_t* __restrict__ lt_ptr, const int32_t* __restrict__ lt_perm, const double* __restrict__ G,
+    float* __restrict__ dpos, double* __restrict__ atom_work) {
+    ImageDiff geom;
+    geom.table = cells;
+    geom.img = g_img;
+    pos_grad<ImageDiff, VIRIAL>(geom, node_graph, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm, G,
+                                dpos, l_col, atom_work);
 }
 
 // One workgroup of 256 threads per graph g: the threads stride over the atoms gptr[g] .. gptr[g + 1] of atom_work (kept inside
@@ -392,4 +427,73 @@ extern "C" int pamnet_pos_bwd_pbc_virial_f32(const float* pos, const double* cel
         PAMNET_LAUNCH_CHECK();
     }
     return PAMNET_OK;
+}
+
+// Both all-image entry points: atom_work == nullptr is the plain form (the caller has checked its own arguments).
+static int pos_bwd_img(const float* pos, const double* cell_table, const int32_t* node_graph, int64_t n, const int32_t* g_ptr,
+                       const int32_t* g_row, const int32_t* g_col, const int32_t* g_img, const int32_t* gt_ptr,
+                       const int32_t* gt_perm, const float* ddist_g, const int32_t* l_ptr, const int32_t* l_row,
+                       const int32_t* l_col, const int32_t* lt_ptr, const int32_t* lt_perm, const float* ddist_l, int64_t el,
+                       const int32_t* t_ptr, const int32_t* t_row, const int32_t* t_col, const int32_t* t_kind,
+                       const int32_t* tt_ptr, const int32_t* tt_perm, const float* dangle, double* bond_work, float* dpos,
+                       const int32_t* gptr, int64_t n_graphs, double* atom_work, float* dstrain, hipStream_t st) {
+    if (n > 0) {
+        if (el > 0) {
+            hipLaunchKernelGGL(bond_grad_pbc_kernel, dim3(blocks_for(el * 64)), dim3(256), 0, st, pos, cell_table, node_graph,
+                               l_row, l_col, ddist_l, el, t_ptr, t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, bond_work);
+            PAMNET_LAUNCH_CHECK();
+        }
+        if (atom_work)
+            hipLaunchKernelGGL((pos_grad_img_kernel<true>), dim3(blocks_for(n * 64)), dim3(256), 0, st, pos, cell_table, node_graph,
+                               n, g_ptr, g_row, g_col, g_img, gt_ptr, gt_perm, ddist_g, l_ptr, l_col, lt_ptr, lt_perm, bond_work,
+                               dpos, atom_work);
+        else
+            hipLaunchKernelGGL((pos_grad_img_kernel<false>), dim3(blocks_for(n * 64)), dim3(256), 0, st, pos, cell_table, node_graph,
+                               n, g_ptr, g_row, g_col, g_img, gt_ptr, gt_perm, ddist_g, l_ptr, l_col, lt_ptr, lt_perm, bond_work,
+                               dpos, (double*)nullptr);
+        PAMNET_LAUNCH_CHECK();
+    }
+    if (atom_work && n_graphs > 0) {
+        hipLaunchKernelGGL(virial_reduce_kernel, dim3((unsigned)n_graphs), dim3(256), 0, st, atom_work, gptr, n, dstrain);
+        PAMNET_LAUNCH_CHECK();
+    }
+    return PAMNET_OK;
+}
+
+extern "C" int pamnet_pos_bwd_img_f32(const float* pos, const double* cell_table, const int32_t* node_graph, int64_t n,
+                                      const int32_t* g_ptr, const int32_t* g_row, const int32_t* g_col, const int32_t* g_img,
+                                      const int32_t* gt_ptr, const int32_t* gt_perm, const float* ddist_g, int64_t eg,
+                                      const int32_t* l_ptr, const int32_t* l_row, const int32_t* l_col, const int32_t* lt_ptr,
+                                      const int32_t* lt_perm, const float* ddist_l, int64_t el, const int32_t* t_ptr,
+                                      const int32_t* t_row, const int32_t* t_col, const int32_t* t_kind, const int32_t* tt_ptr,
+                                      const int32_t* tt_perm, const float* dangle, int64_t tp, double* bond_work, float* dpos,
+                                      pamnet_stream_t stream) {
+    if (n < 0 || eg < 0 || el < 0 || tp < 0) return PAMNET_EINVAL;
+    if (!pos || !cell_table || !node_graph || !g_ptr || !g_row || !g_col || !g_img || !gt_ptr || !gt_perm || !ddist_g || !l_ptr ||
+        !l_row || !l_col || !lt_ptr || !lt_perm || !ddist_l || !t_ptr || !t_row || !t_col || !t_kind || !tt_ptr || !tt_perm ||
+        !dangle || !bond_work || !dpos)
+        return PAMNET_EINVAL;
+    return pos_bwd_img(pos, cell_table, node_graph, n, g_ptr, g_row, g_col, g_img, gt_ptr, gt_perm, ddist_g, l_ptr, l_row, l_col,
+                       lt_ptr, lt_perm, ddist_l, el, t_ptr, t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, bond_work, dpos, nullptr,
+                       0, nullptr, nullptr, as_stream(stream));
+}
+
+extern "C" int pamnet_pos_bwd_img_virial_f32(const float* pos, const double* cell_table, const int32_t* node_graph, int64_t n,
+                                             const int32_t* g_ptr, const int32_t* g_row, const int32_t* g_col,
+                                             const int32_t* g_img, const int32_t* gt_ptr, const int32_t* gt_perm,
+                                             const float* ddist_g, int64_t eg, const int32_t* l_ptr, const int32_t* l_row,
+                                             const int32_t* l_col, const int32_t* lt_ptr, const int32_t* lt_perm,
+                                             const float* ddist_l, int64_t el, const int32_t* t_ptr, const int32_t* t_row,
+                                             const int32_t* t_col, const int32_t* t_kind, const int32_t* tt_ptr,
+                                             const int32_t* tt_perm, const float* dangle, int64_t tp, double* bond_work, float* dpos,
+                                             const int32_t* gptr, int64_t n_graphs, double* atom_work, float* dstrain,
+                                             pamnet_stream_t stream) {
+    if (n < 0 || eg < 0 || el < 0 || tp < 0 || n_graphs < 0) return PAMNET_EINVAL;
+    if (!pos || !cell_table || !node_graph || !g_ptr || !g_row || !g_col || !g_img || !gt_ptr || !gt_perm || !ddist_g || !l_ptr ||
+        !l_row || !l_col || !lt_ptr || !lt_perm || !ddist_l || !t_ptr || !t_row || !t_col || !t_kind || !tt_ptr || !tt_perm ||
+        !dangle || !bond_work || !dpos || !gptr || !atom_work || !dstrain)
+        return PAMNET_EINVAL;
+    return pos_bwd_img(pos, cell_table, node_graph, n, g_ptr, g_row, g_col, g_img, gt_ptr, gt_perm, ddist_g, l_ptr, l_row, l_col,
+                       lt_ptr, lt_perm, ddist_l, el, t_ptr, t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, bond_work, dpos, gptr,
+                       n_graphs, atom_work, dstrain, as_stream(stream));
 }

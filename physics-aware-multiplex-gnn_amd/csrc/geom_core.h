@@ -68,6 +68,37 @@ __device__ __forceinline__ Disp min_image(const PbcCell& t, const float* __restr
     return min_image(t, pos[3 * a], pos[3 * a + 1], pos[3 * a + 2], pos[3 * b], pos[3 * b + 1], pos[3 * b + 2]);
 }
 
+// ---- all images (a global graph over every image within the cutoff) -------------------------------------------------------
+// The displacement a - b - n @ cell for a GIVEN image n: min_image's statements with the rounding left out, in the same fma
+// order, so with n = nearest_image(a, b) it returns min_image(a, b) bit for bit, and it negates exactly under (a, b, n) ->
+// (b, a, -n).  n holds integers (exact in fp64 up to 2^53; the edge lists store them as int32).
+__device__ __forceinline__ Disp image_disp(const PbcCell& t, float ax, float ay, float az, float bx, float by, float bz, double n0,
+                                           double n1, double n2) {
+    const double dx = (double)ax - (double)bx, dy = (double)ay - (double)by, dz = (double)az - (double)bz;
+    Disp d;
+    d.x = fma(-n2, t.c[6], fma(-n1, t.c[3], fma(-n0, t.c[0], dx)));
+    d.y = fma(-n2, t.c[7], fma(-n1, t.c[4], fma(-n0, t.c[1], dy)));
+    d.z = fma(-n2, t.c[8], fma(-n1, t.c[5], fma(-n0, t.c[2], dz)));
+    return d;
+}
+
+// image_disp with the image read from row q of an edge list's [E, 3] int32 array
+__device__ __forceinline__ Disp image_disp(const PbcCell& t, float ax, float ay, float az, float bx, float by, float bz,
+                                           const int32_t* __restrict__ img, int64_t q) {
+    return image_disp(t, ax, ay, az, bx, by, bz, (double)img[3 * q], (double)img[3 * q + 1], (double)img[3 * q + 2]);
+}
+
+// The image min_image() subtracts: its three rounding statements.  The all-image search centres its box of candidates here.
+__device__ __forceinline__ void nearest_image(const PbcCell& t, float ax, float ay, float az, float bx, float by, float bz,
+                                              double& n0, double& n1, double& n2) {
+    const double dx = (double)ax - (double)bx, dy = (double)ay - (double)by, dz = (double)az - (double)bz;
+    n0 = rint(fma(dz, t.inv[6], fma(dy, t.inv[3], __dmul_rn(dx, t.inv[0]))));
+    n1 = rint(fma(dz, t.inv[7], fma(dy, t.inv[4], __dmul_rn(dx, t.inv[1]))));
+    n2 = rint(fma(dz, t.inv[8], fma(dy, t.inv[5], __dmul_rn(dx, t.inv[2]))));
+}
+
+constexpr int IMG_BOX_MAX = 4;        // largest half-width of the candidate box per lattice direction (9^3 images per pair)
+
 // How a kernel of graph construction turns two atoms into a displacement: open space (the raw difference, the arithmetic
 // the kernels always had) or a periodic cell (the image rule, rounded once to fp32).  bind(): once per thread, for the graph
 // its atoms belong to.

@@ -518,6 +518,76 @@ __global__ __launch_bounds__(256) void radius_wave_pbc_kernel(const float* __res
     radius_wave_search<FILL>(geom, pos, node_graph, gptr, n, r, count, ptr, nbr, dist, cap, row_of, max_nb, cap_flag);
 }
 
+// ---- the radius search over ALL images of a periodic cell (the global graph of cells below twice the cutoff) ---------------
+// Row i: every (j, n), j an atom of i's graph (i itself too) and n an integer triple, with |p_i - p_j - n @ cell| <= r, but for
+// the one entry j == i, n == 0; ascending (j, n0, n1, n2).  Candidates of a pair: n = nearest_image(i, j) + m, |m_k| <= N_k (the
+// graph's row of img_box, pamnet_cell_images_i32) -- a superset of the images within r, the rest fails the distance test.  One
+// wavefront per atom; its lanes take 64 consecutive values of the flat candidate index c = (j - beg) * M + m_lin, M = (2 N0 + 1)
+// (2 N1 + 1)(2 N2 + 1), m_lin row-major in (m0, m1, m2) -- which is ascending (j, n) -- and the survivors keep that order through
+// the prefix population count of the ballot, as in radius_wave_search.  Each lane carries its (j, m_lin) along by adding 64 in
+// mixed radix: no division by M inside the loop.  The length is Periodic::dist's arithmetic on the given image: image_disp rounded
+// once to fp32, then dist3_xyz against the origin; (i, j, n) and (j, i, -n) carry bitwise equal lengths.
+// No row is cut: a multigraph with a cut row is not symmetric.  max_nb > 0 only raises CAP_BIT (count pass) for a row whose hits,
+// the query itself counted as in the twins, exceed it.
+template <bool FILL>
+__global__ __launch_bounds__(256) void radius_img_kernel(const float* __restrict__ pos, const double* __restrict__ cells,
+                                                         const int32_t* __restrict__ img_box,
+                                                         const int32_t* __restrict__ node_graph,
+                                                         const int32_t* __restrict__ gptr, int64_t n, float r,
+                                                         int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
+                                                         int32_t* __restrict__ nbr, float* __restrict__ dist, int64_t cap,
+                                                         int32_t* __restrict__ row_of, int32_t* __restrict__ img, int max_nb,
+                                                         int32_t* __restrict__ cap_flag) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (i >= n) return;                                           // (uniform over the wavefront)
+    const int g = node_graph[i];
+    const int beg = gptr[g], ng = gptr[g + 1] - beg;
+    const PbcCell t = load_cell(cells, g);
+    const int N0 = min(max(img_box[3 * g], 0), IMG_BOX_MAX), N1 = min(max(img_box[3 * g + 1], 0), IMG_BOX_MAX),
+              N2 = min(max(img_box[3 * g + 2], 0), IMG_BOX_MAX);
+    const int W2 = 2 * N2 + 1, W12 = (2 * N1 + 1) * W2, M = (2 * N0 + 1) * W12;            // M <= 729
+    const float xi = pos[3 * i], yi = pos[3 * i + 1], zi = pos[3 * i + 2];
+    int jrel = lane / M, ml = lane % M;                           // this lane's candidate: atom beg + jrel, box entry ml
+    const int dj = 64 / M, dm = 64 % M;
+    const int64_t total = (int64_t)ng * M;
+    int c = 0;
+    const int64_t w0 = FILL ? ptr[i] : 0;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int64_t c0 = 0; c0 < total; c0 += 64) {                  // (uniform over the wavefront)
+        const int j = beg + jrel;
+        float d = 0.f;
+        double n0 = 0.0, n1 = 0.0, n2 = 0.0;
+        bool keep = false;
+        if (jrel < ng) {
+            const float xj = pos[3 * (int64_t)j], yj = pos[3 * (int64_t)j + 1], zj = pos[3 * (int64_t)j + 2];
+            nearest_image(t, xi, yi, zi, xj, yj, zj, n0, n1, n2);
+            const int m0 = ml / W12, rest = ml - m0 * W12, m1 = rest / W2, m2 = rest - m1 * W2;
+            n0 += (double)(m0 - N0), n1 += (double)(m1 - N1), n2 += (double)(m2 - N2);
+            const Disp w = image_disp(t, xi, yi, zi, xj, yj, zj, n0, n1, n2);
+            d = dist3_xyz((float)w.x, (float)w.y, (float)w.z, 0.f, 0.f, 0.f);
+            keep = d <= r && !(j == i && n0 == 0.0 && n1 == 0.0 && n2 == 0.0);
+        }
+        const unsigned long long votes = __ballot(keep);
+        if (FILL && keep) {
+            const int64_t w = w0 + c + __builtin_popcountll(votes & below);
+            if (w < cap) {                                        // cap: see pamnet_radius_fill_i32
+                nbr[w] = j;
+                dist[w] = d;
+                if (row_of) row_of[w] = (int32_t)i;
+                img[3 * w] = (int32_t)n0, img[3 * w + 1] = (int32_t)n1, img[3 * w + 2] = (int32_t)n2;
+            }
+        }
+        c += __builtin_popcountll(votes);
+        jrel += dj, ml += dm;
+        if (ml >= M) ml -= M, ++jrel;
+    }
+    if (!FILL && lane == 0) {
+        count[i] = c;
+        if (max_nb > 0 && c >= max_nb && cap_flag) atomicOr(cap_flag, CAP_BIT);      // (c + the query itself > max_nb)
+    }
+}
+
 // graphs this large on average take the wavefront-per-node form (QM9 molecules: ~18 atoms -> one thread per node)
 constexpr int64_t RADIUS_WAVE_MIN_NODES = 96;
 
@@ -1077,6 +1147,40 @@ __global__ __launch_bounds__(256) void cell_prepare_kernel(const float* __restri
     if (!ok) atomicOr(flag, PBC_BIT);
 }
 
+// One thread per graph: the half-widths of the all-image search's candidate box, N_k = ceil(cutoff / h_k) with h_k = |det| /
+// |a_{k+1} x a_{k+2}| the perpendicular height along lattice direction k, in fp64 from the table's cell.  An image within the
+// cutoff has |f_k - n_k| <= cutoff / h_k for the fractional displacement f, so |rint(f_k) - n_k| <= floor(cutoff / h_k + 1/2) <=
+// N_k: the box holds every image the search must find.  A cell that needs N_k > IMG_BOX_MAX (or has no heights at all) raises
+// PBC_BIT and gets an empty box, so whatever runs before the host reads the flag stays short.
+__global__ __launch_bounds__(256) void cell_images_kernel(const double* __restrict__ table, int64_t n_graphs, double cutoff,
+                                                          int32_t* __restrict__ img_box, int32_t* __restrict__ flag) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_graphs) return;
+    const double* a = table + PBC_ROW * g;
+    double x[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double* u = a + 3 * ((k + 1) % 3);
+        const double* v = a + 3 * ((k + 2) % 3);
+        x[k][0] = u[1] * v[2] - u[2] * v[1];
+        x[k][1] = u[2] * v[0] - u[0] * v[2];
+        x[k][2] = u[0] * v[1] - u[1] * v[0];
+    }
+    const double det = a[0] * x[0][0] + a[1] * x[0][1] + a[2] * x[0][2];
+    int N[3];
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double area = sqrt(x[k][0] * x[k][0] + x[k][1] * x[k][1] + x[k][2] * x[k][2]);
+        const double need = ceil(cutoff / (fabs(det) / area));
+        ok = ok && (need <= (double)IMG_BOX_MAX);             // (NaN compares false)
+        N[k] = ok ? (int)need : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) img_box[3 * g + k] = ok ? N[k] : 0;
+    if (!ok) atomicOr(flag, PBC_BIT);
+}
+
 // ---- transposed triplet / pair row list without a sort -----------------------------------------------------------------
 // For source bond q = (k -> j) the rows that gather it (what pamnet_csr_from_keys_i32 returns for keys = tp_idx) are: one
 // triplet row of every bond e leaving j towards an atom other than k (row = e's first row + q's rank among e's triplets),
@@ -1389,6 +1493,44 @@ extern "C" int pamnet_radius_pbc_fill_i32(const float* pos, const double* cell_t
     else
         hipLaunchKernelGGL((radius_pbc_kernel<true>), dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), pos, cell_table,
                            node_graph, gptr, n, r, (int32_t*)nullptr, ptr, nbr, dist, cap, row_of, mx, (int32_t*)nullptr);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
+extern "C" int pamnet_cell_images_i32(const double* cell_table, int64_t n_graphs, float cutoff, int32_t* img_box, int32_t* flag,
+                                      pamnet_stream_t stream) {
+    if (n_graphs < 0 || !(cutoff > 0.f) || !(cutoff <= 3.0e38f)) return PAMNET_EINVAL;      // (NaN and inf refused)
+    if (n_graphs == 0) return PAMNET_OK;
+    if (!cell_table || !img_box || !flag) return PAMNET_ENULL;
+    hipLaunchKernelGGL(cell_images_kernel, dim3(blocks_for(n_graphs)), dim3(256), 0, as_stream(stream), cell_table, n_graphs,
+                       (double)cutoff, img_box, flag);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
+extern "C" int pamnet_radius_img_count_i32(const float* pos, const double* cell_table, const int32_t* img_box,
+                                           const int32_t* node_graph, const int32_t* gptr, int64_t n, int64_t n_graphs, float r,
+                                           int64_t max_neighbors, int32_t* count, int32_t* cap_flag, pamnet_stream_t stream) {
+    if (n < 0 || n_graphs < 0 || max_neighbors < 0 || max_neighbors > 0x7fffffff) return PAMNET_EINVAL;
+    if (n == 0) return PAMNET_OK;
+    if (!pos || !cell_table || !img_box || !node_graph || !gptr || !count) return PAMNET_ENULL;
+    hipLaunchKernelGGL((radius_img_kernel<false>), dim3(blocks_for(n, 4)), dim3(256), 0, as_stream(stream), pos, cell_table,
+                       img_box, node_graph, gptr, n, r, count, (const int32_t*)nullptr, (int32_t*)nullptr, (float*)nullptr,
+                       (int64_t)0, (int32_t*)nullptr, (int32_t*)nullptr, (int)max_neighbors, cap_flag);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
+extern "C" int pamnet_radius_img_fill_i32(const float* pos, const double* cell_table, const int32_t* img_box,
+                                          const int32_t* node_graph, const int32_t* gptr, int64_t n, int64_t n_graphs, float r,
+                                          int64_t max_neighbors, const int32_t* ptr, int32_t* nbr, float* dist, int32_t* row_of,
+                                          int32_t* img, int64_t cap, pamnet_stream_t stream) {
+    if (n < 0 || cap < 0 || n_graphs < 0 || max_neighbors < 0 || max_neighbors > 0x7fffffff) return PAMNET_EINVAL;
+    if (n == 0) return PAMNET_OK;
+    if (!pos || !cell_table || !img_box || !node_graph || !gptr || !ptr || !nbr || !dist || !img) return PAMNET_ENULL;
+    hipLaunchKernelGGL((radius_img_kernel<true>), dim3(blocks_for(n, 4)), dim3(256), 0, as_stream(stream), pos, cell_table,
+                       img_box, node_graph, gptr, n, r, (int32_t*)nullptr, ptr, nbr, dist, cap, row_of, img, (int)max_neighbors,
+                       (int32_t*)nullptr);
     PAMNET_LAUNCH_CHECK();
     return PAMNET_OK;
 }

@@ -184,6 +184,7 @@ class Graph(object):
 
     capped = False        # max_num_neighbors cut a row of the radius graph: not symmetric, general transposes (build_graph)
     cell_tab = None       # periodic batch: the cell table [num_graphs, 18] fp64 every *_pbc_* kernel reads (cell_table)
+    img_g = None          # periodic batch with cell_images='all': the image [E_g, 3] int32 of every global edge (radius_img_fill)
     pos_grad = False      # geometry linked to positions that require grad (differentiable_geometry)
 
     # Row lists / counts per kind are only needed by the generic (non-fused) path and by tests: built on first use so
@@ -219,6 +220,38 @@ def cell_table(cell, cutoff, flag):
     tab = torch.empty((ng, 18), dtype=torch.float64, device=cell.device)
     lib.call('pamnet_cell_prepare_f64', lib.ptr(cell), ng, float(cutoff), lib.ptr(tab), lib.ptr(flag), lib.stream_of(cell))
     return tab
+
+
+def cell_images(cell_tab, cutoff_g, flag):
+    """The candidate box of the all-image search (pamnet_cell_images_i32): per graph N_k = ceil(cutoff_g / height_k), int32 [G, 3].
+    ORs PBC_BIT into `flag` when some N_k > 4 (a height below cutoff_g / 4)."""
+    ng = int(cell_tab.size(0))
+    box = torch.empty((ng, 3), dtype=I32, device=cell_tab.device)
+    lib.call('pamnet_cell_images_i32', lib.ptr(cell_tab), ng, float(cutoff_g), lib.ptr(box), lib.ptr(flag), lib.stream_of(cell_tab))
+    return box
+
+
+def radius_img_count(pos, cell_tab, box, node_graph, gptr, r, max_neighbors=0, cap_flag=None):
+    """Scanned row sizes of the radius search over all images of a periodic cell (pamnet_radius_img_count_i32): row i counts every
+    (atom j, image n) within r of atom i, i's own images included.  No row is ever cut: max_neighbors > 0 only ORs CAP_BIT into
+    `cap_flag` for a row whose hits, the query itself counted, exceed it."""
+    n = pos.size(0)
+    count = _i32(n, pos.device)
+    lib.call('pamnet_radius_img_count_i32', lib.ptr(pos), lib.ptr(cell_tab), lib.ptr(box), lib.ptr(node_graph), lib.ptr(gptr), n,
+             int(gptr.numel()) - 1, float(r), int(max_neighbors or 0), lib.ptr(count), lib.ptr(cap_flag), lib.stream_of(pos))
+    return exclusive_scan(count)
+
+
+def radius_img_fill(pos, cell_tab, box, node_graph, gptr, r, ptr, total, max_neighbors=0):
+    """(ptr, nbr, dist, row_of, img) of that search: ascending (neighbour, image) inside a row; img [total, 3] int32 with
+    pos_row - pos_col - img @ cell the edge's vector."""
+    dev = pos.device
+    nbr, dist, row_of = _i32(total, dev), _f32(total, dev), _i32(total, dev)
+    img = torch.empty((total, 3), dtype=I32, device=dev)
+    lib.call('pamnet_radius_img_fill_i32', lib.ptr(pos), lib.ptr(cell_tab), lib.ptr(box), lib.ptr(node_graph), lib.ptr(gptr),
+             pos.size(0), int(gptr.numel()) - 1, float(r), int(max_neighbors or 0), lib.ptr(ptr), lib.ptr(nbr), lib.ptr(dist),
+             lib.ptr(row_of), lib.ptr(img), int(total), lib.stream_of(pos))
+    return ptr, nbr, dist, row_of, img
 
 
 def _call_in_cell(open_sym, pbc_sym, pos, pbc, *rest):
@@ -462,7 +495,13 @@ def _raise_bad_inputs():
                      '[0, num_graphs), atom types in [0, embeddings.size(0)), edge_index in [0, num_nodes)')
 
 
-def _raise_bad_cell(cutoff_l, cutoff_g):
+def _raise_bad_cell(cutoff_l, cutoff_g, all_images=False):
+    if all_images:
+        raise ValueError('periodic cell too small or singular for cell_images=\'all\': every cell of the batch must be non-singular '
+                         'with each of its three perpendicular heights |det| / |a_i x a_j| above 2 * cutoff_l = %g (the local graph '
+                         'keeps one image per pair) and not below cutoff_g / 4 = %g (the global search tries at most 4 images to '
+                         'either side per lattice direction) -- replicate the cell along its short directions, or lower the '
+                         'cutoffs' % (2 * float(cutoff_l), float(cutoff_g) / 4))
     rc = max(float(cutoff_l), float(cutoff_g))
     raise ValueError('periodic cell too small or singular: every cell of the batch must be non-singular with each of its three '
                      'perpendicular heights |det| / |a_i x a_j| above 2 * max(cutoff_l, cutoff_g) = %g (each pair then has at '
@@ -495,6 +534,25 @@ def _checked_cell(cell, dataset, edge_index, sizes, n_graphs, pos):
                                   'requires_grad=True)` and differentiate with respect to it (torch.autograd.grad(E.sum(), '
                                   '[data.pos, data.strain])); forces with respect to `pos` are available')
     return cell.detach().contiguous().view(int(n_graphs), 9)
+
+
+def _checked_cell_images(cell_images, cell):
+    """`data.cell_images`: which images the GLOBAL graph of a periodic batch holds.  Returns True for 'all'."""
+    if cell_images is None:
+        return False
+    if cell_images not in ('minimum', 'all'):
+        raise ValueError("`cell_images` must be None, 'minimum' (one image per pair: every cell height above 2 * max(cutoff_l, "
+                         "cutoff_g)) or 'all' (every image within cutoff_g in the global graph: heights above 2 * cutoff_l); got %r"
+                         % (cell_images,))
+    if cell is None:
+        raise ValueError('`cell_images` belongs to periodic batches (`cell`): drop it, or hand the structure over with its `cell`')
+    return cell_images == 'all'
+
+
+def _raise_cap_binds(max_nb):
+    raise ValueError("max_num_neighbors = %d is below the largest row of the all-image global graph (the atom itself counted), and "
+                     "with cell_images='all' no row is cut (a cut multigraph is not symmetric): raise model.max_num_neighbors, or "
+                     "set it to None" % max_nb)
 
 
 def _checked_strain(strain, cell, n_graphs, pos):
@@ -815,6 +873,7 @@ class _Lists(object):
     = the expanded row ids when the fill wrote them), the local one (lp, l_src, l_dst, l_dist), and what the builder happens
     to know already."""
     sign = cell_tab = None                        # PDBbind: +1 pocket / -1 ligand per node; periodic batch: cell_table
+    img_g = None                                  # periodic batch, cell_images='all': the image of every global edge
     gp = gn = gd = g_rows = lp = l_src = l_dst = l_dist = None
     tp_ptr = tp_total = tcount = None             # triplet / pair pointer, total and triplet counts, if made already
     tp_hint = None                                # triplet + pair rows already known on the host
@@ -836,7 +895,7 @@ class _Lists(object):
 
 
 _Args = namedtuple('_Args', 'cutoff_l cutoff_g flow x_raw pos edge_index need_grad knn_k with_triplets n_types sizes mol_local '
-                            'max_nb cell strain_nz')
+                            'max_nb cell strain_nz all_images')
 _Bonds = namedtuple('_Bonds', 'ptr src dst dist tp_ptr tcount raw')
 
 
@@ -888,6 +947,8 @@ def _qm9_bond_free(g, ing, a):
             return None
     r = _Lists(pos, _Sizes(flag, a.sizes))
     sz, r.loc_radius = r.sz, True
+    if a.all_images:
+        return _all_image_lists(g, a, r, flag)
     # Periodic cells: the same sequence with the minimum-image forms of the two searches and of the angle fill.  The table is
     # prepared first; its verdict (PBC_BIT) travels in the validity word with the sizes' round trip.
     tab = r.cell_tab = None if a.cell is None else cell_table(a.cell, max(float(a.cutoff_l), float(a.cutoff_g)), flag)
@@ -909,6 +970,30 @@ def _qm9_bond_free(g, ing, a):
         r.global_by_neighbour(g.n, a.need_grad)
     r.lp, r.l_src, r.l_dist = radius_fill(pos, g.node_graph, g.gptr, a.cutoff_l, lp, total_l, zeroed=sz.arena, rows_out=rows,
                                           cell_tab=tab)
+    r.l_dst = rows.pop()
+    return r
+
+
+def _all_image_lists(g, a, r, flag):
+    """cell_images='all': the local graph as ever -- the minimum-image radius graph at cutoff_l, which alone has to be a simple
+    graph, so the cells need heights above 2 * cutoff_l only -- and the global graph over every image within cutoff_g, a
+    multigraph with an image per edge (radius_img_fill).  The same single round trip: the cell's verdict (both conditions raise
+    PBC_BIT) and the cap's travel in the validity word with the sizes.  No row is cut, so a cap that binds is an error."""
+    pos, sz = r.pos, r.sz
+    assert sz.known is None                       # (periodic batches carry no host sizes: _checked_cell)
+    tab = r.cell_tab = cell_table(a.cell, float(a.cutoff_l), flag)
+    box = cell_images(tab, a.cutoff_g, flag)
+    gptr_g = radius_img_count(pos, tab, box, g.node_graph, g.gptr, a.cutoff_g, a.max_nb, flag)
+    lp = radius_count(pos, g.node_graph, g.gptr, a.cutoff_l, cell_tab=tab)
+    (total_g, total_l, r.tp_hint), capped = sz.read(gptr_g[-1], lp[-1], _symmetric_tp_total(lp, a.with_triplets),
+                                                    allow=CAP_BIT | PBC_BIT, cutoffs=(a.cutoff_l, a.cutoff_g, True),
+                                                    strain_nz=a.strain_nz)
+    if capped:
+        _raise_cap_binds(a.max_nb)
+    r.gp, r.gn, r.gd, r.g_rows, r.img_g = radius_img_fill(pos, tab, box, g.node_graph, g.gptr, a.cutoff_g, gptr_g, total_g,
+                                                          max_neighbors=a.max_nb)
+    rows = []
+    r.lp, r.l_src, r.l_dist = radius_fill(pos, g.node_graph, g.gptr, a.cutoff_l, lp, total_l, rows_out=rows, cell_tab=tab)
     r.l_dst = rows.pop()
     return r
 
@@ -1048,6 +1133,8 @@ def _finish(g, r, dataset, a):
     g.pos, g.sign, g.capped = pos, r.sign, r.capped
     if r.cell_tab is not None:
         g.cell_tab = r.cell_tab
+    if r.img_g is not None:
+        g.img_g = r.img_g
     if sz.known is not None:
         g.check = sz.flag
     if r.loops is not None:
@@ -1080,7 +1167,9 @@ def _finish(g, r, dataset, a):
     if a.need_grad:
         # d x[j] of the global gather: the reverse-edge index of a radius graph (symmetric by construction, unless the
         # neighbour cap cut it); for a list stored by neighbour the inverse of that transposition; a counting sort otherwise
-        radius_g = dataset in ('QM9', 'PDBbind') and not r.capped
+        # -- but for the all-image multigraph, whose rows repeat columns: the counting sort of its columns.  (It is symmetric
+        # as a multiset, so its rows aggregate at the neighbour as they stand: never stored by neighbour.)
+        radius_g = dataset in ('QM9', 'PDBbind') and not r.capped and r.img_g is None
         g.glob_T = SymmetricTranspose(g.glob) if radius_g else (r.glob_inv if r.glob_inv is not None
                                                                else Transpose(g.glob.col, n))
         # d x[j] of the local gather: a radius graph for PDBbind and bond-free QM9, the inverse transposition for RNA;
@@ -1094,7 +1183,7 @@ def _finish(g, r, dataset, a):
 
 def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_index=None, num_graphs=None,
                 need_grad=True, knn_k=None, with_triplets=True, n_types=None, sizes=None, default_basis=True, mol_local=None,
-                max_num_neighbors=None, aux_tables=True, cell=None, strain=None):
+                max_num_neighbors=None, aux_tables=True, cell=None, strain=None, cell_images=None):
     """Graph-construction part of PAMNet.forward (models.py:104-177).  Returns a Graph.
 
     `cell` (QM9 schema, bond-free, no `sizes`): fp32 [num_graphs, 3, 3] on the device, row k of cell[g] = lattice vector a_k of
@@ -1102,6 +1191,12 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
     radius searches, the bond lengths, both angle kinds and the position backward.  Positions need not be wrapped.  Each cell
     must be non-singular with all three perpendicular heights above 2 * max(cutoff_l, cutoff_g) (ValueError otherwise, with the
     sizes' round trip).  Always the step-by-step launches.
+
+    `cell_images` (periodic batches): None / 'minimum' = the above.  'all': the GLOBAL graph holds every image within cutoff_g --
+    row i every (atom j, integer triple n) with |pos_i - pos_j - n @ cell| <= cutoff_g, i's own images included, ascending (j, n),
+    the triple of every edge in g.img_g -- while the local graph stays the minimum-image one.  The cells then need heights above
+    2 * cutoff_l only (and not below cutoff_g / 4).  max_num_neighbors cuts no row of that graph: a cap that binds is a
+    ValueError.
 
     `strain` (periodic batches): the tensor that names the variable of the virial (differentiable_geometry) -- fp32 zeros
     [num_graphs, 3, 3] on the device.  Only validated here; its count of non-zero entries rides in the sizes' round trip.
@@ -1132,6 +1227,7 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
         if n_graphs is None:
             n_graphs = int(batch[-1]) + 1
         cell = _checked_cell(cell, dataset, edge_index, sizes, n_graphs, pos)
+    all_images = _checked_cell_images(cell_images, cell)
     strain_nz = None if strain is None else _checked_strain(strain, cell, n_graphs, pos)
     max_nb = int(max_num_neighbors or 0)
     knn_k = KNN_K if knn_k is None else int(knn_k)
@@ -1167,7 +1263,7 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
         raise ValueError("Invalid dataset. If you are using any dataset related to RNA 3D structure prediction, "
                          "be sure to use 'rna' as the first 3 characters of the dataset name.")
     a = _Args(cutoff_l, cutoff_g, flow, x_raw, pos, edge_index, need_grad, knn_k, with_triplets, n_types, sizes, mol_local,
-              max_nb, cell, strain_nz)
+              max_nb, cell, strain_nz, all_images)
     r = lists(g, ing, a)
     if r is not None:                             # (None: the molecule-local builder has made everything)
         _finish(g, r, dataset, a)
@@ -1246,14 +1342,16 @@ class _Geometry(torch.autograd.Function):
     """pos [N, 3] (, strain [G, 3, 3] of zeros, periodic graphs) -> (dist_g, dist_l, tp_angle) of a graph built from these
     positions (models.py:62-66,165-177).  The forward hands out the values graph construction already computed; the backward is
     pamnet_pos_bwd_f32 -- or, when the gradient with respect to the strain is asked for, pamnet_pos_bwd_pbc_virial_f32, which
-    writes the same dpos and the virial of every graph.  Everything the backward reads is kept (pos through save_for_backward,
-    so an in-place change of it is caught): a graph that is retained can be walked again."""
+    writes the same dpos and the virial of every graph; a graph with an all-image global list (g.img_g) takes the *_img_* forms.
+    Everything the backward reads is kept (pos through save_for_backward, so an in-place change of it is caught): a graph that is
+    retained can be walked again."""
 
     @staticmethod
     def forward(ctx, pos, strain, g):
         ctx.save_for_backward(pos)
         ctx.idx = _index_lists(g)
         ctx.pbc = None if g.cell_tab is None else (g.cell_tab, g.node_graph)      # periodic graph: the image rule's inputs
+        ctx.img = g.img_g                                                          # all-image global list: its edges' images
         ctx.graphs = None if strain is None else (g.gptr, int(g.n_graphs))        # what the virial's reduction reads
         return g.dist_g.clone(), g.dist_l.clone(), g.tp_angle.clone()
 
@@ -1268,16 +1366,20 @@ class _Geometry(torch.autograd.Function):
         work = torch.empty(3 * max(el, 1), dtype=torch.float64, device=pos.device)
         dpos = torch.empty((n, 3), dtype=torch.float32, device=pos.device)
         P = lib.ptr
+        img = ctx.img is not None
+        if img:                                       # (the *_img_* forms: g_img behind g_col)
+            glob = glob[:3] + (ctx.img,) + glob[3:]
         if not (ctx.graphs is not None and ctx.needs_input_grad[1]):
-            _call_in_cell('pamnet_pos_bwd_f32', 'pamnet_pos_bwd_pbc_f32', pos, ctx.pbc, n, *map(P, glob), P(d_dg), eg,
-                          *map(P, loc), P(d_dl), el, *map(P, trip), P(d_ang), tp, P(work), P(dpos), lib.stream_of(pos))
+            _call_in_cell('pamnet_pos_bwd_f32', 'pamnet_pos_bwd_img_f32' if img else 'pamnet_pos_bwd_pbc_f32', pos, ctx.pbc, n,
+                          *map(P, glob), P(d_dg), eg, *map(P, loc), P(d_dl), el, *map(P, trip), P(d_ang), tp, P(work), P(dpos),
+                          lib.stream_of(pos))
             return dpos, None, None
         gptr, n_graphs = ctx.graphs
         atom_work = torch.empty(9 * max(n, 1), dtype=torch.float64, device=pos.device)
         dstrain = torch.empty((max(n_graphs, 1), 9), dtype=torch.float32, device=pos.device)[:n_graphs]
-        lib.call('pamnet_pos_bwd_pbc_virial_f32', P(pos), *map(P, ctx.pbc), n, *map(P, glob), P(d_dg), eg, *map(P, loc), P(d_dl),
-                 el, *map(P, trip), P(d_ang), tp, P(work), P(dpos), P(gptr), n_graphs, P(atom_work), P(dstrain),
-                 lib.stream_of(pos))
+        lib.call('pamnet_pos_bwd_img_virial_f32' if img else 'pamnet_pos_bwd_pbc_virial_f32', P(pos), *map(P, ctx.pbc), n,
+                 *map(P, glob), P(d_dg), eg, *map(P, loc), P(d_dl), el, *map(P, trip), P(d_ang), tp, P(work), P(dpos), P(gptr),
+                 n_graphs, P(atom_work), P(dstrain), lib.stream_of(pos))
         return (dpos if ctx.needs_input_grad[0] else None), dstrain.view(n_graphs, 3, 3), None
 
 
