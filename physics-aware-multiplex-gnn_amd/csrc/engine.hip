@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "common.h"
+#include "node_chain_args.h"
 
 namespace {
 
@@ -121,7 +122,6 @@ struct Plan {
     bool agg_in;          // forward: the local aggregations are formed by the chain launch that consumes them
     bool gather;          // backward: the segment sums are formed by the fused head + chain launch that consumes them
     int32_t pk, pkc;      // what a launch is told about its weights: 0 raw, 1 fp32 images; the chains' own: 2 = bf16x3 images
-    int64_t pcs;          // PAMNET_CHAIN_PIECES for the fused backward launches of a bf16 plan, else 0
 };
 
 inline Plan make_plan(const Graph& g, bool packed, bool forked, Dir dir) {
@@ -152,7 +152,6 @@ inline Plan make_plan(const Graph& g, bool packed, bool forked, Dir dir) {
     p.gather = packed && sw.fuse_segsum && parked;
     p.pk = packed ? 1 : 0;
     p.pkc = p.bf16 ? 2 : p.pk;
-    p.pcs = p.bf16 ? PAMNET_CHAIN_PIECES : 0;
     return p;
 }
 
@@ -392,27 +391,20 @@ struct Forward {
     // Each nullable.
     int chain(const ChainSaved& c, const float* res_x, const float* const* W, const float* const* tb, const NextHead* next,
               const MlpTiles* ride, const pamnet_local_agg* agg) const {
-        static const float* const no_img[1] = {nullptr};
-        const NextHead nx = next ? NextHead{next->img, next->bx1, next->nblk, sv(next->Zx1), next->P} : NextHead{no_img};
-        const float* const* wp = next ? nx.img + 1 : nullptr;
-        const int64_t ldwp = next ? 3 * D : 0;
-        float* const x1 = next ? t.x1 : nullptr;
-        if (!ride && !agg)
-            return pamnet_node_tail_fwd_f32(c.x2, res_x, g.n, W, tb + T_B, tb[T_WOUT], tb[T_BOUT], tb[T_WATT], sv(c.Z), sv(c.R),
-                                            c.xout, nullptr, nullptr, nx.img[0], nx.bx1, wp, ldwp, nx.nblk, nx.Zx1, x1, nx.P,
-                                            P.pkc, st);
-        const MlpTiles rd = ride ? *ride : MlpTiles{};
-        const float* const mx = ride ? e_sbf : nullptr;
-        const float* const* mp = ride ? rd.mlp : nullptr;
-        float* const* mo = ride ? rd.out : nullptr;
-        const int64_t rows = ride ? g.tp : 0, wgs = ride ? P.idle : 0;
-        if (agg)
-            return pamnet_node_tail_fwd_agg_f32(c.x2, res_x, g.n, W, tb + T_B, tb[T_WOUT], tb[T_BOUT], tb[T_WATT], sv(c.Z),
-                                                sv(c.R), c.xout, nx.img[0], nx.bx1, wp, ldwp, nx.nblk, nx.Zx1, x1, nx.P, mx, rows,
-                                                rd.tile0, rd.ntiles, mp, mo, wgs, P.pkc, agg, st);
-        return pamnet_node_tail_fwd_rider_f32(c.x2, res_x, g.n, W, tb + T_B, tb[T_WOUT], tb[T_BOUT], tb[T_WATT], sv(c.Z), sv(c.R),
-                                              c.xout, nx.img[0], nx.bx1, wp, ldwp, nx.nblk, nx.Zx1, x1, nx.P, mx, rows, rd.tile0,
-                                              rd.ntiles, mp, mo, wgs, P.pkc, st);
+        node_chain::ChainFwd a{};
+        a.x2 = c.x2, a.res_x = res_x, a.n = g.n;
+        a.W = W, a.b = tb + T_B, a.w_out = tb[T_WOUT], a.b_out = tb[T_BOUT], a.w_att = tb[T_WATT];
+        a.Z = sv(c.Z), a.R = sv(c.R), a.x_out = c.xout;      // (out = att = null: deferred heads)
+        if (next) {
+            a.next.Wx1 = next->img[0], a.next.bx1 = next->bx1, a.next.wp = next->img + 1, a.next.ldwp = 3 * D;
+            a.next.nblk = next->nblk, a.next.Zx1 = sv(next->Zx1), a.next.x1 = t.x1, a.next.P = next->P;
+        }
+        if (ride) {
+            a.rider.x = e_sbf, a.rider.rows = g.tp, a.rider.tile0 = ride->tile0, a.rider.ntiles = ride->ntiles;
+            a.rider.mlp = ride->mlp, a.rider.out = ride->out, a.rider.wgs = P.idle;
+        }
+        a.agg = agg, a.packed = P.pkc, a.stream = st;
+        return node_chain::node_chain_fwd(a);
     }
 };
 
@@ -489,13 +481,14 @@ struct Backward {
             CK(pamnet_wgrad_rider_plan_f32(jr.n, jr.dZ, jr.ld_dz, jr.A, jr.ld_a, jr.mode, jr.rows, jr.dW, jr.ld_dw, jr.db,
                                            ride->partial, P.idle, rider, ride->slots));
         }
-        void* const r = ride ? rider : nullptr;
-        if (src)
-            CK(pamnet_node_pre_tail_bwd_gather_f32(h.dP, src, ptr, perm, t.dx2, t.dresx, g.n, h.img[0], h.img + 1, h.nblk | P.pcs,
-                                                   h.Zx1, h.dZx1, c.gh, W, c.Z, dz, t.dx2, t.dresx, r, st));
-        else
-            CK(pamnet_node_pre_tail_bwd_f32(h.dP, t.dx2, t.dresx, g.n, h.img[0], h.img + 1, h.nblk | P.pcs, h.Zx1, h.dZx1, c.gh, W,
-                                            c.Z, dz, t.dx2, t.dresx, r, st));
+        node_chain::HeadBwd hb{};
+        hb.dP = h.dP, hb.gather_src = src, hb.gather_ptr = src ? ptr : nullptr, hb.gather_perm = src ? perm : nullptr;
+        hb.dx1_direct = t.dx2, hb.d_add = t.dresx, hb.Wx1 = h.img[0], hb.wp = h.img + 1, hb.nblk = h.nblk;
+        hb.Zx1 = h.Zx1, hb.dZx1 = h.dZx1;
+        node_chain::ChainBwd a{};
+        a.g_head = c.gh, a.n = g.n, a.W = W, a.Z = c.Z, a.dZ = dz, a.d_x2 = t.dx2, a.d_resx = t.dresx;
+        a.packed = P.pkc, a.head = &hb, a.rider = ride ? rider : nullptr, a.stream = st;
+        CK(node_chain::node_chain_bwd(a));
         if (ride) CK(pamnet_wgrad_rider_enqueue_f32(wctx, rider));
         return PAMNET_OK;
     }

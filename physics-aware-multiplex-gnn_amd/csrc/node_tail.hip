@@ -22,6 +22,7 @@
 #include "common.h"
 #include "edge_core.h"
 #include "gemm_core.h"
+#include "node_chain_args.h"
 #include "wgrad_core.h"
 
 using namespace pamnet;
@@ -70,17 +71,26 @@ struct Mlp2Rider {
     edge::Mlp2Set set;
     int tile0, ntiles, n_chain;
 };
+// the rows of rider workgroup blockIdx.x - n_chain: the rider's tiles dealt evenly, in chunks of up to RMT tiles
+template <int RMT>
+__device__ __forceinline__ edge::Span rider_span(const Mlp2Rider& rd) {
+    const int b = (int)blockIdx.x - rd.n_chain, nr = (int)gridDim.x - rd.n_chain;
+    const int base = rd.ntiles / nr, rem = rd.ntiles % nr;
+    const int64_t t0 = rd.tile0 + (int64_t)b * base + (b < rem ? b : rem);
+    const int cnt = base + (b < rem ? 1 : 0);
+    edge::Span sp;
+    sp.beg = t0 * 16;
+    const int64_t e = (t0 + cnt) * 16;
+    sp.end = e < rd.m ? e : rd.m;
+    if (sp.beg > sp.end) sp.beg = sp.end;
+    const int nch = (cnt + RMT - 1) / RMT;
+    sp.cmt = nch > 0 ? (cnt + nch - 1) / nch : 1;
+    return sp;
+}
 
 constexpr int BMN = 16;                       // rows per workgroup
 constexpr int SLOT = BMN * LDT;               // floats per LDS slot
 constexpr int TWG = 512;                      // 8 waves
-// more row tiles than CUs: a CU gets several workgroups in turn -- the lean chain forms (co-resident workgroups) from here
-constexpr unsigned LEAN_FROM_TILES = (unsigned)PARKED_TILES_MAX;
-// PAMNET_CHAIN_LEAN=0: never, 1: forward only (default: both directions) -- read once, for A/B timing
-inline int lean_mode() {
-    static const int v = [] { const char* e = getenv("PAMNET_CHAIN_LEAN"); return e ? atoi(e) : 2; }();
-    return v;
-}
 
 // fragment coordinates of accumulator element r of this lane: row = 4*(lane>>4) + r, col = 16*wave + (lane&15)
 struct Frag {
@@ -307,6 +317,22 @@ __device__ __forceinline__ void local_agg_rows(const LocalAgg& la, const int64_t
     }
 }
 
+// Epilogue arithmetic of a forward layer for a lane's four channels (LDS offset o): z = acc + bias, a = SiLU(z) (+ the residual
+// tiles add1, add2 at o; each nullable).  Where z and a go is the caller's: parked in LDS or written from the registers.
+__device__ __forceinline__ void bias_silu_adds(const f32x4& acc, const float4& bias, const float* add1, const float* add2, int o,
+                                               float4& z, float4& a) {
+    z = make_float4(acc[0] + bias.x, acc[1] + bias.y, acc[2] + bias.z, acc[3] + bias.w);
+    a = make_float4(silu(z.x), silu(z.y), silu(z.z), silu(z.w));
+    if (add1) {
+        const float4 t = *reinterpret_cast<const float4*>(add1 + o);
+        a.x += t.x, a.y += t.y, a.z += t.z, a.w += t.w;
+    }
+    if (add2) {
+        const float4 t = *reinterpret_cast<const float4*>(add2 + o);
+        a.x += t.x, a.y += t.y, a.z += t.z, a.w += t.w;
+    }
+}
+
 template <bool PACKED, bool HEADS, bool RIDER = false>
 __global__ __launch_bounds__(WG) void node_tail_fwd_kernel(const float* __restrict__ x2,
                                                            const float* __restrict__ res_x, int64_t n, TailParams p,
@@ -322,18 +348,7 @@ __global__ __launch_bounds__(WG) void node_tail_fwd_kernel(const float* __restri
         if ((int)blockIdx.x >= rd.n_chain) {
             constexpr int RMT = 3;                            // 3-tile chunks: the 4-wave geometry without spills
             static_assert(18 * SLOT * 4 >= RMT * edge::MLP2_TILE_B, "rider tiles must fit the chain's LDS");
-            const int b = (int)blockIdx.x - rd.n_chain, nr = (int)gridDim.x - rd.n_chain;
-            const int base = rd.ntiles / nr, rem = rd.ntiles % nr;
-            const int64_t t0 = rd.tile0 + (int64_t)b * base + (b < rem ? b : rem);
-            const int cnt = base + (b < rem ? 1 : 0);
-            edge::Span sp;
-            sp.beg = t0 * 16;
-            const int64_t e = (t0 + cnt) * 16;
-            sp.end = e < rd.m ? e : rd.m;
-            if (sp.beg > sp.end) sp.beg = sp.end;
-            const int nch = (cnt + RMT - 1) / RMT;
-            sp.cmt = nch > 0 ? (cnt + nch - 1) / nch : 1;
-            edge::mlp2_fwd_body<RMT, 4>(rd.x, rd.set, sp, lds);
+            edge::mlp2_fwd_body<RMT, 4>(rd.x, rd.set, rider_span<RMT>(rd), lds);
             return;
         }
     }
@@ -390,17 +405,8 @@ __global__ __launch_bounds__(WG) void node_tail_fwd_kernel(const float* __restri
 #pragma unroll
         for (int n2 = 0; n2 < 2; ++n2) {
             const int o = r16 * LDT + wc + 16 * n2 + 4 * kg;   // (16-byte aligned: LDT * 4 = 33 x 16 bytes)
-            const float4 z = make_float4(acc[n2][0] + bv.v[n2].x, acc[n2][1] + bv.v[n2].y, acc[n2][2] + bv.v[n2].z,
-                                         acc[n2][3] + bv.v[n2].w);
-            float4 a = make_float4(silu(z.x), silu(z.y), silu(z.z), silu(z.w));
-            if (add1) {
-                const float4 t = *reinterpret_cast<const float4*>(add1 + o);
-                a.x += t.x, a.y += t.y, a.z += t.z, a.w += t.w;
-            }
-            if (add2) {
-                const float4 t = *reinterpret_cast<const float4*>(add2 + o);
-                a.x += t.x, a.y += t.y, a.z += t.z, a.w += t.w;
-            }
+            float4 z, a;
+            bias_silu_adds(acc[n2], bv.v[n2], add1, add2, o, z, a);
             *reinterpret_cast<float4*>(dst + o) = a;
             *reinterpret_cast<float4*>(zk + o) = z;
             if (tap) *reinterpret_cast<float4*>(tap + o) = a;
@@ -511,7 +517,7 @@ __global__ __launch_bounds__(WG) void node_tail_fwd_kernel(const float* __restri
 // (111 us per launch against 40 us of matrix-pipe time).  This form keeps only the five working tiles in LDS (42 KB:
 // three workgroups per CU) and writes z_k / the taps / the next head's outputs straight from the accumulators, behind the
 // next weight request (vmcnt retires in order: the request does not wait for them), the way node_heads_fwd_kernel does:
-// one workgroup's epilogue runs under another's MFMAs.  Packed weights, deferred heads; same arithmetic, same results.
+// one workgroup's epilogue runs under another's MFMAs.  Same arithmetic, same results; when it runs: plan_fwd (ChainForm::Lean).
 __global__ __launch_bounds__(WG, 3) void node_tail_fwd_lean_kernel(const float* __restrict__ x2, const float* __restrict__ res_x,
                                                                    int64_t n, TailParams p, float* __restrict__ Z,
                                                                    float* __restrict__ R, float* __restrict__ x_out,
@@ -549,17 +555,8 @@ __global__ __launch_bounds__(WG, 3) void node_tail_fwd_lean_kernel(const float* 
 #pragma unroll
         for (int n2 = 0; n2 < 2; ++n2) {
             const int c0 = wc + 16 * n2 + 4 * kg, o = r16 * LDT + c0;
-            const float4 z = make_float4(acc[n2][0] + bv.v[n2].x, acc[n2][1] + bv.v[n2].y, acc[n2][2] + bv.v[n2].z,
-                                         acc[n2][3] + bv.v[n2].w);
-            float4 a = make_float4(silu(z.x), silu(z.y), silu(z.z), silu(z.w));
-            if (add1) {
-                const float4 t = *reinterpret_cast<const float4*>(add1 + o);
-                a.x += t.x, a.y += t.y, a.z += t.z, a.w += t.w;
-            }
-            if (add2) {
-                const float4 t = *reinterpret_cast<const float4*>(add2 + o);
-                a.x += t.x, a.y += t.y, a.z += t.z, a.w += t.w;
-            }
+            float4 z, a;
+            bias_silu_adds(acc[n2], bv.v[n2], add1, add2, o, z, a);
             *reinterpret_cast<float4*>(dst + o) = a;
             if (trow) {
                 if (zg) st_nt4(reinterpret_cast<float4*>(zg + (row0 + r16) * DIM + c0), z);      // (backward-only saves: streamed)
@@ -614,7 +611,7 @@ __global__ __launch_bounds__(WG, 3) void node_tail_fwd_lean_kernel(const float* 
 }
 
 // ---- the forward chain on the bf16 matrix pipe at fp32 accuracy ("bf16x6", gemm_core.h) ---------------------------------
-// The production form of the kernel above (packed weights, deferred heads) with every GEMM as six bf16 piece products: a layer
+// The production form of the kernel above (ChainForm::Bf16 of plan_fwd) with every GEMM as six bf16 piece products: a layer
 // is 48 v_mfma_f32_16x16x32_bf16 per wave (768 matrix-pipe cycles) instead of 64 fp32 MFMAs (2 048).  Every GEMM input tile
 // lives in LDS as three bf16 piece planes (edge_core.h st_pieces4 / lds_frag3p: 12 KB per 16-row tile, conflict-free on both
 // sides), written by the epilogue that produces it -- the split is done once per element; the weights arrive as the edge-level
@@ -701,18 +698,7 @@ __global__ __launch_bounds__(64 * NWV) void node_tail_fwd_bf16_kernel(const floa
             // in one chunk); 4 waves: two slices per wave, a matrix at a time, 3-tile chunks (no spills)
             constexpr int RMT = NWV == 8 ? 5 : 3;
             static_assert((12 * SLOT + 3 * PT / 4) * 4 >= RMT * edge::MLP2_TILE_B, "rider tiles must fit the chain's LDS");
-            const int b = (int)blockIdx.x - rd.n_chain, nr = (int)gridDim.x - rd.n_chain;
-            const int base = rd.ntiles / nr, rem = rd.ntiles % nr;
-            const int64_t t0 = rd.tile0 + (int64_t)b * base + (b < rem ? b : rem);
-            const int cnt = base + (b < rem ? 1 : 0);
-            edge::Span sp;
-            sp.beg = t0 * 16;
-            const int64_t e = (t0 + cnt) * 16;
-            sp.end = e < rd.m ? e : rd.m;
-            if (sp.beg > sp.end) sp.beg = sp.end;
-            const int nch = (cnt + RMT - 1) / RMT;
-            sp.cmt = nch > 0 ? (cnt + nch - 1) / nch : 1;
-            edge::mlp2_fwd_body<RMT, NWV>(rd.x, rd.set, sp, lds);
+            edge::mlp2_fwd_body<RMT, NWV>(rd.x, rd.set, rider_span<RMT>(rd), lds);
             return;
         }
     }
@@ -1045,6 +1031,50 @@ __device__ __forceinline__ void gather_finish(GatherState& gs, const PreBwd& pb,
     }
 }
 
+// The rider workgroups of a fused head + chain backward launch (node_tail_bwd_kernel<., ., true>, node_tail_bwd_bf16_kernel<true>):
+// split-K slot `slot` of the previous chain's weight gradients, staged in the chain's LDS.
+__device__ __forceinline__ void rider_slot(const WBatchS& rider, float* __restrict__ rider_partial, int slot, float* lds) {
+#ifdef PAMNET_PROBE_SKIP_RIDERS
+    return;       // development probe (never in libpamnet_hip.so): WRONG weight gradients, the launch without its riders' time
+#endif
+#ifndef PAMNET_RIDER_4W
+    // all eight waves (wave tile 32x64): the bf16x6 inner loop holds the split fragments of two pipeline stages and
+    // does not fit the 256 registers of a two-waves-per-SIMD kernel with the 64x64 tile; two waves per SIMD also
+    // interleave one wave's splits with the other's MFMAs in hardware
+    wgrad_body<8>(rider, rider_partial, slot, lds);
+#else
+    // four of the eight waves, one per SIMD, each with the 64x64 wave tile of the stand-alone kernel (the other
+    // four leave: a terminated wave no longer takes part in the workgroup barrier)
+    if (threadIdx.x < 256) wgrad_body<4>(rider, rider_partial, slot, lds);
+#endif
+}
+
+// Staging of the head backward's operands by sweep thread (row sr, float4 column sc4; global row sg) of the two parked kernels:
+// the planes of dP -- finished gathers (written to dP_out as well) or read -- go to store(b, v), the fp32 kernel's LDS tiles or the
+// bf16x6 kernel's piece planes; z_x1 -> EX, d x1_direct -> D1.  Returns the thread's d_add, which joins the kept gradient.
+template <typename Store>
+__device__ __forceinline__ float4 stage_head_bwd(GatherState& gst, const PreBwd& pb, int64_t sg, int64_t n, int sr, int sc4,
+                                                 float* EX, float* D1, Store store) {
+    const int64_t plane = n * DIM;
+    float4 gsum[4];
+    gather_finish(gst, pb, sc4, gsum);                         // (rows past n: empty ranges, zeros)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        if (b >= pb.nblk) break;
+        float4 v;
+        if (pb.gsrc[b]) {                                      // (workgroup-uniform) the plane is formed here, and kept
+            v = gsum[b];
+            if (sg < n) stg4(pb.dP_out + (int64_t)b * plane, sg, DIM, sc4, v);
+        } else {
+            v = ldg4z(pb.dP + (int64_t)b * plane, sg, n, DIM, sc4);
+        }
+        store(b, v);
+    }
+    st_lds4(EX, sr, sc4, ldg4z(pb.Zx1, sg, n, DIM, sc4));
+    st_lds4(D1, sr, sc4, ldg4z(pb.dx1_direct, sg, n, DIM, sc4));
+    return ldg4z(pb.d_add, sg, n, DIM, sc4);
+}
+
 template <bool PACKED, bool HEADS, bool PRE = false>
 __global__ __launch_bounds__(TWG) void node_tail_bwd_kernel(const float* __restrict__ d_xout /* may be null */,
                                                             const float* __restrict__ d_out,
@@ -1065,16 +1095,7 @@ __global__ __launch_bounds__(TWG) void node_tail_bwd_kernel(const float* __restr
         // otherwise idle CU -- the weight-gradient launch of that layer shrinks by what rides here.
         static_assert(sizeof(lds) >= sizeof(float) * WGRAD_LDS_FLOATS, "rider staging must fit the chain's LDS");
         if ((int)blockIdx.x >= n_tiles) {
-#ifndef PAMNET_RIDER_4W
-            // all eight waves (wave tile 32x64): the bf16x6 inner loop holds the split fragments of two pipeline stages and
-            // does not fit the 256 registers of a two-waves-per-SIMD kernel with the 64x64 tile; two waves per SIMD also
-            // interleave one wave's splits with the other's MFMAs in hardware
-            wgrad_body<8>(rider, rider_partial, (int)blockIdx.x - n_tiles, lds);
-#else
-            // four of the eight waves, one per SIMD, each with the 64x64 wave tile of the stand-alone kernel (the other
-            // four leave: a terminated wave no longer takes part in the workgroup barrier)
-            if (threadIdx.x < 256) wgrad_body<4>(rider, rider_partial, (int)blockIdx.x - n_tiles, lds);
-#endif
+            rider_slot(rider, rider_partial, (int)blockIdx.x - n_tiles, lds);
             return;
         }
     }
@@ -1113,23 +1134,8 @@ __global__ __launch_bounds__(TWG) void node_tail_bwd_kernel(const float* __restr
             // tiles of the head backward: dP planes -> ZL[7..9] + the (unused) head-partial area, z_x1 -> EX,
             // d x1_direct -> D1, d_add joins K (K = d_add + g_head; the head's d x is added below)
             float* const pl[4] = {ZL + 7 * SLOT, ZL + 8 * SLOT, ZL + 9 * SLOT, red};
-            float4 gsum[4];
-            gather_finish(gst, pb, sc4, gsum);                 // (rows past n: empty ranges, zeros)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                if (b >= pb.nblk) break;
-                float4 v;
-                if (pb.gsrc[b]) {                              // (workgroup-uniform) the plane is formed here, and kept
-                    v = gsum[b];
-                    if (sg < n) stg4(pb.dP_out + (int64_t)b * plane, sg, DIM, sc4, v);
-                } else {
-                    v = ldg4z(pb.dP + (int64_t)b * plane, sg, n, DIM, sc4);
-                }
-                st_lds4(pl[b], sr, sc4, v);
-            }
-            st_lds4(EX, sr, sc4, ldg4z(pb.Zx1, sg, n, DIM, sc4));
-            st_lds4(D1, sr, sc4, ldg4z(pb.dx1_direct, sg, n, DIM, sc4));
-            kx = f4add(kx, ldg4z(pb.d_add, sg, n, DIM, sc4));
+            kx = f4add(kx, stage_head_bwd(gst, pb, sg, n, sr, sc4, EX, D1,
+                                          [&](int b, const float4& v) __attribute__((always_inline)) { st_lds4(pl[b], sr, sc4, v); }));
         }
         st_lds4(K, sr, sc4, kx);
     }
@@ -1271,7 +1277,7 @@ __global__ __launch_bounds__(TWG) void node_tail_bwd_kernel(const float* __restr
 }
 
 // ---- the backward chain on the bf16 matrix pipe at fp32 accuracy ("bf16x6") ----------------------------------------------
-// node_tail_bwd_kernel<true, false, PRE> (packed weights, deferred heads: the production form of single-round batches) with
+// node_tail_bwd_kernel<true, false, PRE> (the production form of single-round batches: ChainForm::Bf16 of plan_bwd) with
 // every GEMM as six bf16 piece products, the way node_tail_fwd_bf16_kernel runs the forward: 24 v_mfma_f32_16x16x32_bf16 per
 // wave and layer (two waves per SIMD: 768 matrix-pipe cycles) instead of 32 fp32 MFMAs (2 048).  Every GEMM input -- the head's
 // d P planes, dz_x1, the dz_k ping / pong -- is written once as three bf16 piece planes (edge_core.h st_pieces4) by the sweep or
@@ -1294,14 +1300,7 @@ __global__ __launch_bounds__(TWG) void node_tail_bwd_bf16_kernel(const float* __
     if constexpr (PRE) {
         static_assert(sizeof(lds) >= sizeof(float) * WGRAD_LDS_FLOATS, "rider staging must fit the chain's LDS");
         if ((int)blockIdx.x >= n_tiles) {                     // riders: see node_tail_bwd_kernel
-#ifdef PAMNET_PROBE_SKIP_RIDERS
-            return;       // development probe (never in libpamnet_hip.so): WRONG weight gradients, the launch without its riders' time
-#endif
-#ifndef PAMNET_RIDER_4W
-            wgrad_body<8>(rider, rider_partial, (int)blockIdx.x - n_tiles, lds);
-#else
-            if (threadIdx.x < 256) wgrad_body<4>(rider, rider_partial, (int)blockIdx.x - n_tiles, lds);
-#endif
+            rider_slot(rider, rider_partial, (int)blockIdx.x - n_tiles, lds);
             return;
         }
     }
@@ -1334,23 +1333,9 @@ __global__ __launch_bounds__(TWG) void node_tail_bwd_bf16_kernel(const float* __
         float4 kx = d_xout ? ldg4z(d_xout, sg, n, DIM, sc4) : f4zero();
         kx = f4add(kx, ldg4z(d_out, sg, n, DIM, sc4));         // + the head branch's d x_out
         if constexpr (PRE) {
-            float4 gsum[4];
-            gather_finish(gst, pb, sc4, gsum);                 // (rows past n: empty ranges, zeros)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                if (b >= pb.nblk) break;
-                float4 v;
-                if (pb.gsrc[b]) {                              // (workgroup-uniform) the plane is formed here, and kept
-                    v = gsum[b];
-                    if (sg < n) stg4(pb.dP_out + (int64_t)b * plane, sg, DIM, sc4, v);
-                } else {
-                    v = ldg4z(pb.dP + (int64_t)b * plane, sg, n, DIM, sc4);
-                }
-                edge::st_pieces4(PL + b * PT, sr, sc4, v);
-            }
-            st_lds4(EX, sr, sc4, ldg4z(pb.Zx1, sg, n, DIM, sc4));
-            st_lds4(D1, sr, sc4, ldg4z(pb.dx1_direct, sg, n, DIM, sc4));
-            kx = f4add(kx, ldg4z(pb.d_add, sg, n, DIM, sc4));
+            kx = f4add(kx, stage_head_bwd(gst, pb, sg, n, sr, sc4, EX, D1, [&](int b, const float4& v) __attribute__((always_inline)) {
+                               edge::st_pieces4(PL + b * PT, sr, sc4, v);      // (the planes as bf16 pieces)
+                           }));
         }
         st_lds4(K, sr, sc4, kx);
     }
@@ -1441,7 +1426,7 @@ __global__ __launch_bounds__(TWG) void node_tail_bwd_bf16_kernel(const float* __
 // (row 4 kg + r, column 16 wave + r16), so here they are REGISTERS: z_{k-1} is fetched by its lane ahead of layer k's MFMAs,
 // dz_k leaves from the accumulators (behind the next weight request), the kept residual gradient and d res_x never leave
 // the lane.  LDS holds the two GEMM-input tiles and, with PRE, the head's <= 4 dP planes: 51 KB, two workgroups of 8 waves
-// per CU -- one's epilogue under the other's MFMAs.  Packed (transposed) weight images, deferred heads; the same arithmetic
+// per CU -- one's epilogue under the other's MFMAs.  When it runs: plan_bwd (ChainForm::Lean); the same arithmetic
 // in the same order as node_tail_bwd_kernel<true, false, PRE>: bitwise the same results.  In-place calls (d_x2 / d_resx
 // aliasing dx1_direct / d_add) stay safe: a lane reads its elements before it writes them.
 template <bool PRE>
@@ -1685,11 +1670,12 @@ __global__ __launch_bounds__(WG) void head_reduce_kernel(const float* __restrict
     }
 }
 
-inline TailParams make_tail(const float* const* weights, const float* const* biases, const float* w_out,
+// the first `nw` matrices of a chain (forward: all ten with their biases and the head vectors; backward: biases null)
+inline TailParams make_tail(const float* const* weights, int nw, const float* const* biases, const float* w_out,
                             const float* b_out, const float* w_att, int packed) {
-    TailParams p;
+    TailParams p{};
     p.packed = packed;
-    for (int k = 0; k < 10; ++k) {
+    for (int k = 0; k < nw; ++k) {
         p.W[k] = weights[k];
         p.b[k] = biases ? biases[k] : nullptr;
     }
@@ -1699,45 +1685,7 @@ inline TailParams make_tail(const float* const* weights, const float* const* bia
     return p;
 }
 
-struct PackJobs {
-    const float* src[192];
-    int ld[192];
-};
-// grid (njobs, 8): block (job, j) writes the 512 float4 fragments of 16-column tile j
-__global__ __launch_bounds__(512) void pack_weights_kernel(PackJobs jobs, int transposed, float* __restrict__ images) {
-    const float* __restrict__ W = jobs.src[blockIdx.x];
-    const int ld = jobs.ld[blockIdx.x];
-    const int j = blockIdx.y, q = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int c = 16 * j + (lane & 15), k0 = 16 * q + 4 * (lane >> 4);
-    float4 v;
-    if (!transposed) v = *reinterpret_cast<const float4*>(W + (size_t)c * ld + k0);
-    else v = make_float4(W[(size_t)k0 * ld + c], W[(size_t)(k0 + 1) * ld + c], W[(size_t)(k0 + 2) * ld + c],
-                         W[(size_t)(k0 + 3) * ld + c]);
-    reinterpret_cast<float4*>(images + (size_t)blockIdx.x * IMG)[(j * 8 + q) * 64 + lane] = v;
-}
-
 }  // namespace
-
-// Fragment-ordered images of n (<= 192) 128x128 matrices (row stride ld[i] floats) into images[i * 16384 ...]; see the
-// layout note above.  transposed = 0: images for Y = X W^T (forward), 1: for Y = X W (backward).
-extern "C" int pamnet_pack_weights_f32(int64_t n, const float* const* W, const int64_t* ld, int32_t transposed,
-                                       float* images, pamnet_stream_t stream) {
-    if (n < 0 || n > 192) return PAMNET_EINVAL;
-    if (n == 0) return PAMNET_OK;
-    if (!W || !ld || !images) return PAMNET_ENULL;
-    PackJobs jobs;
-    for (int i = 0; i < 192; ++i) {
-        const int s = i < n ? i : 0;
-        if (!W[s]) return PAMNET_ENULL;
-        if (ld[s] < DIM || (ld[s] & 3)) return PAMNET_EINVAL;
-        jobs.src[i] = W[s];
-        jobs.ld[i] = (int)ld[s];
-    }
-    hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)n, 8), dim3(512), 0, as_stream(stream), jobs, (int)transposed,
-                       images);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
-}
 
 // One launch for the images of a whole step direction (round 6): kind 0 = the chains' fp32 fragment image above (16 384 floats),
 // kind 1 = the edge-level kernels' bf16x3 fragment image (edge_core.h load_wfragb1: 24 576 floats, the pieces a wave would
@@ -1791,135 +1739,181 @@ extern "C" int pamnet_pack_weights_mixed_f32(int64_t n, const float* const* W, c
     return PAMNET_OK;
 }
 
-// bf16x3 fragment images of n (<= 192) matrices into images[i * 24 576 ...]: kind-1 images of the launch above, one after the
-// other (node_tail_fwd_bf16_kernel and the edge-level kernels read the same layout).
-constexpr int64_t IMGB_FLOATS = 3 * DIM * DIM / 2;
-extern "C" int pamnet_pack_weights_bf16x3(int64_t n, const float* const* W, const int64_t* ld, int32_t transposed,
-                                          float* images, pamnet_stream_t stream) {
+// n (<= 192) images of one kind, one after the other: the launch above with kind[i] = kind, offset[i] = i * floats
+static int pack_uniform(int64_t n, const float* const* W, const int64_t* ld, int32_t kind1, int64_t floats, int32_t transposed,
+                        float* images, pamnet_stream_t stream) {
     if (n < 0 || n > 192) return PAMNET_EINVAL;
     if (n == 0) return PAMNET_OK;
     if (!W || !ld || !images) return PAMNET_ENULL;
     int32_t kind[192];
     int64_t offset[192];
-    for (int i = 0; i < n; ++i) kind[i] = 1, offset[i] = i * IMGB_FLOATS;
+    for (int i = 0; i < n; ++i) kind[i] = kind1, offset[i] = i * floats;
     return pamnet_pack_weights_mixed_f32(n, W, ld, kind, offset, transposed, images, stream);
 }
 
-// PAMNET_CHAIN_WAVES=4|8: the bf16x6 forward chain's workgroup geometry (read once, for A/B timing)
-static int chain_waves() {
-    static const int v = [] { const char* e = getenv("PAMNET_CHAIN_WAVES"); return (e && atoi(e) == 4) ? 4 : 8; }();
-    return v;
+// Fragment-ordered fp32 images of n (<= 192) 128x128 matrices (row stride ld[i] floats) into images[i * 16384 ...]; see the
+// layout note above.  transposed = 0: images for Y = X W^T (forward), 1: for Y = X W (backward).
+extern "C" int pamnet_pack_weights_f32(int64_t n, const float* const* W, const int64_t* ld, int32_t transposed,
+                                       float* images, pamnet_stream_t stream) {
+    return pack_uniform(n, W, ld, 0, IMG, transposed, images, stream);
 }
 
-static int tail_fwd_launch(const float* x2, const float* res_x, int64_t n, const float* const* weights,
-                           const float* const* biases, const float* w_out, const float* b_out, const float* w_att, float* Z,
-                           float* R, float* x_out, float* out, float* att, const float* next_Wx1, const float* next_bx1,
-                           const float* const* next_wp, int64_t next_ldwp, int64_t next_nblk, float* next_Zx1,
-                           float* next_x1, float* next_P, int32_t packed, const Mlp2Rider* rider, int rider_wgs,
-                           pamnet_stream_t stream, const pamnet_local_agg* agg = nullptr) {
-    if (n < 0 || next_nblk < 0 || next_nblk > 4) return PAMNET_EINVAL;
-    if (n == 0) return PAMNET_OK;
-    if (!x2 || !res_x || !weights || !biases || !w_out || !b_out || !w_att || (Z && !R) || !x_out || (!out != !att))
-        return PAMNET_ENULL;
-    const bool heads = out != nullptr;        // out = att = null: the head branch is run later by pamnet_node_heads_fwd_f32
-    for (int k = 0; k < 10; ++k)
-        if (!weights[k] || !biases[k]) return PAMNET_ENULL;
-    PreNext nx{};
-    nx.nblk = (int)next_nblk;
-    if (next_nblk > 0) {
-        if (!next_Wx1 || !next_bx1 || !next_wp || !next_x1 || !next_P) return PAMNET_ENULL;   // next_Zx1: optional save
-        nx.Wx1 = next_Wx1, nx.bx1 = next_bx1, nx.ldwp = (int)next_ldwp;
-        nx.Zx1 = next_Zx1, nx.x1 = next_x1, nx.P = next_P;
-        for (int b = 0; b < next_nblk; ++b) {
-            if (!next_wp[b]) return PAMNET_ENULL;
-            nx.wp[b] = next_wp[b];
-        }
-    }
-    hipStream_t st = as_stream(stream);
-    const dim3 grid((unsigned)ceil_div(n, BMN));
-    const TailParams tp = make_tail(weights, biases, w_out, b_out, w_att, packed ? 1 : 0);
-    if (packed == 2 && heads) return PAMNET_EINVAL;            // bf16x3 images: deferred heads only
-    LocalAgg la{};
-    if (agg) {
-        if (!agg->t_ptr || !agg->l_ptr) return PAMNET_ENULL;
-        // the fp32 chain kernels (packed images, deferred heads) form x2 themselves; every other form reads it: the aggregation
-        // runs as its own launch first, as it did until round 6
-        const bool in_kernel = packed && !heads && (packed == 2 || !(grid.x > LEAN_FROM_TILES && lean_mode() >= 1 && !rider));
-        if (in_kernel) {
-            la.m_ji = (const float4*)agg->m_ji, la.m_nb = (const float4*)agg->m_nb, la.s = (const float4*)agg->s;
-            la.q3 = (const float4*)agg->q3, la.init = (const float4*)agg->init, la.t_ptr = agg->t_ptr, la.t_col = agg->t_col;
-            la.l_ptr = agg->l_ptr, la.m_t = (float4*)agg->m_t, la.x2_out = (float4*)const_cast<float*>(x2);
-            if (!la.m_ji) la = LocalAgg{};                     // (a batch without local edges: x2 = init, by the launch below)
-        }
-        if (!la.m_ji) {
-            const int rc = pamnet_local_agg_fwd_f32(agg->m_ji, agg->m_nb, agg->s, agg->q3, agg->t_ptr, agg->t_col, agg->l_ptr,
-                                                    agg->init, n, agg->m_t, const_cast<float*>(x2), stream);
-            if (rc) return rc;
-        }
-    }
+// bf16x3 fragment images of n (<= 192) matrices into images[i * 24 576 ...]: kind-1 images (node_tail_fwd_bf16_kernel and the
+// edge-level kernels read the same layout).
+extern "C" int pamnet_pack_weights_bf16x3(int64_t n, const float* const* W, const int64_t* ld, int32_t transposed,
+                                          float* images, pamnet_stream_t stream) {
+    return pack_uniform(n, W, ld, 1, 3 * DIM * DIM / 2, transposed, images, stream);
+}
+
+// ---- launch plans -------------------------------------------------------------------------------------------------------
+// Which kernel a chain launch runs, stated once per direction: plain functions of sizes and switches.  node_chain_fwd /
+// node_chain_bwd check their record, ask the plan and launch; the entry points and engine.hip fill records (node_chain_args.h).
+namespace {
+using namespace node_chain;
+
+// more row tiles than CUs: a CU gets several workgroups in turn -- the lean chain forms (co-resident workgroups) from here
+constexpr int64_t LEAN_FROM_TILES = PARKED_TILES_MAX;
+
+// Every developer switch of this file, read once (on the first chain launch of the process); both for A/B timing.
+// PAMNET_CHAIN_LEAN=0: never the lean forms, 1: the forward only (default 2: both directions); PAMNET_CHAIN_WAVES=4|8: the
+// bf16x6 forward chain's workgroup geometry (default 8)
+struct ChainSwitches { int lean, waves; };
+inline const ChainSwitches& chain_switches() {
+    static const ChainSwitches s = [] {
+        auto num = [](const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; };
+        return ChainSwitches{num("PAMNET_CHAIN_LEAN", 2), num("PAMNET_CHAIN_WAVES", 8) == 4 ? 4 : 8};
+    }();
+    return s;
+}
+
+// node_tail_*_kernel<false, .> on the matrices themselves | node_tail_*_kernel<true, .> on fp32 images, a tile's state parked in
+// LDS | node_tail_*_lean_kernel: fp32 images, several workgroups per CU | node_tail_*_bf16_kernel on bf16x3 images (packed = 2)
+enum class ChainForm { RowMajor, Parked, Lean, Bf16 };
+struct FwdPlan { ChainForm form; int waves; bool heads, rider, agg_in_kernel; };
+struct BwdPlan { ChainForm form; bool pre, gather_in_kernel; int rider_slots; };
+
+inline ChainForm chain_form(int64_t tiles, int packed, bool may_be_lean) {
+    if (packed == 2) return ChainForm::Bf16;
+    if (!packed) return ChainForm::RowMajor;
+    return (may_be_lean && tiles > LEAN_FROM_TILES) ? ChainForm::Lean : ChainForm::Parked;
+}
+// The lean forward has neither heads nor riders.  The parked and bf16x6 deferred-heads kernels can form x2 themselves
+// (local_agg_rows); every other form reads it: the aggregation then runs as its own launch first.
+inline FwdPlan plan_fwd(int64_t tiles, int packed, bool heads, bool rider, bool agg) {
+    const ChainSwitches& sw = chain_switches();
+    FwdPlan p{};
+    p.form = chain_form(tiles, packed, !heads && !rider && sw.lean >= 1);
+    p.waves = p.form == ChainForm::Bf16 ? sw.waves : 4;
+    p.heads = heads, p.rider = rider;
+    p.agg_in_kernel = agg && !heads && (p.form == ChainForm::Parked || p.form == ChainForm::Bf16);
+    return p;
+}
+// packed: 2 with PAMNET_CHAIN_PIECES.  The lean backward carries no riders and reads its planes: gathered planes are then
+// formed by the batched segment-sum launch first.
+inline BwdPlan plan_bwd(int64_t tiles, int packed, bool pre, int rider_slots, bool any_gather) {
+    BwdPlan p{};
+    p.form = chain_form(tiles, packed, rider_slots == 0 && chain_switches().lean >= 2);
+    p.pre = pre, p.rider_slots = rider_slots;
+    p.gather_in_kernel = any_gather && p.form != ChainForm::Lean;
+    return p;
+}
+}  // namespace
+
+int node_chain::node_chain_fwd(const ChainFwd& a) {
+    const NextHead& nh = a.next;
+    const MlpRider& mr = a.rider;
+    const bool heads = a.out != nullptr;      // out = att = null: the head branch is run later by pamnet_node_heads_fwd_f32
+    if (mr.rows < 0 || mr.tile0 < 0 || mr.ntiles < 0 || mr.wgs < 0) return PAMNET_EINVAL;
+    const bool rider = mr.ntiles > 0 && mr.wgs > 0;
     if (rider) {
-        if (!packed || heads) return PAMNET_EINVAL;
-        Mlp2Rider rd = *rider;
-        rd.n_chain = (int)grid.x;
-        if (packed == 2)
-            if (chain_waves() == 8)
-                hipLaunchKernelGGL((node_tail_fwd_bf16_kernel<true, 8>), dim3(grid.x + (unsigned)rider_wgs), dim3(TWG), 0, st, x2,
-                                   res_x, n, tp, Z, R, x_out, nx, rd, la);
-            else
-                hipLaunchKernelGGL((node_tail_fwd_bf16_kernel<true, 4>), dim3(grid.x + (unsigned)rider_wgs), dim3(WG), 0, st, x2,
-                                   res_x, n, tp, Z, R, x_out, nx, rd, la);
-        else
-            hipLaunchKernelGGL((node_tail_fwd_kernel<true, false, true>), dim3(grid.x + (unsigned)rider_wgs), dim3(WG), 0, st,
-                               x2, res_x, n, tp, Z, R, x_out, out, att, nx, rd, la);
-    } else if (packed == 2 && chain_waves() == 8) hipLaunchKernelGGL((node_tail_fwd_bf16_kernel<false, 8>), grid, dim3(TWG), 0, st, x2, res_x, n, tp, Z, R, x_out, nx, Mlp2Rider{}, la);
-    else if (packed == 2) hipLaunchKernelGGL((node_tail_fwd_bf16_kernel<false, 4>), grid, dim3(WG), 0, st, x2, res_x, n, tp, Z, R, x_out, nx, Mlp2Rider{}, la);
-    else if (packed && heads) hipLaunchKernelGGL((node_tail_fwd_kernel<true, true>), grid, dim3(WG), 0, st, x2, res_x, n, tp, Z, R, x_out, out, att, nx);
-    else if (packed && grid.x > LEAN_FROM_TILES && lean_mode() >= 1) hipLaunchKernelGGL(node_tail_fwd_lean_kernel, grid, dim3(WG), 0, st, x2, res_x, n, tp, Z, R, x_out, nx);
-    else if (packed) hipLaunchKernelGGL((node_tail_fwd_kernel<true, false>), grid, dim3(WG), 0, st, x2, res_x, n, tp, Z, R, x_out, out, att, nx, Mlp2Rider{}, la);
-    else if (heads) hipLaunchKernelGGL((node_tail_fwd_kernel<false, true>), grid, dim3(WG), 0, st, x2, res_x, n, tp, Z, R, x_out, out, att, nx);
-    else hipLaunchKernelGGL((node_tail_fwd_kernel<false, false>), grid, dim3(WG), 0, st, x2, res_x, n, tp, Z, R, x_out, out, att, nx);
+        if (!mr.x || !mr.mlp || !mr.out || !mr.mlp[0] || !mr.mlp[1] || !mr.mlp[2] || !mr.mlp[3] || !mr.out[2]) return PAMNET_ENULL;
+        if (a.n == 0) return PAMNET_EINVAL;                  // no chain to ride on
+    }
+    if (a.n < 0 || nh.nblk < 0 || nh.nblk > 4) return PAMNET_EINVAL;
+    if (a.n == 0) return PAMNET_OK;
+    if (!a.x2 || !a.res_x || !a.W || !a.b || !a.w_out || !a.b_out || !a.w_att || (a.Z && !a.R) || !a.x_out || (!a.out != !a.att))
+        return PAMNET_ENULL;
+    for (int k = 0; k < 10; ++k)
+        if (!a.W[k] || !a.b[k]) return PAMNET_ENULL;
+    PreNext nx{};
+    nx.nblk = (int)nh.nblk;
+    if (nh.nblk > 0) {
+        if (!nh.Wx1 || !nh.bx1 || !nh.wp || !nh.x1 || !nh.P) return PAMNET_ENULL;       // Zx1: optional save
+        nx.Wx1 = nh.Wx1, nx.bx1 = nh.bx1, nx.ldwp = (int)nh.ldwp, nx.Zx1 = nh.Zx1, nx.x1 = nh.x1, nx.P = nh.P;
+        for (int b = 0; b < nh.nblk; ++b)
+            if (!(nx.wp[b] = nh.wp[b])) return PAMNET_ENULL;
+    }
+    if (a.packed == 2 && heads) return PAMNET_EINVAL;         // bf16x3 images: deferred heads only
+    if (a.agg && (!a.agg->t_ptr || !a.agg->l_ptr)) return PAMNET_ENULL;
+    if (rider && (!a.packed || heads)) return PAMNET_EINVAL;  // riders: weight images, deferred heads
+
+    // (a batch without local edges, m_ji null: x2 = init, by the stand-alone launch)
+    const int64_t tiles = ceil_div(a.n, BMN);
+    const FwdPlan plan = plan_fwd(tiles, a.packed, heads, rider, a.agg && a.agg->m_ji);
+    hipStream_t st = as_stream(a.stream);
+    const TailParams tp = make_tail(a.W, 10, a.b, a.w_out, a.b_out, a.w_att, a.packed ? 1 : 0);
+    LocalAgg la{};
+    if (plan.agg_in_kernel) {
+        const pamnet_local_agg& g = *a.agg;
+        la.m_ji = (const float4*)g.m_ji, la.m_nb = (const float4*)g.m_nb, la.s = (const float4*)g.s;
+        la.q3 = (const float4*)g.q3, la.init = (const float4*)g.init, la.t_ptr = g.t_ptr, la.t_col = g.t_col;
+        la.l_ptr = g.l_ptr, la.m_t = (float4*)g.m_t, la.x2_out = (float4*)const_cast<float*>(a.x2);
+    } else if (a.agg) {
+        const pamnet_local_agg& g = *a.agg;
+        const int rc = pamnet_local_agg_fwd_f32(g.m_ji, g.m_nb, g.s, g.q3, g.t_ptr, g.t_col, g.l_ptr, g.init, a.n, g.m_t,
+                                                const_cast<float*>(a.x2), a.stream);
+        if (rc) return rc;
+    }
+    Mlp2Rider rd{};
+    int64_t rider_wgs = 0;
+    if (plan.rider) {
+        rd.x = mr.x, rd.m = mr.rows;
+        rd.set = edge::Mlp2Set{mr.mlp[0], mr.mlp[1], mr.mlp[2], mr.mlp[3], mr.out[0], mr.out[1], mr.out[2]};
+        rd.tile0 = (int)mr.tile0, rd.ntiles = (int)mr.ntiles, rd.n_chain = (int)tiles;
+        rider_wgs = mr.wgs < mr.ntiles ? mr.wgs : mr.ntiles;  // never more workgroups than tiles
+    }
+    const dim3 grid((unsigned)(tiles + rider_wgs)), block(64 * plan.waves);
+    switch (plan.form) {
+    case ChainForm::RowMajor:
+    case ChainForm::Parked: {
+        const bool images = plan.form == ChainForm::Parked;
+        const auto kernel = !images       ? (heads ? node_tail_fwd_kernel<false, true> : node_tail_fwd_kernel<false, false>)
+                            : heads       ? node_tail_fwd_kernel<true, true>
+                            : plan.rider  ? node_tail_fwd_kernel<true, false, true>
+                                          : node_tail_fwd_kernel<true, false>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, a.x2, a.res_x, a.n, tp, a.Z, a.R, a.x_out, a.out, a.att, nx, rd, la);
+        break;
+    }
+    case ChainForm::Lean:
+        hipLaunchKernelGGL(node_tail_fwd_lean_kernel, grid, block, 0, st, a.x2, a.res_x, a.n, tp, a.Z, a.R, a.x_out, nx);
+        break;
+    case ChainForm::Bf16: {
+        const auto kernel = plan.waves == 8 ? (plan.rider ? node_tail_fwd_bf16_kernel<true, 8> : node_tail_fwd_bf16_kernel<false, 8>)
+                                            : (plan.rider ? node_tail_fwd_bf16_kernel<true, 4> : node_tail_fwd_bf16_kernel<false, 4>);
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, a.x2, a.res_x, a.n, tp, a.Z, a.R, a.x_out, nx, rd, la);
+        break;
+    }
+    }
     PAMNET_LAUNCH_CHECK();
     return PAMNET_OK;
 }
 
+// ---- the forward entry points: fillers of a ChainFwd (operands: include/pamnet_hip.h) ------------------------------------
 extern "C" int pamnet_node_tail_fwd_f32(const float* x2, const float* res_x, int64_t n, const float* const* weights,
                                         const float* const* biases, const float* w_out, const float* b_out,
                                         const float* w_att, float* Z, float* R, float* x_out, float* out, float* att,
                                         const float* next_Wx1, const float* next_bx1, const float* const* next_wp,
                                         int64_t next_ldwp, int64_t next_nblk, float* next_Zx1, float* next_x1,
                                         float* next_P, int32_t packed, pamnet_stream_t stream) {
-    return tail_fwd_launch(x2, res_x, n, weights, biases, w_out, b_out, w_att, Z, R, x_out, out, att, next_Wx1, next_bx1,
-                           next_wp, next_ldwp, next_nblk, next_Zx1, next_x1, next_P, packed, nullptr, 0, stream);
+    ChainFwd a{};
+    a.x2 = x2, a.res_x = res_x, a.n = n, a.W = weights, a.b = biases, a.w_out = w_out, a.b_out = b_out, a.w_att = w_att;
+    a.Z = Z, a.R = R, a.x_out = x_out, a.out = out, a.att = att, a.packed = packed, a.stream = stream;
+    a.next.Wx1 = next_Wx1, a.next.bx1 = next_bx1, a.next.wp = next_wp, a.next.ldwp = next_ldwp, a.next.nblk = next_nblk;
+    a.next.Zx1 = next_Zx1, a.next.x1 = next_x1, a.next.P = next_P;
+    return node_chain_fwd(a);
 }
 
-// The deferred-heads launch with an optional rider and an optional aggregation: the body of the two entry points below.
-static int tail_fwd_ride(const float* x2, const float* res_x, int64_t n, const float* const* weights,
-                         const float* const* biases, const float* w_out, const float* b_out, const float* w_att, float* Z,
-                         float* R, float* x_out, const float* next_Wx1, const float* next_bx1,
-                         const float* const* next_wp, int64_t next_ldwp, int64_t next_nblk, float* next_Zx1, float* next_x1,
-                         float* next_P, const float* mlp_x, int64_t mlp_rows, int64_t mlp_tile0, int64_t mlp_ntiles,
-                         const float* const* mlp, float* const* mlp_out, int64_t rider_wgs, int32_t packed,
-                         const pamnet_local_agg* agg, pamnet_stream_t stream) {
-    if (mlp_rows < 0 || mlp_tile0 < 0 || mlp_ntiles < 0 || rider_wgs < 0 || (packed != 1 && packed != 2)) return PAMNET_EINVAL;
-    if (mlp_ntiles == 0 || rider_wgs == 0)
-        return tail_fwd_launch(x2, res_x, n, weights, biases, w_out, b_out, w_att, Z, R, x_out, nullptr, nullptr, next_Wx1,
-                               next_bx1, next_wp, next_ldwp, next_nblk, next_Zx1, next_x1, next_P, packed, nullptr, 0, stream, agg);
-    if (!mlp_x || !mlp || !mlp_out || !mlp[0] || !mlp[1] || !mlp[2] || !mlp[3] || !mlp_out[2]) return PAMNET_ENULL;
-    if (n == 0) return PAMNET_EINVAL;                        // no chain to ride on
-    Mlp2Rider rd{};
-    rd.x = mlp_x, rd.m = mlp_rows;
-    rd.set = edge::Mlp2Set{mlp[0], mlp[1], mlp[2], mlp[3], mlp_out[0], mlp_out[1], mlp_out[2]};
-    rd.tile0 = (int)mlp_tile0, rd.ntiles = (int)mlp_ntiles;
-    if (rider_wgs > mlp_ntiles) rider_wgs = mlp_ntiles;       // never more workgroups than tiles
-    return tail_fwd_launch(x2, res_x, n, weights, biases, w_out, b_out, w_att, Z, R, x_out, nullptr, nullptr, next_Wx1,
-                           next_bx1, next_wp, next_ldwp, next_nblk, next_Zx1, next_x1, next_P, packed, &rd, (int)rider_wgs, stream,
-                           agg);
-}
-
-// The same launch (packed weight images, deferred heads: out = att = null) with a rider: row tiles
-// [mlp_tile0, mlp_tile0 + mlp_ntiles) (16 rows each) of the two-layer MLP  y = SiLU(W2 SiLU(W1 x + b1) + b2)  over
-// mlp_x [mlp_rows, 128] are computed by `rider_wgs` extra workgroups (mlp = {W1, b1, W2, b2}; mlp_out = {z1, z2, y},
-// z1 / z2 nullable saves) -- pamnet_mlp2_fwd_f32 on the CUs the chain leaves idle.
+// The deferred-heads launch on weight images with an optional rider ...
 extern "C" int pamnet_node_tail_fwd_rider_f32(const float* x2, const float* res_x, int64_t n, const float* const* weights,
                                               const float* const* biases, const float* w_out, const float* b_out,
                                               const float* w_att, float* Z, float* R, float* x_out,
@@ -1928,13 +1922,18 @@ extern "C" int pamnet_node_tail_fwd_rider_f32(const float* x2, const float* res_
                                               float* next_P, const float* mlp_x, int64_t mlp_rows, int64_t mlp_tile0,
                                               int64_t mlp_ntiles, const float* const* mlp, float* const* mlp_out,
                                               int64_t rider_wgs, int32_t packed, pamnet_stream_t stream) {
-    return tail_fwd_ride(x2, res_x, n, weights, biases, w_out, b_out, w_att, Z, R, x_out, next_Wx1, next_bx1, next_wp, next_ldwp,
-                         next_nblk, next_Zx1, next_x1, next_P, mlp_x, mlp_rows, mlp_tile0, mlp_ntiles, mlp, mlp_out, rider_wgs,
-                         packed, nullptr, stream);
+    if (packed != 1 && packed != 2) return PAMNET_EINVAL;
+    ChainFwd a{};
+    a.x2 = x2, a.res_x = res_x, a.n = n, a.W = weights, a.b = biases, a.w_out = w_out, a.b_out = b_out, a.w_att = w_att;
+    a.Z = Z, a.R = R, a.x_out = x_out, a.packed = packed, a.stream = stream;
+    a.next.Wx1 = next_Wx1, a.next.bx1 = next_bx1, a.next.wp = next_wp, a.next.ldwp = next_ldwp, a.next.nblk = next_nblk;
+    a.next.Zx1 = next_Zx1, a.next.x1 = next_x1, a.next.P = next_P;
+    a.rider.x = mlp_x, a.rider.rows = mlp_rows, a.rider.tile0 = mlp_tile0, a.rider.ntiles = mlp_ntiles, a.rider.wgs = rider_wgs;
+    a.rider.mlp = mlp, a.rider.out = mlp_out;
+    return node_chain_fwd(a);
 }
 
-// pamnet_node_tail_fwd_rider_f32 (mlp_ntiles = 0: without riders) whose chain input x2 is FORMED by the launch -- `agg` holds the
-// operands of pamnet_local_agg_fwd_f32 (out = x2, which is also written); deferred heads, packed images.
+// ... and a chain input x2 FORMED by the launch: `agg` holds the operands of pamnet_local_agg_fwd_f32 (out = x2, also written)
 extern "C" int pamnet_node_tail_fwd_agg_f32(float* x2, const float* res_x, int64_t n, const float* const* weights,
                                             const float* const* biases, const float* w_out, const float* b_out,
                                             const float* w_att, float* Z, float* R, float* x_out, const float* next_Wx1,
@@ -1944,9 +1943,15 @@ extern "C" int pamnet_node_tail_fwd_agg_f32(float* x2, const float* res_x, int64
                                             const float* const* mlp, float* const* mlp_out, int64_t rider_wgs, int32_t packed,
                                             const pamnet_local_agg* agg, pamnet_stream_t stream) {
     if (!agg) return PAMNET_ENULL;
-    return tail_fwd_ride(x2, res_x, n, weights, biases, w_out, b_out, w_att, Z, R, x_out, next_Wx1, next_bx1, next_wp, next_ldwp,
-                         next_nblk, next_Zx1, next_x1, next_P, mlp_x, mlp_rows, mlp_tile0, mlp_ntiles, mlp, mlp_out, rider_wgs,
-                         packed, agg, stream);
+    if (packed != 1 && packed != 2) return PAMNET_EINVAL;
+    ChainFwd a{};
+    a.x2 = x2, a.res_x = res_x, a.n = n, a.W = weights, a.b = biases, a.w_out = w_out, a.b_out = b_out, a.w_att = w_att;
+    a.Z = Z, a.R = R, a.x_out = x_out, a.agg = agg, a.packed = packed, a.stream = stream;
+    a.next.Wx1 = next_Wx1, a.next.bx1 = next_bx1, a.next.wp = next_wp, a.next.ldwp = next_ldwp, a.next.nblk = next_nblk;
+    a.next.Zx1 = next_Zx1, a.next.x1 = next_x1, a.next.P = next_P;
+    a.rider.x = mlp_x, a.rider.rows = mlp_rows, a.rider.tile0 = mlp_tile0, a.rider.ntiles = mlp_ntiles, a.rider.wgs = rider_wgs;
+    a.rider.mlp = mlp, a.rider.out = mlp_out;
+    return node_chain_fwd(a);
 }
 
 extern "C" int pamnet_node_heads_fwd_f32(int64_t n_layers, const float* const* x_out, const float* const* weights,
@@ -1993,12 +1998,10 @@ extern "C" int pamnet_node_tail_bwd_f32(const float* d_xout, const float* d_out,
         return PAMNET_ENULL;
     hipStream_t st = as_stream(stream);
     const unsigned grid = (unsigned)ceil_div(n, BMN);
-    if (packed)
-        hipLaunchKernelGGL((node_tail_bwd_kernel<true, true>), dim3(grid), dim3(TWG), 0, st, d_xout, d_out, d_att, n,
-                           make_tail(weights, nullptr, w_out, nullptr, w_att, 1), Z, dZ, d_x2, d_resx, head_partial);
-    else
-        hipLaunchKernelGGL((node_tail_bwd_kernel<false, true>), dim3(grid), dim3(TWG), 0, st, d_xout, d_out, d_att, n,
-                           make_tail(weights, nullptr, w_out, nullptr, w_att, 0), Z, dZ, d_x2, d_resx, head_partial);
+    const auto kernel = packed ? node_tail_bwd_kernel<true, true> : node_tail_bwd_kernel<false, true>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(TWG), 0, st, d_xout, d_out, d_att, n,
+                       make_tail(weights, 10, nullptr, w_out, nullptr, w_att, packed ? 1 : 0), Z, dZ, d_x2, d_resx, head_partial,
+                       PreBwd{}, WBatchS{}, (float*)nullptr, 0);
     PAMNET_LAUNCH_CHECK();
     if (d_wout || d_watt || d_bout) {      // all null: the caller reduces head_partial itself (pamnet_wgrad_batched_f32)
         if (!d_wout || !d_watt || !d_bout) return PAMNET_ENULL;
@@ -2009,113 +2012,94 @@ extern "C" int pamnet_node_tail_bwd_f32(const float* d_xout, const float* d_out,
     return PAMNET_OK;
 }
 
-extern "C" int pamnet_node_tail_main_bwd_f32(const float* d_xout, const float* g_head, int64_t n,
-                                             const float* const* weights, const float* Z, float* dZ, float* d_x2,
-                                             float* d_resx, int32_t packed, pamnet_stream_t stream) {
-    if (n < 0) return PAMNET_EINVAL;
-    if (n == 0) return PAMNET_OK;
-    if (!g_head || !weights || !Z || !dZ || !d_x2 || !d_resx) return PAMNET_ENULL;
+/* The backward chain without the head branch (differentiated by pamnet_node_heads_bwd_f32: g_head is its d x_out), optionally
+ * preceded, on the same row tiles, by the backward of the next layer's head (a.head: pamnet_node_pre_bwd_f32 with its d x
+ * feeding this chain's d x_out, so there is no d_xout then; weight images only). */
+int node_chain::node_chain_bwd(const ChainBwd& a) {
+    const HeadBwd* h = a.head;
+    if (a.n < 0 || (h && (h->nblk < 1 || h->nblk > 4))) return PAMNET_EINVAL;
+    if (h ? (a.d_xout || (a.packed != 1 && a.packed != 2)) : a.rider != nullptr) return PAMNET_EINVAL;
+    if (a.n == 0) return PAMNET_OK;
+    if (!a.g_head || !a.W || !a.Z || !a.dZ || !a.d_x2 || !a.d_resx) return PAMNET_ENULL;
     for (int k = 0; k < 7; ++k)
-        if (!weights[k]) return PAMNET_ENULL;
-    hipStream_t st = as_stream(stream);
-    const unsigned grid = (unsigned)ceil_div(n, BMN);
-    TailParams tp{};
-    for (int k = 0; k < 7; ++k) tp.W[k] = weights[k];
-    tp.packed = packed ? 1 : 0;
-    if (packed == 2)                                          // bf16x3 (kind-1, transposed) images: the bf16x6 chain
-        hipLaunchKernelGGL((node_tail_bwd_bf16_kernel<false>), dim3(grid), dim3(TWG), 0, st, d_xout, g_head, n, tp, Z, dZ, d_x2,
-                           d_resx);
-    else if (packed && grid > LEAN_FROM_TILES && lean_mode() >= 2)
-        hipLaunchKernelGGL((node_tail_bwd_lean_kernel<false>), dim3(grid), dim3(TWG), 0, st, d_xout, g_head, n, tp, Z, dZ, d_x2,
-                           d_resx, PreBwd{});
-    else if (packed)
-        hipLaunchKernelGGL((node_tail_bwd_kernel<true, false>), dim3(grid), dim3(TWG), 0, st, d_xout, g_head,
-                           (const float*)nullptr, n, tp, Z, dZ, d_x2, d_resx, (float*)nullptr);
-    else
-        hipLaunchKernelGGL((node_tail_bwd_kernel<false, false>), dim3(grid), dim3(TWG), 0, st, d_xout, g_head,
-                           (const float*)nullptr, n, tp, Z, dZ, d_x2, d_resx, (float*)nullptr);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
-}
-
-/* tail_main_bwd preceded, on the same row tiles, by the backward of the next layer's head (pamnet_node_pre_bwd_f32 with
- * its d x feeding this chain's d x_out; d_xout of the chain is that d x, so there is no d_xout argument).  Packed
- * (transposed-orientation) weight images only. */
-static int node_pre_tail_bwd_impl(float* dP, const float* const* gsrc, const int32_t* const* gptr,
-                                  const int32_t* const* gperm, const float* dx1_direct, const float* d_add, int64_t n,
-                                  const float* Wx1, const float* const* wp, int64_t nblk, const float* Zx1,
-                                  float* dZx1, const float* g_head, const float* const* weights,
-                                  const float* Z, float* dZ, float* d_x2, float* d_resx,
-                                  const void* rider, pamnet_stream_t stream) {
-    const bool pieces = nblk >= 0 && (nblk & PAMNET_CHAIN_PIECES) != 0;      // every image a bf16x3 (kind-1) one: the bf16x6 chain
-    if (pieces) nblk &= ~(int64_t)PAMNET_CHAIN_PIECES;
-    if (n < 0 || nblk < 1 || nblk > 4) return PAMNET_EINVAL;
-    if (n == 0) return PAMNET_OK;
-    if (!dP || !dx1_direct || !d_add || !Wx1 || !wp || !Zx1 || !dZx1 || !g_head || !weights || !Z || !dZ || !d_x2 || !d_resx)
-        return PAMNET_ENULL;
+        if (!a.W[k]) return PAMNET_ENULL;
     PreBwd pb{};
-    pb.dP = dP, pb.Wx1 = Wx1, pb.Zx1 = Zx1, pb.dx1_direct = dx1_direct, pb.d_add = d_add, pb.dZx1 = dZx1;
-    pb.nblk = (int)nblk;
-    pb.dP_out = dP;
     bool any_gather = false;
-    for (int b = 0; b < nblk; ++b) {
-        if (!wp[b]) return PAMNET_ENULL;
-        pb.wp[b] = wp[b];
-        if (gsrc && gsrc[b]) {
-            if (!gptr || !gptr[b]) return PAMNET_ENULL;
-            pb.gsrc[b] = gsrc[b], pb.gptr[b] = gptr[b], pb.gperm[b] = gperm ? gperm[b] : nullptr;
-            any_gather = true;
+    if (h) {
+        if (!h->dP || !h->dx1_direct || !h->d_add || !h->Wx1 || !h->wp || !h->Zx1 || !h->dZx1) return PAMNET_ENULL;
+        pb.dP = h->dP, pb.Wx1 = h->Wx1, pb.Zx1 = h->Zx1, pb.dx1_direct = h->dx1_direct, pb.d_add = h->d_add, pb.dZx1 = h->dZx1;
+        pb.nblk = (int)h->nblk;
+        pb.dP_out = h->dP;
+        for (int b = 0; b < h->nblk; ++b) {
+            if (!h->wp[b]) return PAMNET_ENULL;
+            pb.wp[b] = h->wp[b];
+            if (h->gather_src && h->gather_src[b]) {
+                if (!h->gather_ptr || !h->gather_ptr[b]) return PAMNET_ENULL;
+                pb.gsrc[b] = h->gather_src[b], pb.gptr[b] = h->gather_ptr[b];
+                pb.gperm[b] = h->gather_perm ? h->gather_perm[b] : nullptr;
+                any_gather = true;
+            }
         }
     }
-    TailParams tp{};
-    for (int k = 0; k < 7; ++k) {
-        if (!weights[k]) return PAMNET_ENULL;
-        tp.W[k] = weights[k];
-    }
-    tp.packed = 1;
-    const int n_tiles = (int)ceil_div(n, BMN);
     WBatchS rb{};
     float* rpart = nullptr;
     int rslots = 0;
-    if (rider) {                                              // planned by pamnet_wgrad_rider_plan_f32
-        const WgradRider* r = static_cast<const WgradRider*>(rider);
+    if (a.rider) {                                            // planned by pamnet_wgrad_rider_plan_f32
+        const WgradRider* r = static_cast<const WgradRider*>(a.rider);
         rb = r->batch, rpart = r->partial, rslots = r->slots;
     }
-    const bool lean = !pieces && rslots == 0 && (unsigned)n_tiles > LEAN_FROM_TILES && lean_mode() >= 2;
-    if (lean && any_gather) {
-        // the lean form reads its planes: form them with the batched segment-sum launch first (what the engine did until round 6)
+
+    const int n_tiles = (int)ceil_div(a.n, BMN);
+    const BwdPlan plan = plan_bwd(n_tiles, a.packed, h != nullptr, rslots, any_gather);
+    const TailParams tp = make_tail(a.W, 7, nullptr, nullptr, nullptr, nullptr, a.packed ? 1 : 0);
+    if (any_gather && !plan.gather_in_kernel) {
         float* so[4];
         const float* sa[4];
         const int32_t *sp[4], *sr[4];
         int64_t nj = 0;
-        for (int b = 0; b < nblk; ++b)
-            if (pb.gsrc[b]) so[nj] = dP + (int64_t)b * n * DIM, sa[nj] = pb.gsrc[b], sp[nj] = pb.gperm[b], sr[nj] = pb.gptr[b], ++nj;
-        const int rc = pamnet_segment_sum_multi_f32(nj, so, sa, sp, sr, n, DIM, stream);
+        for (int b = 0; b < pb.nblk; ++b)
+            if (pb.gsrc[b]) so[nj] = h->dP + (int64_t)b * a.n * DIM, sa[nj] = pb.gsrc[b], sp[nj] = pb.gperm[b], sr[nj] = pb.gptr[b], ++nj;
+        const int rc = pamnet_segment_sum_multi_f32(nj, so, sa, sp, sr, a.n, DIM, a.stream);
         if (rc) return rc;
         for (int b = 0; b < 4; ++b) pb.gsrc[b] = nullptr;
     }
-    if (pieces)
-        hipLaunchKernelGGL((node_tail_bwd_bf16_kernel<true>), dim3((unsigned)(n_tiles + rslots)), dim3(TWG), 0, as_stream(stream),
-                           (const float*)nullptr, g_head, n, tp, Z, dZ, d_x2, d_resx, pb, rb, rpart, n_tiles);
-    else if (lean)
-        hipLaunchKernelGGL((node_tail_bwd_lean_kernel<true>), dim3((unsigned)n_tiles), dim3(TWG), 0, as_stream(stream),
-                           (const float*)nullptr, g_head, n, tp, Z, dZ, d_x2, d_resx, pb);
-    else
-        hipLaunchKernelGGL((node_tail_bwd_kernel<true, false, true>), dim3((unsigned)(n_tiles + rslots)), dim3(TWG), 0,
-                           as_stream(stream), (const float*)nullptr, g_head, (const float*)nullptr, n, tp, Z, dZ, d_x2, d_resx,
-                           (float*)nullptr, pb, rb, rpart, n_tiles);
+    hipStream_t st = as_stream(a.stream);
+    const dim3 grid((unsigned)(n_tiles + plan.rider_slots)), block(TWG);
+    switch (plan.form) {
+    case ChainForm::RowMajor:
+    case ChainForm::Parked: {
+        const auto kernel = plan.form == ChainForm::RowMajor ? node_tail_bwd_kernel<false, false>
+                            : plan.pre                       ? node_tail_bwd_kernel<true, false, true>
+                                                             : node_tail_bwd_kernel<true, false>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, a.d_xout, a.g_head, (const float*)nullptr, a.n, tp, a.Z, a.dZ, a.d_x2,
+                           a.d_resx, (float*)nullptr, pb, rb, rpart, n_tiles);      // (d_att, head_partial: the HEADS forms' only)
+        break;
+    }
+    case ChainForm::Lean: {
+        const auto kernel = plan.pre ? node_tail_bwd_lean_kernel<true> : node_tail_bwd_lean_kernel<false>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, a.d_xout, a.g_head, a.n, tp, a.Z, a.dZ, a.d_x2, a.d_resx, pb);
+        break;
+    }
+    case ChainForm::Bf16: {
+        const auto kernel = plan.pre ? node_tail_bwd_bf16_kernel<true> : node_tail_bwd_bf16_kernel<false>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, a.d_xout, a.g_head, a.n, tp, a.Z, a.dZ, a.d_x2, a.d_resx, pb, rb, rpart,
+                           n_tiles);
+        break;
+    }
+    }
     PAMNET_LAUNCH_CHECK();
     return PAMNET_OK;
 }
 
-extern "C" int pamnet_node_pre_tail_bwd_f32(const float* dP, const float* dx1_direct, const float* d_add, int64_t n,
-                                            const float* Wx1, const float* const* wp, int64_t nblk, const float* Zx1,
-                                            float* dZx1, const float* g_head, const float* const* weights,
-                                            const float* Z, float* dZ, float* d_x2, float* d_resx,
-                                            const void* rider, pamnet_stream_t stream) {
-    return node_pre_tail_bwd_impl(const_cast<float*>(dP), nullptr, nullptr, nullptr, dx1_direct, d_add, n, Wx1, wp, nblk, Zx1, dZx1,
-                                  g_head, weights, Z, dZ, d_x2, d_resx, rider, stream);
+extern "C" int pamnet_node_tail_main_bwd_f32(const float* d_xout, const float* g_head, int64_t n,
+                                             const float* const* weights, const float* Z, float* dZ, float* d_x2,
+                                             float* d_resx, int32_t packed, pamnet_stream_t stream) {
+    ChainBwd a{};
+    a.d_xout = d_xout, a.g_head = g_head, a.n = n, a.W = weights, a.Z = Z;
+    a.dZ = dZ, a.d_x2 = d_x2, a.d_resx = d_resx, a.packed = packed, a.stream = stream;
+    return node_chain_bwd(a);
 }
+
 /* The same with planes of dP formed inside the launch: gather_src[b] != null -> plane b (written to dP + b n 128 as well) is the
  * segment sum of gather_src[b] over (gather_ptr[b], gather_perm[b] nullable) -- the launches of pamnet_segment_sum(_multi)_f32
  * that used to run ahead of this one. */
@@ -2127,8 +2111,28 @@ extern "C" int pamnet_node_pre_tail_bwd_gather_f32(float* dP, const float* const
                                                    float* dZ, float* d_x2, float* d_resx, const void* rider,
                                                    pamnet_stream_t stream) {
     if (!gather_src || !gather_ptr) return PAMNET_ENULL;
-    return node_pre_tail_bwd_impl(dP, gather_src, gather_ptr, gather_perm, dx1_direct, d_add, n, Wx1, wp, nblk, Zx1, dZx1, g_head,
-                                  weights, Z, dZ, d_x2, d_resx, rider, stream);
+    const bool pieces = nblk >= 0 && (nblk & PAMNET_CHAIN_PIECES) != 0;      // every image a bf16x3 (kind-1) one: the bf16x6 chain
+    HeadBwd h{};
+    h.dP = dP, h.gather_src = gather_src, h.gather_ptr = gather_ptr, h.gather_perm = gather_perm;
+    h.dx1_direct = dx1_direct, h.d_add = d_add, h.Wx1 = Wx1, h.wp = wp, h.Zx1 = Zx1, h.dZx1 = dZx1;
+    h.nblk = pieces ? nblk & ~(int64_t)PAMNET_CHAIN_PIECES : nblk;
+    ChainBwd a{};
+    a.g_head = g_head, a.n = n, a.W = weights, a.Z = Z, a.dZ = dZ, a.d_x2 = d_x2, a.d_resx = d_resx;
+    a.packed = pieces ? 2 : 1, a.head = &h, a.rider = rider, a.stream = stream;
+    return node_chain_bwd(a);
+}
+/* tail_main_bwd preceded, on the same row tiles, by the backward of the next layer's head (pamnet_node_pre_bwd_f32 with
+ * its d x feeding this chain's d x_out; d_xout of the chain is that d x, so there is no d_xout argument).  Packed
+ * (transposed-orientation) weight images only.  Every plane of dP is read: the launch above with nothing to gather. */
+extern "C" int pamnet_node_pre_tail_bwd_f32(const float* dP, const float* dx1_direct, const float* d_add, int64_t n,
+                                            const float* Wx1, const float* const* wp, int64_t nblk, const float* Zx1,
+                                            float* dZx1, const float* g_head, const float* const* weights,
+                                            const float* Z, float* dZ, float* d_x2, float* d_resx,
+                                            const void* rider, pamnet_stream_t stream) {
+    static const float* const no_src[4] = {};
+    static const int32_t* const no_ptr[4] = {};
+    return pamnet_node_pre_tail_bwd_gather_f32(const_cast<float*>(dP), no_src, no_ptr, nullptr, dx1_direct, d_add, n, Wx1, wp, nblk,
+                                               Zx1, dZx1, g_head, weights, Z, dZ, d_x2, d_resx, rider, stream);
 }
 
 extern "C" int pamnet_node_heads_bwd_f32(int64_t n_layers, const float* const* d_out, const float* const* d_att,

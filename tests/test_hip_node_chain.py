@@ -21,8 +21,8 @@ message weights; 128 otherwise), weight images are packed from those strided sli
 forwards also without their optional saves (same bits in the required outputs), backwards with the next head in front both in
 place (d_x2 is dx1_direct, d_resx is d_add: the engine's call) and with separate buffers (same bits).
 
-Regimes.  fwd_kernel / agg_in_kernel / main_bwd_kernel / pre_tail_bwd_kernel below MIRROR the host code of node_tail.hip
-(tail_fwd_launch, pamnet_node_tail_main_bwd_f32, node_pre_tail_bwd_impl); the tables FWD_TABLE / BWD_TABLE name the kernel every
+Regimes.  fwd_kernel / agg_in_kernel / main_bwd_kernel / pre_tail_bwd_kernel below MIRROR the launch plans of node_tail.hip
+(plan_fwd and plan_bwd, with the launches of node_chain_fwd / node_chain_bwd); the tables FWD_TABLE / BWD_TABLE name the kernel every
 parametrised row count is meant to reach and are asserted first, with the bound itself (common.h PARKED_TILES_MAX = 256 row
 tiles, read from the source; PLAN_BOUNDS of test_hip_model.py): a changed bound makes the tables fail as stale.
     rows <= 4096 (256 tiles)      packed = 1, deferred heads: node_tail_fwd_kernel<true, false> (parked);  backward: node_tail_bwd_kernel
@@ -42,7 +42,7 @@ the floor of the rule (2e-6 forward, 5e-6 backward) decided every case, 2 x torc
     main_bwd rowmajor / images (parked and lean)  (3.8e-7, 4.4e-7)                                  bf16x6  (3.2e-7, 6.0e-7)
     pre_tail_bwd images (parked and lean)  (3.9e-7, 4.8e-7)                                         bf16x6  (3.3e-7, 4.6e-7)
     pre_tail_bwd_gather images  (3.6e-7, 3.8e-7)                                                    bf16x6  (3.6e-7, 5.8e-7)
-(row-major matrices and images gave the same worst figures throughout.)  The whole file: 126 tests, 16 s.
+(row-major matrices and images gave the same worst figures throughout.)  The whole file: 134 tests, 15 s.
 
 FOUND BY test_gathered_planes (all four cases; with PAMNET_CHAIN_LEAN=0 also by test_gathered_planes_4097): the planes
 pamnet_node_pre_tail_bwd_gather_f32 forms inside its launch met fp64 but were not the bits of pamnet_segment_sum_multi_f32 in
@@ -96,7 +96,7 @@ def _tiles(n):
 
 
 def fwd_kernel(packed, heads, n, rider=False):
-    """node_tail.hip tail_fwd_launch: the kernel a forward launch gets."""
+    """node_tail.hip plan_fwd and the launch of node_chain_fwd: the kernel a forward launch gets."""
     if packed == 2:
         return 'node_tail_fwd_bf16_kernel<%s, %d>' % ('true' if rider else 'false', WAVES)
     if rider:
@@ -111,12 +111,12 @@ def fwd_kernel(packed, heads, n, rider=False):
 
 
 def agg_in_kernel(packed, n, rider=False):
-    """node_tail.hip tail_fwd_launch (`in_kernel`): does the chain launch form x2 itself?"""
+    """node_tail.hip plan_fwd (`agg_in_kernel`, for packed images and deferred heads): does the chain launch form x2 itself?"""
     return packed == 2 or not (_tiles(n) > PARKED_TILES_MAX and LEAN >= 1 and not rider)
 
 
 def main_bwd_kernel(packed, n):
-    """node_tail.hip pamnet_node_tail_main_bwd_f32."""
+    """node_tail.hip plan_bwd and the launch of node_chain_bwd, without a head (pamnet_node_tail_main_bwd_f32)."""
     if packed == 2:
         return 'node_tail_bwd_bf16_kernel<false>'
     if packed and _tiles(n) > PARKED_TILES_MAX and LEAN >= 2:
@@ -125,7 +125,7 @@ def main_bwd_kernel(packed, n):
 
 
 def pre_tail_bwd_kernel(pieces, n):
-    """node_tail.hip node_pre_tail_bwd_impl (no riders)."""
+    """node_tail.hip plan_bwd and the launch of node_chain_bwd, with a head and no riders (pamnet_node_pre_tail_bwd_f32)."""
     if pieces:
         return 'node_tail_bwd_bf16_kernel<true>'
     if _tiles(n) > PARKED_TILES_MAX and LEAN >= 2:
@@ -620,6 +620,21 @@ def test_forward_chain(dev, n, form):
     _report(entry)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize('packed', [1, 2])
+@pytest.mark.parametrize('n', [17, 4097])
+def test_forward_entry_points_agree(dev, n, packed):
+    """pamnet_node_tail_fwd_f32 with out = att = null and pamnet_node_tail_fwd_rider_f32 with mlp_ntiles = 0 fill the same record
+    (node_chain_args.h ChainFwd) and reach the same launch: every output has the same bits.  17 rows: a partial tile in the parked
+    plan; 4 097: the first row count of the lean plan."""
+    s = _fwd_set(dev, n)
+    a = _fwd_run(s, packed, False, 2)
+    b = _fwd_run(s, packed, False, 2, entry='pamnet_node_tail_fwd_rider_f32')
+    assert not bool(torch.isnan(a['x_out'].v).any()) and not bool(torch.isnan(a['P'].v[:2]).any())
+    for k in ('Z', 'R', 'x_out', 'Zx1', 'x1', 'P'):
+        assert _eq(a[k].v, b[k].v), (n, packed, k)
+
+
 # ------------------------------------------------------------------------------------------ 6. riders on the fp32 chain
 @pytest.mark.gpu
 @pytest.mark.parametrize('tile0,ntiles,wgs', [(0, 7, 3), (3, 4, 9), (6, 1, 1)])
@@ -1065,6 +1080,21 @@ def test_pre_tail_backward(dev, n, pieces):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('pieces', [False, True])
+@pytest.mark.parametrize('n', [17, 4097])
+def test_backward_entry_points_agree(dev, n, pieces):
+    """pamnet_node_pre_tail_bwd_f32 and pamnet_node_pre_tail_bwd_gather_f32 with every gather_src[b] null fill the same record
+    (node_chain_args.h ChainBwd) and reach the same launch: dZ, dZx1, d_x2 and d_resx have the same bits (nblk = 2)."""
+    s = _bwd_set(dev, n)
+    a = _pre_tail_run(s, 2, pieces, False)
+    b = _pre_tail_run(s, 2, pieces, False, gather=([None, None], [None, None], [None, None]))
+    assert all(v.guards_intact() for v in list(a.values()) + list(b.values()))
+    assert not bool(torch.isnan(a['d_x2'].v).any()) and not bool(torch.isnan(a['dZ'].v[:7]).any())
+    for k in PRE_TAIL_OUT:
+        assert _eq(a[k].v, b[k].v), (n, pieces, k)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize('packed', [0, 1])
 @pytest.mark.parametrize('n', [1, 17, 37])
 def test_pre_backward(dev, n, packed):
@@ -1203,6 +1233,13 @@ def test_argument_errors(dev):
         _call('pamnet_node_tail_fwd_rider_f32', x2, base[0], 0, *base[2:], *nxt(2), *mlp, 1, st)
     with pytest.raises(RuntimeError, match='ENULL'):          # agg = null
         _call('pamnet_node_tail_fwd_agg_f32', x2, *base, *nxt(2), *no_rider, 1, None, st)
+    # an invalid rider request (row-major matrices) together with an aggregation: refused before the aggregation is launched
+    lg, W0 = _LocalGraph(dev, n), s.wt.ptrs(0, 0)[0]
+    o['x2'], o['m_t'] = _Out(dev, n, D), _Out(dev, lg.E, D)
+    agg = _Agg(lg.m_ji.data_ptr(), lg.m_nb.data_ptr(), lg.s.data_ptr(), lg.q3.data_ptr(), lg.init.data_ptr(), lg.t_ptr.data_ptr(),
+               lg.t_col.data_ptr(), lg.l_ptr.data_ptr(), o['m_t'].p)
+    with pytest.raises(RuntimeError, match='EINVAL'):
+        _call('pamnet_node_tail_fwd_agg_f32', o['x2'].p, base[0], n, _parr(W0), *base[3:], *nxt(2), *mlp, 0, ctypes.addressof(agg), st)
     holed = list(W1)
     holed[4] = None
     with pytest.raises(RuntimeError, match='ENULL'):          # a null entry among the ten weights
