@@ -406,6 +406,19 @@ int pamnet_mol_graph_free_fill_i32(const float* pos, const int32_t* gptr, int64_
                                    float cutoff_l, float cutoff_g, int32_t with_triplets, int32_t need_grad,
                                    const int32_t* mol_tot, int64_t eg_cap, int64_t tp_cap, const pamnet_mol_graph_out* out,
                                    pamnet_stream_t stream);
+/* The bond-free form under periodic cells: cell_table [n_graphs, 18] from pamnet_cell_prepare_f64 (prepared for max(cutoff_l,
+ * cutoff_g): under that minimum-image condition both graphs are still simple symmetric graphs on the molecule's atoms).  Every
+ * distance is the minimum-image one by the rule and arithmetic of pamnet_radius_pbc_count/fill_i32, every angle that of
+ * pamnet_triplet_fill_pbc_f32; everything else -- arguments, validation, limits, mol_tot / totals, violation bits -- as in
+ * the two entry points above, and every array bit-identical to what the step-by-step periodic entry points give.  The
+ * kernels stay inside their arrays for any table content (a singular cell's inf / NaN distances pass no cutoff test). */
+int pamnet_mol_graph_pbc_count_i32(const float* pos, const double* cell_table, const int32_t* gptr, int64_t n, int64_t n_graphs,
+                                   float cutoff_l, float cutoff_g, int32_t with_triplets, int32_t* mol_tot, int32_t* totals,
+                                   pamnet_stream_t stream);
+int pamnet_mol_graph_pbc_fill_i32(const float* pos, const double* cell_table, const int32_t* gptr, int64_t n, int64_t n_graphs,
+                                  int64_t n_local, float cutoff_l, float cutoff_g, int32_t with_triplets, int32_t need_grad,
+                                  const int32_t* mol_tot, int64_t eg_cap, int64_t tp_cap, const pamnet_mol_graph_out* out,
+                                  pamnet_stream_t stream);
 
 int pamnet_graph_plan(const pamnet_graph_desc* desc, int64_t* layout /* [PAMNET_GRAPH_FIELDS] */, int64_t* arena_ints);
 int pamnet_graph_build_i32(const pamnet_graph_desc* desc, int32_t* arena, float* sbf /* [tp, 42], nullable */,

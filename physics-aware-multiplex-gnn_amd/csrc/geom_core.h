@@ -105,6 +105,9 @@ constexpr int IMG_BOX_MAX = 4;        // largest half-width of the candidate box
 struct OpenSpace {
     __device__ __forceinline__ void bind(int) {}
     __device__ __forceinline__ float dist(const float* __restrict__ pos, int64_t a, int64_t b) const { return dist3(pos, a, b); }
+    __device__ __forceinline__ float dist(float ax, float ay, float az, float bx, float by, float bz) const {
+        return dist3_xyz(ax, ay, az, bx, by, bz);
+    }
     __device__ __forceinline__ void sub(float ax, float ay, float az, float bx, float by, float bz, float& x, float& y,
                                         float& z) const {
         x = ax - bx, y = ay - by, z = az - bz;
@@ -117,6 +120,10 @@ struct Periodic {
     __device__ __forceinline__ void bind(int g) { t = load_cell(table, g); }
     __device__ __forceinline__ float dist(const float* __restrict__ pos, int64_t a, int64_t b) const {
         const Disp d = min_image(t, pos, a, b);
+        return dist3_xyz((float)d.x, (float)d.y, (float)d.z, 0.f, 0.f, 0.f);
+    }
+    __device__ __forceinline__ float dist(float ax, float ay, float az, float bx, float by, float bz) const {
+        const Disp d = min_image(t, ax, ay, az, bx, by, bz);  // (the same statements on positions held in registers)
         return dist3_xyz((float)d.x, (float)d.y, (float)d.z, 0.f, 0.f, 0.f);
     }
     __device__ __forceinline__ void sub(float ax, float ay, float az, float bx, float by, float bz, float& x, float& y,

@@ -22,6 +22,17 @@
 // ascending -- ARE the bonds in CSR order of their targets: no input reads, no bond range, no stray-bond check; everything
 // behind that point runs unchanged.  The local edge count of a molecule is data dependent: the count launch leaves it in
 // mol_tot[g, 2] (where the bonded form keeps the first bond) and the fill launch sums the preceding molecules' counts.
+//
+// Periodic form (pamnet_mol_graph_pbc_*): the bond-free form with the geometry policy Periodic (geom_core.h) in place of
+// OpenSpace.  Under the minimum-image condition the cell table was prepared for (every height above 2 * max(cutoff_l,
+// cutoff_g)) a pair has at most one image within either cutoff, so both graphs of a cell are still simple symmetric graphs on
+// its <= 64 atoms and the masks carry over as they are.  The policy supplies the displacement in three places -- the masks'
+// distance test, the edge lengths, the two vectors of every angle -- with the argument order of pamnet_radius_pbc_* and
+// pamnet_triplet_fill_pbc_f32 (bit-identical arrays: tests/test_pbc_builder.py); everything else works on indices.  The
+// cell row of a wavefront's molecule is wave-uniform: 18 doubles in scalar registers, one bind per wavefront.  The all-image
+// global graph (cell_images='all') is a multigraph whose rows repeat columns and exceed 64 entries: not a mask, not built here.
+#include <type_traits>
+
 #include "common.h"
 #include "geom_core.h"
 
@@ -83,22 +94,26 @@ __device__ __forceinline__ void bond_range(const int32_t* __restrict__ dst, int 
 }
 
 // Adjacency masks of this lane's atom inside its molecule at cutoff_g (and, bond-free form, at cutoff_l): the rule and
-// arithmetic of pamnet_radius_count/fill_i32 (self excluded, d <= r on the rounded fp32 distance).
-template <bool FREE>
-__device__ __forceinline__ void radius_masks(float xi, float yi, float zi, int lane, int na, float cutoff_g, float cutoff_l,
-                                             unsigned long long& mask, unsigned long long& lmask) {
+// arithmetic of pamnet_radius_count/fill_i32 (self excluded, d <= r on the rounded fp32 distance) -- under GEOM = Periodic of
+// pamnet_radius_pbc_count/fill_i32: the distance of the minimum image, query first.  A NaN distance (a singular cell's table)
+// fails both comparisons: no bit is set.
+template <bool FREE, class GEOM>
+__device__ __forceinline__ void radius_masks(const GEOM& geom, float xi, float yi, float zi, int lane, int na, float cutoff_g,
+                                             float cutoff_l, unsigned long long& mask, unsigned long long& lmask) {
     mask = lmask = 0ull;
     for (int j = 0; j < na; ++j) {
-        const float d = dist3_xyz(xi, yi, zi, lane_value(xi, j), lane_value(yi, j), lane_value(zi, j));
+        const float d = geom.dist(xi, yi, zi, lane_value(xi, j), lane_value(yi, j), lane_value(zi, j));
         if (j != lane && lane < na && d <= cutoff_g) mask |= 1ull << j;
         if (FREE && j != lane && lane < na && d <= cutoff_l) lmask |= 1ull << j;
     }
 }
 
-template <bool FILL, bool FREE>
+// GEOM (geom_core.h): OpenSpace, or Periodic (bond-free form only) with `cells` = the batch's cell table; bound once per
+// wavefront to the molecule's row, which is wave-uniform: cell and inverse live in scalar registers.
+template <bool FILL, bool FREE, class GEOM>
 __global__ __launch_bounds__(64) void mol_graph_kernel(MolIn in, int32_t* __restrict__ mol_tot,
                                                        int32_t* __restrict__ totals, pamnet_mol_graph_out out,
-                                                       int64_t eg_cap, int64_t tp_cap) {
+                                                       int64_t eg_cap, int64_t tp_cap, const double* __restrict__ cells) {
     __shared__ float px[MOL_ATOMS], py[MOL_ATOMS], pz[MOL_ATOMS];
     __shared__ int l_src[MOL_BONDS], l_dst[MOL_BONDS];        // bonds in CSR order of their targets (stable)
     __shared__ int lt[MOL_BONDS];                             // ... listed by source atom (the transposed list)
@@ -138,6 +153,9 @@ __global__ __launch_bounds__(64) void mol_graph_kernel(MolIn in, int32_t* __rest
         }
         return;
     }
+    GEOM geom;
+    if constexpr (std::is_same<GEOM, Periodic>::value) geom.table = cells;
+    geom.bind(g);
     float xi = 0.f, yi = 0.f, zi = 0.f;
     if (lane < na) {
         const int64_t a = a0 + lane;
@@ -147,7 +165,7 @@ __global__ __launch_bounds__(64) void mol_graph_kernel(MolIn in, int32_t* __rest
     unsigned long long mask = 0ull, lmask = 0ull;
     if constexpr (FREE) {
         // ---- both radius graphs' adjacency masks; the local one's bits are the bonds in CSR order of their targets
-        radius_masks<true>(xi, yi, zi, lane, na, in.cutoff_g, in.cutoff_l, mask, lmask);
+        radius_masks<true>(geom, xi, yi, zi, lane, na, in.cutoff_g, in.cutoff_l, mask, lmask);
         const int ldeg = __popcll(lmask);
         const int linc = wave_incl(ldeg, lane);
         nb = __shfl(linc, 63, 64);
@@ -253,7 +271,7 @@ __global__ __launch_bounds__(64) void mol_graph_kernel(MolIn in, int32_t* __rest
     const int tp_m = carry;
 
     // ---- radius graph inside the molecule: adjacency masks + degrees
-    if constexpr (!FREE) radius_masks<false>(xi, yi, zi, lane, na, in.cutoff_g, 0.f, mask, lmask);
+    if constexpr (!FREE) radius_masks<false>(geom, xi, yi, zi, lane, na, in.cutoff_g, 0.f, mask, lmask);
     const int deg = __popcll(mask);
     const int ginc = wave_incl(deg, lane);
     const int eg_m = __shfl(ginc, 63, 64);
@@ -296,18 +314,21 @@ __global__ __launch_bounds__(64) void mol_graph_kernel(MolIn in, int32_t* __rest
         const float pix = px[i], piy = py[i], piz = pz[i], pjx = px[j], pjy = py[j], pjz = pz[j];
         out.l_row[b0 + k] = a0 + i;
         out.l_col[b0 + k] = a0 + j;
-        out.l_dist[b0 + k] = dist3_xyz(pix, piy, piz, pjx, pjy, pjz);
+        out.l_dist[b0 + k] = geom.dist(pix, piy, piz, pjx, pjy, pjz);
         int64_t w = toff + tptr[k];
         out.t_ptr[b0 + k] = (int32_t)(w < tp_cap ? w : tp_cap);
+        float ux, uy, uz, vx, vy, vz;
         if (in.with_triplets) {
-            for (int q = lptr[j]; q < lptr[j + 1]; ++q) {       // pamnet_triplet_fill_f32, same expressions
+            for (int q = lptr[j]; q < lptr[j + 1]; ++q) {       // pamnet_triplet_fill(_pbc)_f32, same expressions
                 const int kk = l_src[q];
                 if (kk == i) continue;
                 if (w < tp_cap) {
                     out.t_col[w] = b0 + q;
                     out.t_row[w] = b0 + k;
                     out.t_kind[w] = 0;
-                    out.t_angle[w] = angle3(pjx - pix, pjy - piy, pjz - piz, px[kk] - pjx, py[kk] - pjy, pz[kk] - pjz);
+                    geom.sub(pjx, pjy, pjz, pix, piy, piz, ux, uy, uz);
+                    geom.sub(px[kk], py[kk], pz[kk], pjx, pjy, pjz, vx, vy, vz);
+                    out.t_angle[w] = angle3(ux, uy, uz, vx, vy, vz);
                 }
                 ++w;
             }
@@ -318,7 +339,9 @@ __global__ __launch_bounds__(64) void mol_graph_kernel(MolIn in, int32_t* __rest
                 out.t_col[w] = b0 + q;
                 out.t_row[w] = b0 + k;
                 out.t_kind[w] = 1;
-                out.t_angle[w] = angle3(pix - pjx, piy - pjy, piz - pjz, px[j2] - pix, py[j2] - piy, pz[j2] - piz);
+                geom.sub(pix, piy, piz, pjx, pjy, pjz, ux, uy, uz);
+                geom.sub(px[j2], py[j2], pz[j2], pix, piy, piz, vx, vy, vz);
+                out.t_angle[w] = angle3(ux, uy, uz, vx, vy, vz);
             }
             ++w;
         }
@@ -336,7 +359,7 @@ __global__ __launch_bounds__(64) void mol_graph_kernel(MolIn in, int32_t* __rest
             if (w < eg_cap) {
                 out.g_row[w] = a0 + lane;
                 out.g_col[w] = a0 + j;
-                out.g_dist[w] = dist3_xyz(xi, yi, zi, px[j], py[j], pz[j]);
+                out.g_dist[w] = geom.dist(xi, yi, zi, px[j], py[j], pz[j]);
                 if (in.need_grad) {                             // (clamped: wrong sizes must stay inside the arrays)
                     const int64_t rv = eoff + gex[j] + __popcll(adj[j] & ((1ull << lane) - 1ull));
                     out.gT_perm[w] = (int32_t)(rv < eg_cap ? rv : eg_cap - 1);
@@ -417,6 +440,43 @@ int check_free(const float* pos, const int32_t* gptr, int64_t n, int64_t n_graph
     return PAMNET_OK;
 }
 
+// The two launches of the bond-free form, for either policy (`cells`: the cell table of the periodic one, else null).
+template <class GEOM>
+int free_count(const float* pos, const double* cells, const int32_t* gptr, int64_t n, int64_t n_graphs, float cutoff_l,
+               float cutoff_g, int32_t with_triplets, int32_t* mol_tot, int32_t* totals, pamnet_stream_t stream) {
+    const int rc = check_free(pos, gptr, n, n_graphs, 0, cutoff_l, cutoff_g);
+    if (rc) return rc;
+    if (!mol_tot || !totals) return PAMNET_ENULL;
+    const MolIn in{pos, gptr, nullptr, nullptr, n, n_graphs, 0, cutoff_g, with_triplets ? 1 : 0, 0, cutoff_l};
+    const pamnet_mol_graph_out none{};
+    hipLaunchKernelGGL((mol_graph_kernel<false, true, GEOM>), dim3((unsigned)n_graphs), dim3(64), 0, as_stream(stream), in,
+                       mol_tot, totals, none, (int64_t)0, (int64_t)0, cells);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
+template <class GEOM>
+int free_fill(const float* pos, const double* cells, const int32_t* gptr, int64_t n, int64_t n_graphs, int64_t n_local,
+              float cutoff_l, float cutoff_g, int32_t with_triplets, int32_t need_grad, const int32_t* mol_tot, int64_t eg_cap,
+              int64_t tp_cap, const pamnet_mol_graph_out* out, pamnet_stream_t stream) {
+    const int rc = check_free(pos, gptr, n, n_graphs, n_local, cutoff_l, cutoff_g);
+    if (rc) return rc;
+    if (!mol_tot || !out) return PAMNET_ENULL;
+    if (eg_cap < 0 || tp_cap < 0) return PAMNET_EINVAL;
+    const pamnet_mol_graph_out& o = *out;
+    if (!o.g_ptr || !o.l_ptr || !o.t_ptr) return PAMNET_ENULL;
+    if (eg_cap > 0 && (!o.g_row || !o.g_col || !o.g_dist || (need_grad && !o.gT_perm))) return PAMNET_ENULL;
+    if (n_local > 0 && (!o.l_row || !o.l_col || !o.l_dist || (need_grad && !o.lT_perm))) return PAMNET_ENULL;
+    if (tp_cap > 0 && (!o.t_row || !o.t_col || !o.t_angle || !o.t_kind || (need_grad && !o.tT_perm))) return PAMNET_ENULL;
+    if (need_grad && (!o.lT_ptr || !o.tT_ptr)) return PAMNET_ENULL;
+    const MolIn in{pos, gptr, nullptr, nullptr, n, n_graphs, n_local, cutoff_g, with_triplets ? 1 : 0, need_grad ? 1 : 0,
+                   cutoff_l};
+    hipLaunchKernelGGL((mol_graph_kernel<true, true, GEOM>), dim3((unsigned)n_graphs), dim3(64), 0, as_stream(stream), in,
+                       const_cast<int32_t*>(mol_tot), (int32_t*)nullptr, o, eg_cap, tp_cap, cells);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
 }  // namespace
 
 extern "C" int pamnet_mol_graph_count_i32(const float* pos, const int32_t* gptr, int64_t n, int64_t n_graphs,
@@ -428,8 +488,8 @@ extern "C" int pamnet_mol_graph_count_i32(const float* pos, const int32_t* gptr,
     if (!mol_tot || !totals) return PAMNET_ENULL;
     const MolIn in{pos, gptr, src, dst, n, n_graphs, n_bonds, cutoff_g, with_triplets ? 1 : 0, 0, 0.f};
     const pamnet_mol_graph_out none{};
-    hipLaunchKernelGGL((mol_graph_kernel<false, false>), dim3((unsigned)n_graphs), dim3(64), 0, as_stream(stream), in, mol_tot, totals,
-                       none, (int64_t)0, (int64_t)0);
+    hipLaunchKernelGGL((mol_graph_kernel<false, false, OpenSpace>), dim3((unsigned)n_graphs), dim3(64), 0, as_stream(stream), in, mol_tot, totals,
+                       none, (int64_t)0, (int64_t)0, (const double*)nullptr);
     PAMNET_LAUNCH_CHECK();
     return PAMNET_OK;
 }
@@ -449,44 +509,47 @@ extern "C" int pamnet_mol_graph_fill_i32(const float* pos, const int32_t* gptr, 
     if (tp_cap > 0 && (!o.t_row || !o.t_col || !o.t_angle || !o.t_kind || (need_grad && !o.tT_perm))) return PAMNET_ENULL;
     if (need_grad && (!o.lT_ptr || !o.tT_ptr)) return PAMNET_ENULL;
     const MolIn in{pos, gptr, src, dst, n, n_graphs, n_bonds, cutoff_g, with_triplets ? 1 : 0, need_grad ? 1 : 0, 0.f};
-    hipLaunchKernelGGL((mol_graph_kernel<true, false>), dim3((unsigned)n_graphs), dim3(64), 0, as_stream(stream), in,
-                       const_cast<int32_t*>(mol_tot), (int32_t*)nullptr, o, eg_cap, tp_cap);
+    hipLaunchKernelGGL((mol_graph_kernel<true, false, OpenSpace>), dim3((unsigned)n_graphs), dim3(64), 0, as_stream(stream), in,
+                       const_cast<int32_t*>(mol_tot), (int32_t*)nullptr, o, eg_cap, tp_cap, (const double*)nullptr);
     PAMNET_LAUNCH_CHECK();
     return PAMNET_OK;
 }
 
+
 extern "C" int pamnet_mol_graph_free_count_i32(const float* pos, const int32_t* gptr, int64_t n, int64_t n_graphs,
                                                float cutoff_l, float cutoff_g, int32_t with_triplets, int32_t* mol_tot,
                                                int32_t* totals, pamnet_stream_t stream) {
-    const int rc = check_free(pos, gptr, n, n_graphs, 0, cutoff_l, cutoff_g);
-    if (rc) return rc;
-    if (!mol_tot || !totals) return PAMNET_ENULL;
-    const MolIn in{pos, gptr, nullptr, nullptr, n, n_graphs, 0, cutoff_g, with_triplets ? 1 : 0, 0, cutoff_l};
-    const pamnet_mol_graph_out none{};
-    hipLaunchKernelGGL((mol_graph_kernel<false, true>), dim3((unsigned)n_graphs), dim3(64), 0, as_stream(stream), in, mol_tot,
-                       totals, none, (int64_t)0, (int64_t)0);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
+    return free_count<OpenSpace>(pos, nullptr, gptr, n, n_graphs, cutoff_l, cutoff_g, with_triplets, mol_tot, totals, stream);
 }
 
 extern "C" int pamnet_mol_graph_free_fill_i32(const float* pos, const int32_t* gptr, int64_t n, int64_t n_graphs,
                                               int64_t n_local, float cutoff_l, float cutoff_g, int32_t with_triplets,
                                               int32_t need_grad, const int32_t* mol_tot, int64_t eg_cap, int64_t tp_cap,
                                               const pamnet_mol_graph_out* out, pamnet_stream_t stream) {
-    const int rc = check_free(pos, gptr, n, n_graphs, n_local, cutoff_l, cutoff_g);
-    if (rc) return rc;
-    if (!mol_tot || !out) return PAMNET_ENULL;
-    if (eg_cap < 0 || tp_cap < 0) return PAMNET_EINVAL;
-    const pamnet_mol_graph_out& o = *out;
-    if (!o.g_ptr || !o.l_ptr || !o.t_ptr) return PAMNET_ENULL;
-    if (eg_cap > 0 && (!o.g_row || !o.g_col || !o.g_dist || (need_grad && !o.gT_perm))) return PAMNET_ENULL;
-    if (n_local > 0 && (!o.l_row || !o.l_col || !o.l_dist || (need_grad && !o.lT_perm))) return PAMNET_ENULL;
-    if (tp_cap > 0 && (!o.t_row || !o.t_col || !o.t_angle || !o.t_kind || (need_grad && !o.tT_perm))) return PAMNET_ENULL;
-    if (need_grad && (!o.lT_ptr || !o.tT_ptr)) return PAMNET_ENULL;
-    const MolIn in{pos, gptr, nullptr, nullptr, n, n_graphs, n_local, cutoff_g, with_triplets ? 1 : 0, need_grad ? 1 : 0,
-                   cutoff_l};
-    hipLaunchKernelGGL((mol_graph_kernel<true, true>), dim3((unsigned)n_graphs), dim3(64), 0, as_stream(stream), in,
-                       const_cast<int32_t*>(mol_tot), (int32_t*)nullptr, o, eg_cap, tp_cap);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
+    return free_fill<OpenSpace>(pos, nullptr, gptr, n, n_graphs, n_local, cutoff_l, cutoff_g, with_triplets, need_grad, mol_tot,
+                                eg_cap, tp_cap, out, stream);
+}
+
+// Periodic cells (cell_table [n_graphs, 18]: pamnet_cell_prepare_f64): sizes are judged first, then a missing table like any
+// other missing array.
+extern "C" int pamnet_mol_graph_pbc_count_i32(const float* pos, const double* cell_table, const int32_t* gptr, int64_t n,
+                                              int64_t n_graphs, float cutoff_l, float cutoff_g, int32_t with_triplets,
+                                              int32_t* mol_tot, int32_t* totals, pamnet_stream_t stream) {
+    if (!cell_table) {
+        const int rc = check_free(pos, gptr, n, n_graphs, 0, cutoff_l, cutoff_g);
+        return rc ? rc : PAMNET_ENULL;
+    }
+    return free_count<Periodic>(pos, cell_table, gptr, n, n_graphs, cutoff_l, cutoff_g, with_triplets, mol_tot, totals, stream);
+}
+
+extern "C" int pamnet_mol_graph_pbc_fill_i32(const float* pos, const double* cell_table, const int32_t* gptr, int64_t n,
+                                             int64_t n_graphs, int64_t n_local, float cutoff_l, float cutoff_g,
+                                             int32_t with_triplets, int32_t need_grad, const int32_t* mol_tot, int64_t eg_cap,
+                                             int64_t tp_cap, const pamnet_mol_graph_out* out, pamnet_stream_t stream) {
+    if (!cell_table) {
+        const int rc = check_free(pos, gptr, n, n_graphs, n_local, cutoff_l, cutoff_g);
+        return rc ? rc : PAMNET_ENULL;
+    }
+    return free_fill<Periodic>(pos, cell_table, gptr, n, n_graphs, n_local, cutoff_l, cutoff_g, with_triplets, need_grad,
+                               mol_tot, eg_cap, tp_cap, out, stream);
 }

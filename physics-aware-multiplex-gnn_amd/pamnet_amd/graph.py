@@ -770,12 +770,14 @@ def _engine_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos, edge_ind
     return g
 
 
-def _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=None):
+def _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=None, cell_tab=None, strain_nz=None):
     """QM9 schema, plain tensors: the molecule-local builder (csrc/graph_mol.hip) -- count launch, ONE host round trip for
     the sizes / validity / qualification, fill launch.  Fills `g` and returns True; False when the batch does not qualify
     (a molecule over the builder's limits, bonds not grouped by molecule, self loops): nothing of `g` was touched.
     `cutoff_l`: the bond-free form -- `ing` carries no bonds, the local graph is the radius graph at cutoff_l and its size
-    comes back with the other totals."""
+    comes back with the other totals.  `cell_tab` (cell_table; bond-free form only): the periodic form -- the same two launches
+    with every displacement the minimum-image one (pamnet_mol_graph_pbc_*); the table's verdict (PBC_BIT of the flag word) and
+    `strain_nz` (_checked_strain) travel in the same round trip and raise in _Sizes.read's order."""
     gptr, src0, dst0, flag, loops, totals = ing.gptr, ing.src, ing.dst, ing.flag, ing.loops, ing.totals
     dev = pos.device
     free = cutoff_l is not None
@@ -784,11 +786,19 @@ def _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=N
     mol_tot = _i32(4 * ng, dev)
     wt = 1 if with_triplets else 0
     local = (float(cutoff_l),) if free else (lib.ptr(src0), lib.ptr(dst0), m)      # what defines the local graph
-    lib.call('pamnet_mol_graph_free_count_i32' if free else 'pamnet_mol_graph_count_i32', lib.ptr(pos), lib.ptr(gptr), n, ng,
-             *local, float(cutoff_g), wt, lib.ptr(mol_tot), lib.ptr(totals), st)
-    eg, tp, viol, counted, bad, lp_ = host_ints(totals[0], totals[1], totals[2], totals[3], flag, loops)
-    if bad:
+    pbc = None if cell_tab is None else (cell_tab,)
+    assert free or pbc is None                        # (periodic batches are bond-free: _checked_cell)
+    _call_in_cell('pamnet_mol_graph_free_count_i32' if free else 'pamnet_mol_graph_count_i32', 'pamnet_mol_graph_pbc_count_i32',
+                  pos, pbc, lib.ptr(gptr), n, ng, *local, float(cutoff_g), wt, lib.ptr(mol_tot), lib.ptr(totals), st)
+    got = host_ints(totals[0], totals[1], totals[2], totals[3], flag, loops, *(() if strain_nz is None else (strain_nz,)))
+    nz = 0 if strain_nz is None else got.pop()
+    eg, tp, viol, counted, bad, lp_ = got
+    if bad & ~(PBC_BIT if pbc else 0):
         _raise_bad_inputs()
+    if bad:
+        _raise_bad_cell(cutoff_l, cutoff_g)
+    if nz:
+        _raise_nonzero_strain(nz)
     if free:
         m = counted
     if viol or lp_ or counted != m or eg <= 0 or tp <= 0:
@@ -813,8 +823,11 @@ def _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=N
         o.gT_perm, o.lT_ptr, o.lT_perm = gT_perm.data_ptr(), lT_ptr.data_ptr(), lT_perm.data_ptr()
         o.tT_ptr, o.tT_perm = tT_ptr.data_ptr(), tT_perm.data_ptr()
     local = (m, float(cutoff_l)) if free else (lib.ptr(src0), lib.ptr(dst0), m)
-    lib.call('pamnet_mol_graph_free_fill_i32' if free else 'pamnet_mol_graph_fill_i32', lib.ptr(pos), lib.ptr(gptr), n, ng,
-             *local, float(cutoff_g), wt, 1 if need_grad else 0, lib.ptr(mol_tot), eg, tp, ctypes.addressof(o), st)
+    _call_in_cell('pamnet_mol_graph_free_fill_i32' if free else 'pamnet_mol_graph_fill_i32', 'pamnet_mol_graph_pbc_fill_i32',
+                  pos, pbc, lib.ptr(gptr), n, ng, *local, float(cutoff_g), wt, 1 if need_grad else 0, lib.ptr(mol_tot), eg, tp,
+                  ctypes.addressof(o), st)
+    if cell_tab is not None:
+        g.cell_tab = cell_tab
     g.loops = loops
     g.pos = pos
     g.glob, g.dist_g = CSR(g_ptr, g_row, g_col), g_dist
@@ -939,11 +952,20 @@ def _qm9_bond_free(g, ing, a):
     """Bond-free molecules: the local graph is the radius graph at cutoff_l inside every molecule (what the reference's
     forward, models.py:104-115, computes when handed edge_index = radius(pos, pos, cutoff_l, batch, batch): get_edge_info
     strips the self loops) -- a search of its own, without a neighbour cap, so cutoff_l may lie on either side of cutoff_g
-    and a cap that binds in the global search leaves it alone.  Returns None when the molecule-local builder has filled `g`."""
+    and a cap that binds in the global search leaves it alone.  Returns None when the molecule-local builder has filled `g`.
+
+    A periodic batch takes the builder only when the caller vouches for it (mol_local=True): the cell table, the count launch,
+    the one round trip, the fill launch.  One that does not qualify after all (a cell over the builder's limits, an empty list)
+    goes on below with the table already prepared.  cell_images='all' never does: the all-image global graph is a multigraph
+    whose rows repeat columns and may exceed 64 entries, not an adjacency mask per atom."""
     pos = a.pos.to(torch.float32).contiguous()
     flag = _flag(g, ing, a.x_raw, a.n_types)
-    if a.cell is None and _builder_applies(g, ing, a):
-        if _mol_local_graph(g, pos, ing, a.cutoff_g, a.with_triplets, a.need_grad, cutoff_l=a.cutoff_l):
+    tab = None
+    if _builder_applies(g, ing, a) and (a.cell is None or (a.mol_local is True and not a.all_images)):
+        if a.cell is not None:
+            tab = cell_table(a.cell, max(float(a.cutoff_l), float(a.cutoff_g)), flag)
+        if _mol_local_graph(g, pos, ing, a.cutoff_g, a.with_triplets, a.need_grad, cutoff_l=a.cutoff_l, cell_tab=tab,
+                            strain_nz=a.strain_nz):
             return None
     r = _Lists(pos, _Sizes(flag, a.sizes))
     sz, r.loc_radius = r.sz, True
@@ -951,7 +973,9 @@ def _qm9_bond_free(g, ing, a):
         return _all_image_lists(g, a, r, flag)
     # Periodic cells: the same sequence with the minimum-image forms of the two searches and of the angle fill.  The table is
     # prepared first; its verdict (PBC_BIT) travels in the validity word with the sizes' round trip.
-    tab = r.cell_tab = None if a.cell is None else cell_table(a.cell, max(float(a.cutoff_l), float(a.cutoff_g)), flag)
+    if a.cell is not None and tab is None:
+        tab = cell_table(a.cell, max(float(a.cutoff_l), float(a.cutoff_g)), flag)
+    r.cell_tab = tab
     gptr_g = radius_count(pos, g.node_graph, g.gptr, a.cutoff_g, a.max_nb, flag, cell_tab=tab)
     lp = radius_count(pos, g.node_graph, g.gptr, a.cutoff_l, cell_tab=tab)
     if sz.known is not None:
@@ -1190,13 +1214,16 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
     graph g.  Every displacement between two atoms of a graph is then the minimum-image one (csrc/geom_core.h min_image): both
     radius searches, the bond lengths, both angle kinds and the position backward.  Positions need not be wrapped.  Each cell
     must be non-singular with all three perpendicular heights above 2 * max(cutoff_l, cutoff_g) (ValueError otherwise, with the
-    sizes' round trip).  Always the step-by-step launches.
+    sizes' round trip).  mol_local=None (the default) and False take the step-by-step launches; mol_local=True takes the periodic
+    form of the molecule-local builder (cell table, count launch, one round trip, fill launch: the same arrays bit for bit) and
+    falls through to the step-by-step launches when a cell turns out to hold over MOL_ATOMS atoms or MOL_BONDS directed local edges.
 
     `cell_images` (periodic batches): None / 'minimum' = the above.  'all': the GLOBAL graph holds every image within cutoff_g --
     row i every (atom j, integer triple n) with |pos_i - pos_j - n @ cell| <= cutoff_g, i's own images included, ascending (j, n),
     the triple of every edge in g.img_g -- while the local graph stays the minimum-image one.  The cells then need heights above
     2 * cutoff_l only (and not below cutoff_g / 4).  max_num_neighbors cuts no row of that graph: a cap that binds is a
-    ValueError.
+    ValueError.  Always the step-by-step launches, whatever `mol_local` says: the rows of that multigraph repeat columns and may
+    hold more than 64 entries, which the builder's adjacency masks (one bit per atom of the cell) cannot express.
 
     `strain` (periodic batches): the tensor that names the variable of the virial (differentiable_geometry) -- fp32 zeros
     [num_graphs, 3, 3] on the device.  Only validated here; its count of non-zero entries rides in the sizes' round trip.

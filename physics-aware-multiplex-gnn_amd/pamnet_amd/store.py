@@ -37,7 +37,8 @@ def size_key(model, bonded=True):
 
 
 class Batch(object):
-    """Duck-typed `data` of PAMNet.forward: x, pos, edge_index ([2, E] int32), batch (int32), y, num_graphs, sizes."""
+    """Duck-typed `data` of PAMNet.forward: x, pos, edge_index ([2, E] int32), batch (int32), y, num_graphs, sizes; a batch of
+    a periodic store also cell ([num_graphs, 3, 3] fp32) and never sizes."""
 
     def __init__(self):
         self._pamnet_prepared = None
@@ -53,7 +54,12 @@ class MoleculeStore(object):
     data_list: objects / dicts with x ([n] atom types for QM9; [n, w] rows of coordinates + features for PDBbind / RNA),
     optionally pos [n, 3] and edge_index [2, e] (QM9: node ids local to the molecule, both directions present as in
     qm9_dataset.py:243) and y (scalar target).  QM9 schema without edge_index: bond-free molecules -- the local graph is
-    the radius graph at the model's cutoff_l (graph.build_graph), its sizes are counted like every other."""
+    the radius graph at the model's cutoff_l (graph.build_graph), its sizes are counted like every other.
+
+    Periodic datasets: bond-free QM9-schema items that ALL carry `cell` ([3, 3], row k = lattice vector a_k).  The cells stay on
+    the device (fp32 [M, 3, 3]) and a batch gets its own by one gather (`bt.cell`).  Such a store hands out no `sizes` (a batch
+    with `cell` has no zero-round-trip route: graph.build_graph) but still vouches, per model, that every cell is within the
+    molecule-local builder's limits: its batches are then built by the cell table, two launches and one round trip."""
 
     def __init__(self, data_list, device):
         self.device = torch.device(device)
@@ -62,11 +68,29 @@ class MoleculeStore(object):
             def __init__(self, d):
                 get = d.get if isinstance(d, dict) else (lambda k, default=None: getattr(d, k, default))
                 self.x, self.pos, self.edge_index, self.y = get('x'), get('pos'), get('edge_index'), get('y', None)
+                self.cell = get('cell', None)
 
         data_list = [_View(d) for d in data_list]
         n = np.array([int(d.x.shape[0]) for d in data_list], dtype=np.int64)
         self.has_edges = data_list[0].edge_index is not None
         self.has_pos = data_list[0].pos is not None
+        self.has_cell = data_list[0].cell is not None
+        if any((d.cell is not None) != self.has_cell for d in data_list):
+            raise ValueError('a store is periodic as a whole: either every item carries `cell` ([3, 3]) or none does -- %d of %d '
+                             'do' % (sum(d.cell is not None for d in data_list), len(data_list)))
+        if self.has_cell:
+            if self.has_edges:
+                raise ValueError('periodic batches are bond-free: hand over `cell` without `edge_index` (the local graph is then '
+                                 'the minimum-image radius graph at cutoff_l), or drop `cell` for a bonded molecule in open space')
+            x0 = torch.as_tensor(data_list[0].x)
+            if not self.has_pos or not (x0.dim() == 1 or (x0.dim() == 2 and x0.shape[1] == 1)):
+                raise ValueError('periodic cells (`cell`) are implemented for the QM9 schema (pos + atom types) only, not for %r: drop '
+                                 '`cell`, or hand the structure over as a QM9-schema batch'
+                                 % ('x %s%s' % (tuple(x0.shape[1:]), '' if self.has_pos else ' without pos'),))
+            for d in data_list:
+                if tuple(torch.as_tensor(d.cell).shape) != (3, 3):
+                    raise ValueError('`cell` of a store item must have shape [3, 3] (row k = lattice vector a_k); got %s'
+                                     % (tuple(torch.as_tensor(d.cell).shape),))
         if self.has_edges:
             # remove_self_loops (models.py:63) once, at ingestion: resident bond lists are loop-free by construction, so
             # a batch never trips the forward's self-loop flag and the per-molecule counts describe what the forward uses
@@ -91,6 +115,8 @@ class MoleculeStore(object):
         else:
             self.esrc = self.edst = None
         ys = [getattr(d, 'y', None) for d in data_list]
+        self.cell = (torch.stack([torch.as_tensor(d.cell).to(torch.float32) for d in data_list]).contiguous().to(dev)
+                     if self.has_cell else None)                              # [M, 3, 3]
         self.y = None if any(v is None for v in ys) else torch.as_tensor(
             np.array([float(torch.as_tensor(v).reshape(-1)[0]) for v in ys], dtype=np.float32)).to(dev)
         self.nptr_d = torch.from_numpy(self.nptr.astype(np.int32)).to(dev)
@@ -127,9 +153,10 @@ class MoleculeStore(object):
     # -------------------------------------------------------------------------------------------------- per-molecule sizes
     def counts_for(self, model, chunk=None):
         """Per-graph (global edges, local edges, triplet + pair rows) for `model` (its dataset schema, cutoffs, flow and
-        layer kind): counted on the device by the forward's own graph construction, `chunk` graphs per pass, read back
-        ONCE per dataset.  The local edges of a graph are contiguous in the batch's CSR (sorted by target node), so every
-        count is a difference of CSR pointers at the graph's node range."""
+        layer kind): counted on the device by the forward's own graph construction (a periodic store: with the cells, on the
+        step-by-step route, where a bad cell raises its ValueError), `chunk` graphs per pass, read back ONCE per dataset.
+        The local edges of a graph are contiguous in the batch's CSR (sorted by target node), so every count is a difference of
+        CSR pointers at the graph's node range."""
         key = size_key(model, self.has_edges)
         if key in self._counts:
             return self._counts[key]
@@ -144,7 +171,7 @@ class MoleculeStore(object):
             g = G.build_graph(model.dataset, model.cutoff_l, model.cutoff_g, model.flow, bt.x, bt.batch, bt.pos, bt.edge_index,
                               num_graphs=b - a, need_grad=False, with_triplets=not model.small,
                               n_types=model.embeddings.size(0) if hasattr(model, 'embeddings') else None,
-                              max_num_neighbors=getattr(model, 'max_num_neighbors', None))
+                              max_num_neighbors=getattr(model, 'max_num_neighbors', None), cell=getattr(bt, 'cell', None))
             capped = capped or bool(getattr(g, 'capped', False))
             nodes = torch.from_numpy((self.nptr[a:b + 1] - self.nptr[a]).astype(np.int64)).to(self.device)
             pg, pl = g.glob.ptr.long()[nodes], g.loc.ptr.long()[nodes]
@@ -201,12 +228,16 @@ class MoleculeStore(object):
                  e_out, lib.ptr(bt.x), lib.ptr(bt.pos), lib.ptr(bt.batch),
                  bt.edge_index.data_ptr() if e_out else None, (bt.edge_index.data_ptr() + 4 * e_out) if e_out else None,
                  lib.ptr(self.y), lib.ptr(bt.y), lib.stream_of(bt.x))       # (the targets ride in the same launch)
+        if self.has_cell:                                  # the cells of the batch: one gather with the uploaded selection
+            bt.cell = torch.index_select(self.cell, 0, sel)
         bt.num_graphs = b
         # the batch is produced by work queued on this stream: a consumer on another stream (the input pipeline's side
         # stream, train.Prefetcher) waits for exactly this event
         bt.inputs_ready = torch.cuda.Event()
         bt.inputs_ready.record(torch.cuda.current_stream(dev))
-        if with_sizes:
+        if with_sizes and self.has_cell:                   # no host sizes beside `cell`; the builder's limits are vouched for
+            bt.mol_local = self._mol_local
+        elif with_sizes:
             bt.sizes = {key: (int(eg[idx].sum()), int(el[idx].sum()), int(tp[idx].sum()))
                         for key, (eg, el, tp) in self._counts.items() if not self._capped.get(key)}
             bt.mol_local = self._mol_local
