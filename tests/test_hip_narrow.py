@@ -4,8 +4,8 @@ models.py:185-188).  Tolerance: max-normalised error <= 1e-5 (north_star), forwa
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
+import narrow_refs as R
 from conftest import maxnorm_err
 
 pytestmark = pytest.mark.gpu
@@ -56,9 +56,7 @@ def test_global_message(dev, d, n, max_deg):
     ref_in = [t.detach().double().requires_grad_(True) for t in (x1, P, e, wm, bm, wea)]
     rx1, rP, re, rwm, rbm, rwea = ref_in
     i, j = csr.row_of.long(), csr.col.long()
-    z = rP[i, :d] + rP[j, d:] + re @ rwm[:, 2 * d:].t() + rbm
-    msg = F.silu(z) * (re @ rwea.t())
-    ref = rx1 + torch.zeros(n, d, dtype=torch.float64, device=dev).index_add_(0, i, msg)
+    ref = R.global_message(rx1, rP, re, rwm, rbm, rwea, i, j)
     ref.backward(gout.double())
     assert maxnorm_err(out.detach().cpu(), ref.detach().cpu()) < TOL
     _check_grads((x1, P, e, wm, bm, wea), ref_in, ('x1', 'P', 'e', 'wm', 'bm', 'wea'))
@@ -92,11 +90,7 @@ def test_mlp2(dev, d, m, res_x, with_r):
     y.backward(g)
     ref_in = [t.detach().double().requires_grad_(True) for t in (x, w1, b1, w2, b2, r)]
     rx, rw1, rb1, rw2, rb2, rr = ref_in
-    ref = F.silu(F.linear(F.silu(F.linear(rx, rw1, rb1)), rw2, rb2))
-    if res_x:
-        ref = ref + rx
-    if with_r:
-        ref = ref + rr
+    ref = R.mlp2(rx, rw1, rb1, rw2, rb2, res_x, rr if with_r else None)
     ref.backward(g.double())
     assert maxnorm_err(y.detach().cpu(), ref.detach().cpu()) < TOL
     n = 6 if with_r else 5
@@ -118,7 +112,7 @@ def test_linear_and_projection(dev, d, m):
     g = torch.randn_like(y)
     y.backward(g)
     rx, rw, rb = [t.detach().double().requires_grad_(True) for t in (x, w, b)]
-    ref = F.silu(F.linear(rx, rw, rb))
+    ref = R.linear(rx, rw, rb, act=True)
     ref.backward(g.double())
     assert maxnorm_err(y.detach().cpu(), ref.detach().cpu()) < TOL
     _check_grads((x, lin.weight, lin.bias), (rx, rw, rb), ('x', 'w', 'b'))
@@ -128,7 +122,7 @@ def test_linear_and_projection(dev, d, m):
     g = torch.randn_like(p)
     p.backward(g)
     rx2, rwj, rwk = [t.detach().double().requires_grad_(True) for t in (x2, wj, wk)]
-    ref = F.linear(rx2, torch.cat([rwj[:, :d], rwk[:, :d], rwj[:, d:2 * d], rwk[:, d:2 * d]], 0))
+    ref = R.project4(rx2, rwj, rwk)
     ref.backward(g.double())
     assert maxnorm_err(p.detach().cpu(), ref.detach().cpu()) < TOL
     _check_grads((x2, wj, wk), (rx2, rwj, rwk), ('x', 'wj', 'wk'))
@@ -151,12 +145,7 @@ def test_embed(dev, d, k, two, m):
     y.backward(g)
     rf = f.detach().double().requires_grad_(need_df)
     rwa, rba, rwb, rbb = [t.detach().double().requires_grad_(True) for t in (wa, ba, wb, bb)]
-    ya = F.silu(F.linear(rf, rwa, rba))
-    if two:
-        yb = F.silu(F.linear(rf, rwb, rbb))
-        ref = torch.where(kind.bool().unsqueeze(1), yb, ya)
-    else:
-        ref = ya
+    ref = R.embed(rf, kind, rwa, rba, rwb, rbb)
     ref.backward(g.double())
     assert maxnorm_err(y.detach().cpu(), ref.detach().cpu()) < TOL
     names, ps, rs = ['wa', 'ba'], [wa, ba], [rwa, rba]
@@ -188,11 +177,8 @@ def test_embed_rbf_in_kernel(dev, d, m):
     y2.backward(g)
     assert torch.equal(y1, y2)
     # fp64 reference of SiLU(W (u(x) sin(f x)) + b)
-    x = (dist.double() / 5.0)
     fr, wr, br = [mk(t.double()) for t in (freq0, lin.weight, lin.bias)]
-    x5 = x ** 5
-    u = torch.where(x < 1, 1.0 / x + x5 * (-21.0 + x * (35.0 - 15.0 * x)), torch.zeros_like(x))
-    ref = F.silu(F.linear(u.unsqueeze(1) * torch.sin(fr * x.unsqueeze(1)), wr, br))
+    ref = R.embed_rbf(dist, fr, wr, br, 5.0)
     ref.backward(g.double())
     _check_grads((f1, w1, b1), (fr, wr, br), ('freq', 'w', 'b'))
     _check_grads((f2, w2, b2), (fr, wr, br), ('freq (two-step)', 'w', 'b'))
@@ -215,9 +201,7 @@ def test_local_gate(dev, d, n, max_deg):
     ref_in = [t.detach().double().requires_grad_(True) for t in (P, Q, b1, b2)]
     rP, rQ, rb1, rb2 = ref_in
     i, j = csr.row_of.long(), csr.col.long()
-    z1 = rP[i, :d] + rP[j, 2 * d:3 * d] + rQ[:, :d] + rb1
-    z2 = rP[i, d:2 * d] + rP[j, 3 * d:] + rQ[:, d:2 * d] + rb2
-    r_ji, r_nb = F.silu(z1), F.silu(z2) * rQ[:, 2 * d:3 * d]
+    r_ji, r_nb = R.local_gate(rP, rQ, rb1, rb2, i, j)
     torch.autograd.backward([r_ji, r_nb], [g1.double(), g2.double()])
     assert maxnorm_err(m_ji.detach().cpu(), r_ji.detach().cpu()) < TOL
     assert maxnorm_err(m_nb.detach().cpu(), r_nb.detach().cpu()) < TOL
