@@ -185,6 +185,26 @@ int pamnet_radius_img_fill_i32(const float* pos, const double* cell_table, const
                                int32_t* nbr, float* dist, int32_t* row_of /* nullable */, int32_t* img, int64_t cap,
                                pamnet_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Per-axis periodicity: slabs, wires and isolated molecules beside bulk cells (part of ABI 18: nothing existing changed).
+ * pbc [n_graphs, 3] bytes: graph g repeats along lattice vector k when pbc[3 g + k] != 0.  The two entry points below stand in
+ * for their twins; every other periodic entry point takes the table they make as it is.
+ *   pamnet_cell_prepare_axes_f64: pamnet_cell_prepare_f64 on the COMPLETED cell.  The vector handed over along an open axis is
+ *     not used (it may be zero, short, or make the matrix singular); in its place stands a unit vector orthogonal to the
+ *     periodic ones -- two periodic axes i, j: a_k' = a_i x a_j / |a_i x a_j|; one periodic axis i: a_j' = a_i x e normalised, e
+ *     the coordinate unit vector along a_i's component of smallest magnitude (lowest index on ties), and a_k' = a_i x a_j'
+ *     normalised; none: the identity.  cell_table holds the completed cell and its inverse, with the three inverse entries that
+ *     form fractional component k of every open axis k set to +0.0: the image rule then rounds that component to 0 for every
+ *     pair, so nothing is wrapped along k.  ORs 128 into *flag when the periodic vectors are degenerate (zero, parallel, not
+ *     finite) or the height |det'| / |a_i' x a_j'| of a PERIODIC axis does not exceed 2 * cutoff; open axes are not tested.  A
+ *     row with all three flags set gets pamnet_cell_prepare_f64's 18 doubles and verdict bit for bit.
+ *   pamnet_cell_images_axes_i32: pamnet_cell_images_i32 on that table with N_k = 0 and no verdict along open axes.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int pamnet_cell_prepare_axes_f64(const float* cell, const uint8_t* pbc, int64_t n_graphs, float cutoff, double* cell_table,
+                                 int32_t* flag, pamnet_stream_t stream);
+int pamnet_cell_images_axes_i32(const double* cell_table, const uint8_t* pbc, int64_t n_graphs, float cutoff, int32_t* img_box,
+                                int32_t* flag, pamnet_stream_t stream);
+
 /* knn: for every query node its k nearest nodes of the same graph (itself included, as torch_cluster.knn does),
  * ordered by (distance, index); then the self entry is dropped and entries with dist > cutoff are masked out:
  * nbr[i*k + s] = neighbour index or -1, dist[i*k + s] = distance.  (models.py:143-150) */

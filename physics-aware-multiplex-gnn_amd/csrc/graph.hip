@@ -1181,6 +1181,137 @@ __global__ __launch_bounds__(256) void cell_images_kernel(const double* __restri
     if (!ok) atomicOr(flag, PBC_BIT);
 }
 
+// ---- per-axis periodicity: the same table for slabs, wires and isolated molecules --------------------------------------------
+// pbc [n_graphs, 3] bytes: graph g repeats along its lattice vector k when pbc[3 g + k] is not zero.  The user's vector along
+// an open axis is not read beyond the load: the cell is COMPLETED with unit vectors orthogonal to the periodic ones, the inverse
+// of the completed cell is formed by cell_prepare_kernel's statements, and the three inverse entries that make fractional
+// component k of an open axis k are overwritten with +0.0 -- so min_image / nearest_image round that component to 0 for every
+// pair and no kernel that reads the table ever wraps along k.  Because the completed vectors are orthogonal to the periodic
+// ones, the remaining columns of the inverse are the reciprocal vectors of the periodic lattice inside its own span: an
+// out-of-plane displacement has no share in the in-plane image.  (A skewed user vector would have one.)
+__device__ __forceinline__ void cross3(const double* u, const double* v, double* w) {
+    w[0] = u[1] * v[2] - u[2] * v[1];
+    w[1] = u[2] * v[0] - u[0] * v[2];
+    w[2] = u[0] * v[1] - u[1] * v[0];
+}
+
+// w / |w| into out; false (out untouched) when |w| is zero or not finite
+__device__ __forceinline__ bool unit3(const double* w, double* out) {
+    const double len = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+    if (!(len > 0.0) || !isfinite(len)) return false;
+    out[0] = w[0] / len, out[1] = w[1] / len, out[2] = w[2] / len;
+    return true;
+}
+
+// One thread per graph.  Completion: three periodic axes -- the cell as given; two (i, j; k open) -- a_k' = a_i x a_j
+// normalised; one (i) -- a_j' = a_i x e normalised, e the coordinate unit vector along a_i's component of smallest magnitude
+// (lowest index on ties), a_k' = a_i x a_j' normalised; none -- the identity.  A completion that fails (parallel or zero
+// periodic vectors) leaves coordinate unit vectors on the open axes, a zero inverse and PBC_BIT.  From there on the statements
+// are cell_prepare_kernel's, with the height test on periodic axes only: a row of three set flags gets that kernel's 18 doubles
+// and verdict bit for bit.
+__global__ __launch_bounds__(256) void cell_prepare_axes_kernel(const float* __restrict__ cell, const uint8_t* __restrict__ pbc,
+                                                                int64_t n_graphs, double cutoff, double* __restrict__ table,
+                                                                int32_t* __restrict__ flag) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_graphs) return;
+    double a[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) a[k] = (double)cell[9 * g + k];
+    bool per[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) per[k] = pbc[3 * g + k] != 0;
+    const int n_per = (int)per[0] + (int)per[1] + (int)per[2];
+    bool complete = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)                                   // open axes start as coordinate unit vectors
+        if (!per[k]) a[3 * k] = k == 0 ? 1.0 : 0.0, a[3 * k + 1] = k == 1 ? 1.0 : 0.0, a[3 * k + 2] = k == 2 ? 1.0 : 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int i = (k + 1) % 3, j = (k + 2) % 3;
+        if (n_per == 2 && !per[k]) {                              // slab: the unit normal of the plane of a_i, a_j
+            double w[3];
+            cross3(a + 3 * i, a + 3 * j, w);
+            complete = unit3(w, a + 3 * k);
+        }
+        if (n_per == 1 && per[k]) {                               // wire along a_k: two unit vectors across it (rows i, j)
+            const double* v = a + 3 * k;
+            const double m0 = fabs(v[0]), m1 = fabs(v[1]), m2 = fabs(v[2]);
+            const int e = (m0 <= m1 && m0 <= m2) ? 0 : (m1 <= m2 ? 1 : 2);
+            const double unit[3] = {e == 0 ? 1.0 : 0.0, e == 1 ? 1.0 : 0.0, e == 2 ? 1.0 : 0.0};
+            double w[3], first[3] = {0.0, 0.0, 0.0};
+            cross3(v, unit, w);
+            complete = unit3(w, first);
+            cross3(v, first, w);
+            double second[3];
+            complete = complete && unit3(w, second);
+            if (complete) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) a[3 * i + c] = first[c], a[3 * j + c] = second[c];
+            }
+        }
+    }
+    // x[k] = a_{k+1} x a_{k+2}: column k of the adjugate; det = a_0 . x[0]  (cell_prepare_kernel's statements from here on)
+    double x[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double* u = a + 3 * ((k + 1) % 3);
+        const double* v = a + 3 * ((k + 2) % 3);
+        x[k][0] = u[1] * v[2] - u[2] * v[1];
+        x[k][1] = u[2] * v[0] - u[0] * v[2];
+        x[k][2] = u[0] * v[1] - u[1] * v[0];
+    }
+    const double det = a[0] * x[0][0] + a[1] * x[0][1] + a[2] * x[0][2];
+    bool ok = complete && isfinite(det) && det != 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double area = sqrt(x[k][0] * x[k][0] + x[k][1] * x[k][1] + x[k][2] * x[k][2]);
+        ok = ok && (!per[k] || fabs(det) / area > 2.0 * cutoff);  // (NaN compares false; an open axis has no condition)
+    }
+    const bool invertible = complete && isfinite(det) && det != 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) table[PBC_ROW * g + k] = a[k];
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) table[PBC_ROW * g + 9 + 3 * m + k] = (invertible && per[k]) ? x[k][m] / det : 0.0;
+    if (!ok) atomicOr(flag, PBC_BIT);
+}
+
+// cell_images_kernel on a table completed by cell_prepare_axes_kernel: N_k = 0 along an open axis (the search tries no image
+// there) and no verdict on it.
+__global__ __launch_bounds__(256) void cell_images_axes_kernel(const double* __restrict__ table, const uint8_t* __restrict__ pbc,
+                                                               int64_t n_graphs, double cutoff, int32_t* __restrict__ img_box,
+                                                               int32_t* __restrict__ flag) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_graphs) return;
+    const double* a = table + PBC_ROW * g;
+    double x[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double* u = a + 3 * ((k + 1) % 3);
+        const double* v = a + 3 * ((k + 2) % 3);
+        x[k][0] = u[1] * v[2] - u[2] * v[1];
+        x[k][1] = u[2] * v[0] - u[0] * v[2];
+        x[k][2] = u[0] * v[1] - u[1] * v[0];
+    }
+    const double det = a[0] * x[0][0] + a[1] * x[0][1] + a[2] * x[0][2];
+    int N[3];
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        N[k] = 0;
+        if (pbc[3 * g + k] != 0) {
+            const double area = sqrt(x[k][0] * x[k][0] + x[k][1] * x[k][1] + x[k][2] * x[k][2]);
+            const double need = ceil(cutoff / (fabs(det) / area));
+            ok = ok && (need <= (double)IMG_BOX_MAX);             // (NaN compares false)
+            N[k] = ok ? (int)need : 0;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) img_box[3 * g + k] = ok ? N[k] : 0;
+    if (!ok) atomicOr(flag, PBC_BIT);
+}
+
 // ---- transposed triplet / pair row list without a sort -----------------------------------------------------------------
 // For source bond q = (k -> j) the rows that gather it (what pamnet_csr_from_keys_i32 returns for keys = tp_idx) are: one
 // triplet row of every bond e leaving j towards an atom other than k (row = e's first row + q's rank among e's triplets),
@@ -1459,6 +1590,17 @@ extern "C" int pamnet_cell_prepare_f64(const float* cell, int64_t n_graphs, floa
     return PAMNET_OK;
 }
 
+extern "C" int pamnet_cell_prepare_axes_f64(const float* cell, const uint8_t* pbc, int64_t n_graphs, float cutoff, double* table,
+                                            int32_t* flag, pamnet_stream_t stream) {
+    if (n_graphs < 0 || !(cutoff > 0.f) || !(cutoff <= 3.0e38f)) return PAMNET_EINVAL;      // (NaN and inf refused)
+    if (n_graphs == 0) return PAMNET_OK;
+    if (!cell || !pbc || !table || !flag) return PAMNET_ENULL;
+    hipLaunchKernelGGL(cell_prepare_axes_kernel, dim3(blocks_for(n_graphs)), dim3(256), 0, as_stream(stream), cell, pbc,
+                       n_graphs, (double)cutoff, table, flag);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
 extern "C" int pamnet_radius_pbc_count_i32(const float* pos, const double* cell_table, const int32_t* node_graph,
                                            const int32_t* gptr, int64_t n, int64_t n_graphs, float r, int64_t max_neighbors,
                                            int32_t* count, int32_t* cap_flag, pamnet_stream_t stream) {
@@ -1504,6 +1646,17 @@ extern "C" int pamnet_cell_images_i32(const double* cell_table, int64_t n_graphs
     if (!cell_table || !img_box || !flag) return PAMNET_ENULL;
     hipLaunchKernelGGL(cell_images_kernel, dim3(blocks_for(n_graphs)), dim3(256), 0, as_stream(stream), cell_table, n_graphs,
                        (double)cutoff, img_box, flag);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
+extern "C" int pamnet_cell_images_axes_i32(const double* cell_table, const uint8_t* pbc, int64_t n_graphs, float cutoff,
+                                           int32_t* img_box, int32_t* flag, pamnet_stream_t stream) {
+    if (n_graphs < 0 || !(cutoff > 0.f) || !(cutoff <= 3.0e38f)) return PAMNET_EINVAL;      // (NaN and inf refused)
+    if (n_graphs == 0) return PAMNET_OK;
+    if (!cell_table || !pbc || !img_box || !flag) return PAMNET_ENULL;
+    hipLaunchKernelGGL(cell_images_axes_kernel, dim3(blocks_for(n_graphs)), dim3(256), 0, as_stream(stream), cell_table, pbc,
+                       n_graphs, (double)cutoff, img_box, flag);
     PAMNET_LAUNCH_CHECK();
     return PAMNET_OK;
 }

@@ -10,7 +10,9 @@ forward(data): duck-typed `data` with `.x`, `.batch` (sorted) and, for QM9, `.po
 graph at cutoff_l; such a batch may carry `.cell` (fp32 [num_graphs, 3, 3], row k = lattice vector a_k): periodic boundaries, every
 displacement the model uses is then the minimum-image one (graph.build_graph), and with `.strain` (fp32 zeros [num_graphs, 3, 3]
 that require grad) the gradient with respect to it is the virial per cell (graph.differentiable_geometry); with `.cell_images = 'all'`
-the global graph holds every image within cutoff_g, so cells need heights above 2 * cutoff_l only (graph.build_graph).  Returns
+the global graph holds every image within cutoff_g, so cells need heights above 2 * cutoff_l only (graph.build_graph); with `.pbc`
+(torch.bool [num_graphs, 3] or three bools) a graph repeats along the flagged lattice vectors only -- slabs, wires, and isolated
+molecules beside periodic structures (graph.build_graph).  Returns
 fp32 [num_graphs], differentiable w.r.t. every parameter.  MI355X only: tensors must
 live on a HIP device -- there is no CPU path (the CPU oracle in oracle/ is test infrastructure and is never imported
 from here).
@@ -519,7 +521,7 @@ class _PAMNetBase(nn.Module):
                           sizes=self._sizes_of(data), default_basis=self.sbf.default, mol_local=self._mol_local_of(data),
                           max_num_neighbors=self.max_num_neighbors, aux_tables=self.dim == fused.D,
                           cell=getattr(data, 'cell', None), strain=getattr(data, 'strain', None),
-                          cell_images=getattr(data, 'cell_images', None))
+                          cell_images=getattr(data, 'cell_images', None), pbc=getattr(data, 'pbc', None))
         g.strain_checked = getattr(data, 'strain', None) is not None
         if g.check is not None:                          # zero-host-sync path: the flag word waits for verify()
             self._pending_checks.append(g.check)

@@ -213,21 +213,55 @@ class Graph(object):
 PBC_BIT = 128         # flag-word bit: a periodic cell is singular or too small for the cutoffs (csrc/geom_core.h)
 
 
-def cell_table(cell, cutoff, flag):
+_PBC_ROWS = {}        # (three bools, device) -> uint8 [1, 3] on the device: a `pbc` tuple is uploaded once
+
+
+def _pbc_bytes(pbc, ng, dev):
+    """`pbc` as the kernels read it: uint8 [ng, 3], contiguous, on `dev`.  None for None and for the all-true tuple (the twins'
+    entry points); a tuple is uploaded once per device and expanded on the device; a bool tensor is viewed as bytes."""
+    if pbc is None:
+        return None
+    if isinstance(pbc, torch.Tensor):
+        return pbc.contiguous().view(torch.uint8)
+    key = tuple(bool(v) for v in pbc)
+    if all(key):
+        return None
+    row = _PBC_ROWS.get((key, dev))
+    if row is None:
+        row = _PBC_ROWS[(key, dev)] = torch.tensor([key], dtype=torch.uint8).to(dev)
+    return row.expand(ng, 3).contiguous()
+
+
+def cell_table(cell, cutoff, flag, pbc=None):
     """The table every periodic kernel reads (pamnet_cell_prepare_f64): per graph the cell and its inverse, fp64 [G, 18].  ORs
-    PBC_BIT into `flag` (the batch's validity word) when a cell is singular or has a perpendicular height <= 2 * cutoff."""
+    PBC_BIT into `flag` (the batch's validity word) when a cell is singular or has a perpendicular height <= 2 * cutoff.
+    `pbc` (a bool tensor [G, 3] or three bools, not all true): pamnet_cell_prepare_axes_f64 -- the cell completed with unit
+    vectors orthogonal to the periodic ones in place of the open axes' vectors, those axes' inverse entries +0.0 (no kernel
+    that reads the table wraps along them), the height condition on the periodic axes only."""
     ng = int(cell.size(0))
     tab = torch.empty((ng, 18), dtype=torch.float64, device=cell.device)
-    lib.call('pamnet_cell_prepare_f64', lib.ptr(cell), ng, float(cutoff), lib.ptr(tab), lib.ptr(flag), lib.stream_of(cell))
+    axes = _pbc_bytes(pbc, ng, cell.device)
+    if axes is None:
+        lib.call('pamnet_cell_prepare_f64', lib.ptr(cell), ng, float(cutoff), lib.ptr(tab), lib.ptr(flag), lib.stream_of(cell))
+    else:
+        lib.call('pamnet_cell_prepare_axes_f64', lib.ptr(cell), lib.ptr(axes), ng, float(cutoff), lib.ptr(tab), lib.ptr(flag),
+                 lib.stream_of(cell))
     return tab
 
 
-def cell_images(cell_tab, cutoff_g, flag):
+def cell_images(cell_tab, cutoff_g, flag, pbc=None):
     """The candidate box of the all-image search (pamnet_cell_images_i32): per graph N_k = ceil(cutoff_g / height_k), int32 [G, 3].
-    ORs PBC_BIT into `flag` when some N_k > 4 (a height below cutoff_g / 4)."""
+    ORs PBC_BIT into `flag` when some N_k > 4 (a height below cutoff_g / 4).  `pbc` as in cell_table
+    (pamnet_cell_images_axes_i32): N_k = 0 and no verdict along open axes."""
     ng = int(cell_tab.size(0))
     box = torch.empty((ng, 3), dtype=I32, device=cell_tab.device)
-    lib.call('pamnet_cell_images_i32', lib.ptr(cell_tab), ng, float(cutoff_g), lib.ptr(box), lib.ptr(flag), lib.stream_of(cell_tab))
+    axes = _pbc_bytes(pbc, ng, cell_tab.device)
+    if axes is None:
+        lib.call('pamnet_cell_images_i32', lib.ptr(cell_tab), ng, float(cutoff_g), lib.ptr(box), lib.ptr(flag),
+                 lib.stream_of(cell_tab))
+    else:
+        lib.call('pamnet_cell_images_axes_i32', lib.ptr(cell_tab), lib.ptr(axes), ng, float(cutoff_g), lib.ptr(box), lib.ptr(flag),
+                 lib.stream_of(cell_tab))
     return box
 
 
@@ -495,7 +529,20 @@ def _raise_bad_inputs():
                      '[0, num_graphs), atom types in [0, embeddings.size(0)), edge_index in [0, num_nodes)')
 
 
-def _raise_bad_cell(cutoff_l, cutoff_g, all_images=False):
+_PER_AXIS = ('periodic cell too small or singular%s: with `pbc` the rule holds per axis -- the lattice vectors of the PERIODIC axes of '
+             'every graph must be finite and linearly independent, and the height of each periodic axis within the lattice those '
+             'axes span (the in-plane heights of a slab, the length of a wire\'s one vector) must lie %s; the vector of an '
+             'open axis is not used and has no condition -- replicate the cell along its short periodic directions, lower the '
+             'cutoffs, or open the axis (pbc[g, k] = False) if the structure does not repeat along it')
+
+
+def _raise_bad_cell(cutoff_l, cutoff_g, all_images=False, per_axis=False):
+    if per_axis and all_images:
+        raise ValueError(_PER_AXIS % (" for cell_images='all'", 'above 2 * cutoff_l = %g and not below cutoff_g / 4 = %g'
+                                      % (2 * float(cutoff_l), float(cutoff_g) / 4)))
+    if per_axis:
+        raise ValueError(_PER_AXIS % ('', 'above 2 * max(cutoff_l, cutoff_g) = %g'
+                                      % (2 * max(float(cutoff_l), float(cutoff_g)),)))
     if all_images:
         raise ValueError('periodic cell too small or singular for cell_images=\'all\': every cell of the batch must be non-singular '
                          'with each of its three perpendicular heights |det| / |a_i x a_j| above 2 * cutoff_l = %g (the local graph '
@@ -547,6 +594,31 @@ def _checked_cell_images(cell_images, cell):
     if cell is None:
         raise ValueError('`cell_images` belongs to periodic batches (`cell`): drop it, or hand the structure over with its `cell`')
     return cell_images == 'all'
+
+
+def _checked_pbc(pbc, cell, n_graphs, pos):
+    """`data.pbc`: along which lattice vectors each graph of a periodic batch repeats.  Returns None (absent, or the tuple of
+    three True: the fully periodic path and its entry points), the tuple of three bools, or the bool tensor [num_graphs, 3];
+    or raises the refusal that says what to do instead."""
+    if pbc is None:
+        return None
+    if cell is None:
+        raise ValueError('`pbc` belongs to periodic batches (`cell`): hand the structure over with its `cell` ([num_graphs, 3, '
+                         '3]; the vector of an open axis may be zero), or drop `pbc` for molecules in open space')
+    if isinstance(pbc, torch.Tensor):
+        if pbc.dtype != torch.bool or tuple(pbc.shape) != (int(n_graphs), 3):
+            raise ValueError('`pbc` must be a torch.bool tensor of shape [num_graphs, 3] = [%d, 3] (pbc[g, k]: graph g repeats '
+                             'along cell[g, k]) or a tuple of three bools for every graph; got %s %s -- convert with '
+                             'pbc.to(torch.bool), one row per graph' % (int(n_graphs), pbc.dtype, tuple(pbc.shape)))
+        if pbc.device != pos.device:
+            raise ValueError('`pbc` must live on the device of `pos` (%s); it is on %s -- move it with pbc.to(pos.device)'
+                             % (pos.device, pbc.device))
+        return pbc.detach()
+    if not isinstance(pbc, (tuple, list)) or len(pbc) != 3 or not all(isinstance(v, bool) for v in pbc):
+        raise ValueError('`pbc` must be a tuple or list of three Python bools (the same for every graph) or a torch.bool tensor '
+                         'of shape [num_graphs, 3]; got %r -- e.g. pbc = (True, True, False) for a slab whose third lattice '
+                         'vector is open' % (pbc,))
+    return None if all(pbc) else tuple(pbc)
 
 
 def _raise_cap_binds(max_nb):
@@ -770,14 +842,16 @@ def _engine_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos, edge_ind
     return g
 
 
-def _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=None, cell_tab=None, strain_nz=None):
+def _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=None, cell_tab=None, strain_nz=None,
+                     per_axis=False):
     """QM9 schema, plain tensors: the molecule-local builder (csrc/graph_mol.hip) -- count launch, ONE host round trip for
     the sizes / validity / qualification, fill launch.  Fills `g` and returns True; False when the batch does not qualify
     (a molecule over the builder's limits, bonds not grouped by molecule, self loops): nothing of `g` was touched.
     `cutoff_l`: the bond-free form -- `ing` carries no bonds, the local graph is the radius graph at cutoff_l and its size
     comes back with the other totals.  `cell_tab` (cell_table; bond-free form only): the periodic form -- the same two launches
     with every displacement the minimum-image one (pamnet_mol_graph_pbc_*); the table's verdict (PBC_BIT of the flag word) and
-    `strain_nz` (_checked_strain) travel in the same round trip and raise in _Sizes.read's order."""
+    `strain_nz` (_checked_strain) travel in the same round trip and raise in _Sizes.read's order.  `per_axis`: the table was
+    made with `pbc` (the wording of a bad cell's refusal)."""
     gptr, src0, dst0, flag, loops, totals = ing.gptr, ing.src, ing.dst, ing.flag, ing.loops, ing.totals
     dev = pos.device
     free = cutoff_l is not None
@@ -796,7 +870,7 @@ def _mol_local_graph(g, pos, ing, cutoff_g, with_triplets, need_grad, cutoff_l=N
     if bad & ~(PBC_BIT if pbc else 0):
         _raise_bad_inputs()
     if bad:
-        _raise_bad_cell(cutoff_l, cutoff_g)
+        _raise_bad_cell(cutoff_l, cutoff_g, per_axis=per_axis)
     if nz:
         _raise_nonzero_strain(nz)
     if free:
@@ -908,7 +982,7 @@ class _Lists(object):
 
 
 _Args = namedtuple('_Args', 'cutoff_l cutoff_g flow x_raw pos edge_index need_grad knn_k with_triplets n_types sizes mol_local '
-                            'max_nb cell strain_nz all_images')
+                            'max_nb cell strain_nz all_images pbc')
 _Bonds = namedtuple('_Bonds', 'ptr src dst dist tp_ptr tcount raw')
 
 
@@ -963,9 +1037,9 @@ def _qm9_bond_free(g, ing, a):
     tab = None
     if _builder_applies(g, ing, a) and (a.cell is None or (a.mol_local is True and not a.all_images)):
         if a.cell is not None:
-            tab = cell_table(a.cell, max(float(a.cutoff_l), float(a.cutoff_g)), flag)
+            tab = cell_table(a.cell, max(float(a.cutoff_l), float(a.cutoff_g)), flag, a.pbc)
         if _mol_local_graph(g, pos, ing, a.cutoff_g, a.with_triplets, a.need_grad, cutoff_l=a.cutoff_l, cell_tab=tab,
-                            strain_nz=a.strain_nz):
+                            strain_nz=a.strain_nz, per_axis=a.pbc is not None):
             return None
     r = _Lists(pos, _Sizes(flag, a.sizes))
     sz, r.loc_radius = r.sz, True
@@ -974,7 +1048,7 @@ def _qm9_bond_free(g, ing, a):
     # Periodic cells: the same sequence with the minimum-image forms of the two searches and of the angle fill.  The table is
     # prepared first; its verdict (PBC_BIT) travels in the validity word with the sizes' round trip.
     if a.cell is not None and tab is None:
-        tab = cell_table(a.cell, max(float(a.cutoff_l), float(a.cutoff_g)), flag)
+        tab = cell_table(a.cell, max(float(a.cutoff_l), float(a.cutoff_g)), flag, a.pbc)
     r.cell_tab = tab
     gptr_g = radius_count(pos, g.node_graph, g.gptr, a.cutoff_g, a.max_nb, flag, cell_tab=tab)
     lp = radius_count(pos, g.node_graph, g.gptr, a.cutoff_l, cell_tab=tab)
@@ -984,7 +1058,8 @@ def _qm9_bond_free(g, ing, a):
         gptr_g, lp = sz.expect(gptr_g, total_g), sz.expect(lp, total_l)
     else:
         (total_g, total_l, r.tp_hint), r.capped = sz.read(gptr_g[-1], lp[-1], _symmetric_tp_total(lp, a.with_triplets),
-                                                          allow=CAP_BIT | PBC_BIT, cutoffs=(a.cutoff_l, a.cutoff_g),
+                                                          allow=CAP_BIT | PBC_BIT,
+                                                          cutoffs=(a.cutoff_l, a.cutoff_g, False, a.pbc is not None),
                                                           strain_nz=a.strain_nz)
     rows = []
     r.gp, r.gn, r.gd = radius_fill(pos, g.node_graph, g.gptr, a.cutoff_g, gptr_g, total_g, zeroed=sz.arena, rows_out=rows,
@@ -1005,12 +1080,13 @@ def _all_image_lists(g, a, r, flag):
     PBC_BIT) and the cap's travel in the validity word with the sizes.  No row is cut, so a cap that binds is an error."""
     pos, sz = r.pos, r.sz
     assert sz.known is None                       # (periodic batches carry no host sizes: _checked_cell)
-    tab = r.cell_tab = cell_table(a.cell, float(a.cutoff_l), flag)
-    box = cell_images(tab, a.cutoff_g, flag)
+    tab = r.cell_tab = cell_table(a.cell, float(a.cutoff_l), flag, a.pbc)
+    box = cell_images(tab, a.cutoff_g, flag, a.pbc)
     gptr_g = radius_img_count(pos, tab, box, g.node_graph, g.gptr, a.cutoff_g, a.max_nb, flag)
     lp = radius_count(pos, g.node_graph, g.gptr, a.cutoff_l, cell_tab=tab)
     (total_g, total_l, r.tp_hint), capped = sz.read(gptr_g[-1], lp[-1], _symmetric_tp_total(lp, a.with_triplets),
-                                                    allow=CAP_BIT | PBC_BIT, cutoffs=(a.cutoff_l, a.cutoff_g, True),
+                                                    allow=CAP_BIT | PBC_BIT,
+                                                    cutoffs=(a.cutoff_l, a.cutoff_g, True, a.pbc is not None),
                                                     strain_nz=a.strain_nz)
     if capped:
         _raise_cap_binds(a.max_nb)
@@ -1207,7 +1283,7 @@ def _finish(g, r, dataset, a):
 
 def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_index=None, num_graphs=None,
                 need_grad=True, knn_k=None, with_triplets=True, n_types=None, sizes=None, default_basis=True, mol_local=None,
-                max_num_neighbors=None, aux_tables=True, cell=None, strain=None, cell_images=None):
+                max_num_neighbors=None, aux_tables=True, cell=None, strain=None, cell_images=None, pbc=None):
     """Graph-construction part of PAMNet.forward (models.py:104-177).  Returns a Graph.
 
     `cell` (QM9 schema, bond-free, no `sizes`): fp32 [num_graphs, 3, 3] on the device, row k of cell[g] = lattice vector a_k of
@@ -1224,6 +1300,14 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
     2 * cutoff_l only (and not below cutoff_g / 4).  max_num_neighbors cuts no row of that graph: a cap that binds is a
     ValueError.  Always the step-by-step launches, whatever `mol_local` says: the rows of that multigraph repeat columns and may
     hold more than 64 entries, which the builder's adjacency masks (one bit per atom of the cell) cannot express.
+
+    `pbc` (periodic batches): a torch.bool tensor [num_graphs, 3] on the device, or three Python bools for every graph --
+    pbc[g, k]: graph g repeats along cell[g, k].  None or (True, True, True): the above, by the same entry points.  Along an open
+    axis the user's vector is not used (it may be zero, short or make the matrix singular), no displacement is wrapped, no height
+    condition applies and the all-image search tries no image (img_g[:, k] == 0); a graph with three open axes is an isolated
+    molecule whose arrays are bit for bit those of the open-space build.  The height conditions hold for the periodic axes, in
+    the lattice those axes span (cell_table).  Only the cell table and the image box are made differently; every kernel that
+    reads them is the fully periodic one.
 
     `strain` (periodic batches): the tensor that names the variable of the virial (differentiable_geometry) -- fp32 zeros
     [num_graphs, 3, 3] on the device.  Only validated here; its count of non-zero entries rides in the sizes' round trip.
@@ -1255,6 +1339,7 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
             n_graphs = int(batch[-1]) + 1
         cell = _checked_cell(cell, dataset, edge_index, sizes, n_graphs, pos)
     all_images = _checked_cell_images(cell_images, cell)
+    pbc = _checked_pbc(pbc, cell, n_graphs, pos)
     strain_nz = None if strain is None else _checked_strain(strain, cell, n_graphs, pos)
     max_nb = int(max_num_neighbors or 0)
     knn_k = KNN_K if knn_k is None else int(knn_k)
@@ -1290,7 +1375,7 @@ def build_graph(dataset, cutoff_l, cutoff_g, flow, x_raw, batch, pos=None, edge_
         raise ValueError("Invalid dataset. If you are using any dataset related to RNA 3D structure prediction, "
                          "be sure to use 'rna' as the first 3 characters of the dataset name.")
     a = _Args(cutoff_l, cutoff_g, flow, x_raw, pos, edge_index, need_grad, knn_k, with_triplets, n_types, sizes, mol_local,
-              max_nb, cell, strain_nz, all_images)
+              max_nb, cell, strain_nz, all_images, pbc)
     r = lists(g, ing, a)
     if r is not None:                             # (None: the molecule-local builder has made everything)
         _finish(g, r, dataset, a)

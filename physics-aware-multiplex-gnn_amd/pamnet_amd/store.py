@@ -38,7 +38,7 @@ def size_key(model, bonded=True):
 
 class Batch(object):
     """Duck-typed `data` of PAMNet.forward: x, pos, edge_index ([2, E] int32), batch (int32), y, num_graphs, sizes; a batch of
-    a periodic store also cell ([num_graphs, 3, 3] fp32) and never sizes."""
+    a periodic store also cell ([num_graphs, 3, 3] fp32), pbc ([num_graphs, 3] bool) when its items carry it, and never sizes."""
 
     def __init__(self):
         self._pamnet_prepared = None
@@ -59,7 +59,9 @@ class MoleculeStore(object):
     Periodic datasets: bond-free QM9-schema items that ALL carry `cell` ([3, 3], row k = lattice vector a_k).  The cells stay on
     the device (fp32 [M, 3, 3]) and a batch gets its own by one gather (`bt.cell`).  Such a store hands out no `sizes` (a batch
     with `cell` has no zero-round-trip route: graph.build_graph) but still vouches, per model, that every cell is within the
-    molecule-local builder's limits: its batches are then built by the cell table, two launches and one round trip."""
+    molecule-local builder's limits: its batches are then built by the cell table, two launches and one round trip.  The items of
+    a periodic store may all carry `pbc` (three bools: along which lattice vectors the item repeats; all False = an isolated
+    molecule, whose `cell` may be zero) or none may; the flags stay on the device (bool [M, 3]) and a batch gathers `bt.pbc`."""
 
     def __init__(self, data_list, device):
         self.device = torch.device(device)
@@ -68,7 +70,7 @@ class MoleculeStore(object):
             def __init__(self, d):
                 get = d.get if isinstance(d, dict) else (lambda k, default=None: getattr(d, k, default))
                 self.x, self.pos, self.edge_index, self.y = get('x'), get('pos'), get('edge_index'), get('y', None)
-                self.cell = get('cell', None)
+                self.cell, self.pbc = get('cell', None), get('pbc', None)
 
         data_list = [_View(d) for d in data_list]
         n = np.array([int(d.x.shape[0]) for d in data_list], dtype=np.int64)
@@ -91,6 +93,21 @@ class MoleculeStore(object):
                 if tuple(torch.as_tensor(d.cell).shape) != (3, 3):
                     raise ValueError('`cell` of a store item must have shape [3, 3] (row k = lattice vector a_k); got %s'
                                      % (tuple(torch.as_tensor(d.cell).shape),))
+        self.has_pbc = any(d.pbc is not None for d in data_list)
+        if self.has_pbc:
+            if not self.has_cell:
+                raise ValueError('`pbc` belongs to periodic items (`cell`): hand every item over with its `cell` ([3, 3]; the '
+                                 'vector of an open axis may be zero), or drop `pbc` for molecules in open space')
+            if any(d.pbc is None for d in data_list):
+                raise ValueError('a store carries `pbc` as a whole: either every item has its three bools or none does -- %d of '
+                                 '%d do; give the fully periodic items pbc = (True, True, True)'
+                                 % (sum(d.pbc is not None for d in data_list), len(data_list)))
+            for d in data_list:
+                v = d.pbc.tolist() if isinstance(d.pbc, (torch.Tensor, np.ndarray)) else d.pbc
+                if not isinstance(v, (tuple, list)) or len(v) != 3 or not all(isinstance(f, bool) for f in v):
+                    raise ValueError('`pbc` of a store item must be three bools (the item repeats along cell[k] where pbc[k] '
+                                     'is True); got %r' % (d.pbc,))
+                d.pbc = tuple(v)
         if self.has_edges:
             # remove_self_loops (models.py:63) once, at ingestion: resident bond lists are loop-free by construction, so
             # a batch never trips the forward's self-loop flag and the per-molecule counts describe what the forward uses
@@ -117,6 +134,7 @@ class MoleculeStore(object):
         ys = [getattr(d, 'y', None) for d in data_list]
         self.cell = (torch.stack([torch.as_tensor(d.cell).to(torch.float32) for d in data_list]).contiguous().to(dev)
                      if self.has_cell else None)                              # [M, 3, 3]
+        self.pbc = torch.tensor([d.pbc for d in data_list], dtype=torch.bool).to(dev) if self.has_pbc else None     # [M, 3]
         self.y = None if any(v is None for v in ys) else torch.as_tensor(
             np.array([float(torch.as_tensor(v).reshape(-1)[0]) for v in ys], dtype=np.float32)).to(dev)
         self.nptr_d = torch.from_numpy(self.nptr.astype(np.int32)).to(dev)
@@ -171,7 +189,8 @@ class MoleculeStore(object):
             g = G.build_graph(model.dataset, model.cutoff_l, model.cutoff_g, model.flow, bt.x, bt.batch, bt.pos, bt.edge_index,
                               num_graphs=b - a, need_grad=False, with_triplets=not model.small,
                               n_types=model.embeddings.size(0) if hasattr(model, 'embeddings') else None,
-                              max_num_neighbors=getattr(model, 'max_num_neighbors', None), cell=getattr(bt, 'cell', None))
+                              max_num_neighbors=getattr(model, 'max_num_neighbors', None), cell=getattr(bt, 'cell', None),
+                              pbc=getattr(bt, 'pbc', None))
             capped = capped or bool(getattr(g, 'capped', False))
             nodes = torch.from_numpy((self.nptr[a:b + 1] - self.nptr[a]).astype(np.int64)).to(self.device)
             pg, pl = g.glob.ptr.long()[nodes], g.loc.ptr.long()[nodes]
@@ -230,6 +249,8 @@ class MoleculeStore(object):
                  lib.ptr(self.y), lib.ptr(bt.y), lib.stream_of(bt.x))       # (the targets ride in the same launch)
         if self.has_cell:                                  # the cells of the batch: one gather with the uploaded selection
             bt.cell = torch.index_select(self.cell, 0, sel)
+        if self.has_pbc:                                   # and their periodic axes, the same way
+            bt.pbc = torch.index_select(self.pbc, 0, sel)
         bt.num_graphs = b
         # the batch is produced by work queued on this stream: a consumer on another stream (the input pipeline's side
         # stream, train.Prefetcher) waits for exactly this event

@@ -923,7 +923,7 @@ def _wait_inputs(stream, data):
     ev = getattr(data, 'inputs_ready', None)
     if ev is not None:
         stream.wait_event(ev)
-        for k in ('x', 'pos', 'edge_index', 'batch', 'cell', 'strain'):   # allocated on the producer's stream, read on this one
+        for k in ('x', 'pos', 'edge_index', 'batch', 'cell', 'strain', 'pbc'):   # allocated on the producer's stream, read on this one
             t = getattr(data, k, None)
             if isinstance(t, torch.Tensor) and t.is_cuda:
                 t.record_stream(stream)
