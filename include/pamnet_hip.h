@@ -884,12 +884,13 @@ typedef struct pamnet_embed_job {
     float* partial;
 } pamnet_embed_job;
 /* rows of the atom-type table: forward out[r, :] = table[idx[r], :] (zeros for idx outside [0, n_types)); backward
- * dtable[t, :] = sum_{r: idx[r] = t} g[r, :] through `scratch` (pamnet_reduce_scratch_bytes).  Width 128. */
+ * dtable[t, :] = sum_{r: idx[r] = t} g[r, :] through `scratch` (pamnet_type_rows_scratch_bytes(n_types, 128) bytes; up to 8
+ * rows that is pamnet_reduce_scratch_bytes).  Width 128. */
 typedef struct pamnet_type_rows_job {
     const float* table;      /* [n_types, 128] */
     const int32_t* idx;      /* [n] */
     int64_t n;
-    int64_t n_types;         /* <= 8 */
+    int64_t n_types;         /* 1 .. 128 (above 8: the wide type-row kernels, csrc/type_rows_core.h) */
     float* out;              /* forward [n, 128] */
     const float* g;          /* backward [n, 128] */
     void* scratch;           /* backward */
@@ -963,10 +964,15 @@ int pamnet_stack_bwd_f32(const int64_t* sizes, const int32_t* const* graph_idx, 
  *   pamnet_smooth_l1_loss_f32 : loss[0] = mean h(out - y), h(d) = d^2/2 if |d| < 1 else |d| - 1/2 (beta = 1);
  *                               d_out[i] = grad_scale * clamp(out[i] - y[i], -1, 1) / n       (main_rna_puzzles.py:92)
  *                               (all three: one launch, d_out nullable)
- *   pamnet_type_rows_grad_f32 : out[t,:] = sum_{r: idx[r] = t} g[r,:], t < n_types <= 8   (gradient of embeddings[x],
- *                               models.py:107,140); scratch: pamnet_reduce_scratch_bytes bytes of device memory
+ *   pamnet_type_rows_grad_f32 : out[t,:] = sum_{r: idx[r] = t} g[r,:], t < n_types <= 128   (gradient of embeddings[x],
+ *                               models.py:107,140); d in {4, 8, 16, ..., 256}; idx outside [0, n_types) adds nothing, a type
+ *                               that never occurs gets a zero row; no float atomics, fixed order.  scratch:
+ *                               pamnet_type_rows_scratch_bytes(n_types, d) bytes of device memory, no initialisation needed
+ *                               (n_types <= 8: the pamnet_reduce_scratch_bytes bytes; above: 1 KB of type sets + 64 partial
+ *                               tables, up to 8 MB at 128 x 256)
  * ------------------------------------------------------------------------------------------------------------------ */
 int pamnet_reduce_scratch_bytes(int64_t* bytes);
+int pamnet_type_rows_scratch_bytes(int64_t n_types, int64_t d, int64_t* bytes);
 /* dst[0:n] = src[0:n], 16 bytes per lane, non-temporal (n % 4 == 0): the memory-system calibration beside bench.py's roofline */
 int pamnet_stream_copy_f32(const float* src, float* dst, int64_t n, pamnet_stream_t stream);
 int pamnet_sumsq_partials_f32(const float* g, int64_t n, double* partials, pamnet_stream_t stream);

@@ -146,7 +146,7 @@ struct TJob {
     int n_types;
     float* out;                     // forward [n, 128]
     const float* g;                 // backward [n, 128]
-    float4* partial;                // backward scratch (pamnet_reduce_scratch_bytes)
+    float4* partial;                // backward scratch (pamnet_type_rows_scratch_bytes)
     float* dtable;                  // backward [n_types, 128]
     int nblk;
 };
@@ -531,7 +531,13 @@ __global__ __launch_bounds__(256, 2) void embed_multi_bwd_kernel(const EJobs J) 
         }
         bid -= jb.nblk;
     }
-    if (J.types.nblk)
+    if (!J.types.nblk) return;
+    if (J.types.n_types > type_rows::TYPE_MAX)             // a table of 9 .. 128 rows: masks, then partials, in the scratch
+        type_rows::grad_wide_body(reinterpret_cast<const float4*>(J.types.g), J.types.idx, J.types.n, J.types.n_types,
+                                  DOUT / 4, reinterpret_cast<uint32_t*>(J.types.partial),
+                                  J.types.partial + type_rows::TYPE_BLOCKS, bid, J.types.nblk,
+                                  reinterpret_cast<float4*>(Ds), reinterpret_cast<uint32_t*>(ks));
+    else
         type_rows::grad_body(reinterpret_cast<const float4*>(J.types.g), J.types.idx, J.types.n, J.types.n_types, DOUT / 4,
                              J.types.partial, bid, J.types.nblk, reinterpret_cast<float4*>(Ds));
 }
@@ -545,6 +551,10 @@ __global__ __launch_bounds__(256) void embed_multi_reduce_kernel(const EJobs J) 
         const int K = code_k(jb.code);
         if ((int)blockIdx.x * 32 >= 2 * DOUT * K + 2 * DOUT + 16) return;
         embed_reduce_body(jb, K, blockIdx.x, sm);
+    } else if (J.types.nblk && J.types.n_types > type_rows::TYPE_MAX) {
+        type_rows::finish_wide_body(reinterpret_cast<const uint32_t*>(J.types.partial),
+                                    J.types.partial + type_rows::TYPE_BLOCKS, J.types.nblk, J.types.n_types, DOUT / 4,
+                                    reinterpret_cast<float4*>(J.types.dtable), blockIdx.x);
     } else if (J.types.nblk && blockIdx.x == 0) {
         type_rows::finish_body(J.types.partial, J.types.nblk, J.types.n_types * (DOUT / 4),
                                reinterpret_cast<float4*>(J.types.dtable));
@@ -589,7 +599,7 @@ int make_job(const pamnet_embed_job& h, bool bwd, EJob* o) {
 int make_types(const pamnet_type_rows_job* h, bool bwd, TJob* o) {
     o->nblk = 0;
     if (!h) return PAMNET_OK;
-    if (h->n < 0 || h->n_types < 1 || h->n_types > type_rows::TYPE_MAX) return PAMNET_EINVAL;
+    if (h->n < 0 || h->n_types < 1 || h->n_types > type_rows::TYPE_ROWS_MAX) return PAMNET_EINVAL;
     if (!bwd && (!h->table || (h->n > 0 && (!h->idx || !h->out)))) return PAMNET_ENULL;
     if (bwd && (!h->dtable || !h->scratch || (h->n > 0 && (!h->idx || !h->g)))) return PAMNET_ENULL;
     o->table = h->table, o->idx = h->idx, o->n = h->n, o->n_types = (int)h->n_types, o->out = h->out, o->g = h->g;
@@ -651,6 +661,10 @@ int launch_multi(const pamnet_embed_job* jobs, int32_t n_jobs, const pamnet_type
     for (int j = 0; j < J.n; ++j) {
         const int per = 2 * DOUT * code_k(J.job[j].code) + 2 * DOUT + 16;
         gx = (per + 31) / 32 > gx ? (per + 31) / 32 : gx;
+    }
+    if (J.types.nblk && J.types.n_types > type_rows::TYPE_MAX) {       // the wide finish: one thread per cell (t, c)
+        const int fx = (J.types.n_types * (DOUT / 4) + 255) / 256;
+        gx = fx > gx ? fx : gx;
     }
     hipLaunchKernelGGL(embed_multi_reduce_kernel, dim3(gx, J.n + (J.types.nblk ? 1 : 0)), dim3(256), 0, st, J);
     PAMNET_LAUNCH_CHECK();

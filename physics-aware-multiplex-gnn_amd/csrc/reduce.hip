@@ -154,6 +154,22 @@ __global__ __launch_bounds__(256) void type_rows_finish_kernel(const float4* __r
     type_rows::finish_body(partial, blocks, cells, out);
 }
 
+// tables of 9 .. 128 rows (type_rows_core.h): the slices of type_rows_grad_kernel, eight present types per pass
+__global__ __launch_bounds__(256) void type_rows_grad_wide_kernel(const float4* __restrict__ g, const int32_t* __restrict__ idx,
+                                                                  int64_t n, int n_types, int d4, uint32_t* __restrict__ masks,
+                                                                  float4* __restrict__ partial) {
+    __shared__ float4 red[256];
+    __shared__ uint32_t seen[4];
+    type_rows::grad_wide_body(g, idx, n, n_types, d4, masks, partial, blockIdx.x, gridDim.x, red, seen);
+}
+
+// one thread per cell (t, c): n_types * d4 is up to 4 096 cells
+__global__ __launch_bounds__(256) void type_rows_finish_wide_kernel(const uint32_t* __restrict__ masks,
+                                                                    const float4* __restrict__ partial, int blocks,
+                                                                    int n_types, int d4, float4* __restrict__ out) {
+    type_rows::finish_wide_body(masks, partial, blocks, n_types, d4, out, blockIdx.x);
+}
+
 }  // namespace
 
 // scratch (caller-owned, device) of pamnet_type_rows_grad_f32: pamnet_reduce_scratch_bytes bytes, no initialisation needed
@@ -267,15 +283,36 @@ extern "C" int pamnet_smooth_l1_loss_f32(const float* out, const float* y, int64
     return loss_launch<2>(out, y, n, grad_scale, loss, d_out, stream);
 }
 
-// out[t, :] = sum_{r < n: idx[r] = t} g[r, :]  for t < n_types (<= 8), d in {16, 32, 64, 128, 256}; idx values outside
-// [0, n_types) contribute nothing.
+// scratch bytes of pamnet_type_rows_grad_f32 / the types job of pamnet_embed_multi_bwd_f32 for a table of n_types rows of d:
+// up to 8 rows what pamnet_reduce_scratch_bytes reports, above that the masks and partials of the wide kernels
+extern "C" int pamnet_type_rows_scratch_bytes(int64_t n_types, int64_t d, int64_t* bytes) {
+    const int64_t d4 = d / 4;
+    if (n_types < 1 || n_types > type_rows::TYPE_ROWS_MAX || d < 4 || (d & 3) || d4 > 64 || (d4 & (d4 - 1))) return PAMNET_EINVAL;
+    if (!bytes) return PAMNET_ENULL;
+    *bytes = n_types <= TYPE_MAX ? (int64_t)TYPE_BLOCKS * TYPE_MAX * 64 * 16 : type_rows::wide_scratch_bytes(n_types, d4);
+    return PAMNET_OK;
+}
+
+// out[t, :] = sum_{r < n: idx[r] = t} g[r, :]  for t < n_types (<= 128), d in {16, 32, 64, 128, 256}; idx values outside
+// [0, n_types) contribute nothing.  scratch: pamnet_type_rows_scratch_bytes(n_types, d).
 extern "C" int pamnet_type_rows_grad_f32(const float* g, const int32_t* idx, int64_t n, int64_t n_types, int64_t d,
                                          void* scratch, float* out, pamnet_stream_t stream) {
     const int64_t d4 = d / 4;
-    if (n < 0 || n_types < 1 || n_types > TYPE_MAX || d < 4 || (d & 3) || d4 > 64 || (d4 & (d4 - 1))) return PAMNET_EINVAL;
+    if (n < 0 || n_types < 1 || n_types > type_rows::TYPE_ROWS_MAX || d < 4 || (d & 3) || d4 > 64 || (d4 & (d4 - 1)))
+        return PAMNET_EINVAL;
     if (!out || !scratch || (n > 0 && (!g || !idx))) return PAMNET_ENULL;
     const int blocks = type_rows::blocks_for_rows(n);
     hipStream_t st = as_stream(stream);
+    if (n_types > TYPE_MAX) {
+        uint32_t* masks = static_cast<uint32_t*>(scratch);
+        float4* partial = static_cast<float4*>(scratch) + TYPE_BLOCKS;
+        hipLaunchKernelGGL(type_rows_grad_wide_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float4*)g, idx, n,
+                           (int)n_types, (int)d4, masks, partial);
+        hipLaunchKernelGGL(type_rows_finish_wide_kernel, dim3((unsigned)((n_types * d4 + 255) / 256)), dim3(256), 0, st,
+                           (const uint32_t*)masks, (const float4*)partial, (int)blocks, (int)n_types, (int)d4, (float4*)out);
+        PAMNET_LAUNCH_CHECK();
+        return PAMNET_OK;
+    }
     hipLaunchKernelGGL(type_rows_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float4*)g, idx, n,
                        (int)n_types, (int)d4, static_cast<float4*>(scratch));
     hipLaunchKernelGGL(type_rows_finish_kernel, dim3(1), dim3(256), 0, st, static_cast<const float4*>(scratch), (int)blocks,

@@ -267,7 +267,8 @@ class _PAMNetBase(nn.Module):
     small = False
     max_num_neighbors = 1000            # radius(..., max_num_neighbors=1000), models.py:110,128
 
-    def __init__(self, config, num_spherical=7, num_radial=6, envelope_exponent=5, _pad=True, num_atom_types=5):
+    def __init__(self, config, num_spherical=7, num_radial=6, envelope_exponent=5, _pad=True, num_atom_types=5,
+                 max_atomic_number=None):
         super().__init__()
         self.dataset = config.dataset
         self.config_dim = int(config.dim)
@@ -293,6 +294,21 @@ class _PAMNetBase(nn.Module):
         if num_atom_types != 5 and self.dataset != 'QM9':
             raise ValueError('num_atom_types applies to the QM9 schema only (PDBbind rows carry features, the RNA table has '
                              'its three types): dataset is %r' % (self.dataset,))
+        # ... or the table is indexed by atomic number: row z is the element z (row 0: an ordinary row, e.g. a placeholder
+        # species), `data.x` carries atomic numbers, and checkpoints of different element sets share their rows
+        if max_atomic_number is not None:
+            zmax = ops.TYPE_ROWS_MAX - 1
+            if (isinstance(max_atomic_number, bool) or not isinstance(max_atomic_number, int)
+                    or not 1 <= max_atomic_number <= zmax):
+                raise ValueError('max_atomic_number must be an integer in 1..%d (got %r)' % (zmax, max_atomic_number))
+            if num_atom_types != 5:
+                raise ValueError('max_atomic_number and num_atom_types are two ways to size the same table: give one '
+                                 '(got max_atomic_number=%r with num_atom_types=%r)' % (max_atomic_number, num_atom_types))
+            if self.dataset != 'QM9':
+                raise ValueError('max_atomic_number applies to the QM9 schema only (PDBbind rows carry features, the RNA '
+                                 'table has its three types): dataset is %r' % (self.dataset,))
+            num_atom_types = max_atomic_number + 1
+        self.max_atomic_number = max_atomic_number
         self.num_atom_types = num_atom_types
 
     # ---- parameter walks -------------------------------------------------------------------------------------------
@@ -440,7 +456,10 @@ class _PAMNetBase(nn.Module):
         if self.__dict__.get('_rng_at_ctor') is not None:
             _rng_restore(self.__dict__.pop('_rng_at_ctor'))
         base = PAMNet_s if self.small else PAMNet         # (explicit class: a subclass may have another constructor)
-        twin = base(*self._ctor, _pad=False, num_atom_types=self.num_atom_types)
+        if self.max_atomic_number is not None:            # (the same table: rows 0 .. Z)
+            twin = base(*self._ctor, _pad=False, max_atomic_number=self.max_atomic_number)
+        else:
+            twin = base(*self._ctor, _pad=False, num_atom_types=self.num_atom_types)
         tsd = twin.state_dict()
         self.__dict__['_logical_shapes'] = {k: tuple(v.shape) for k, v in tsd.items()}
         self._register_load_state_dict_pre_hook(self._pad_incoming)
@@ -836,8 +855,9 @@ def _slice_outgoing(module, state_dict, prefix, local_metadata):
 class PAMNet(_PAMNetBase):
     """models.py:21-224."""
 
-    def __init__(self, config, num_spherical=7, num_radial=6, envelope_exponent=5, _pad=True, *, num_atom_types=5):
-        super().__init__(config, num_spherical, num_radial, envelope_exponent, _pad, num_atom_types)
+    def __init__(self, config, num_spherical=7, num_radial=6, envelope_exponent=5, _pad=True, *, num_atom_types=5,
+                 max_atomic_number=None):
+        super().__init__(config, num_spherical, num_radial, envelope_exponent, _pad, num_atom_types, max_atomic_number)
         d = self.dim
         if self._rna:
             self.embeddings = nn.Parameter(torch.ones((3, d)))       # C, N, O
@@ -889,8 +909,9 @@ class PAMNet_s(_PAMNetBase):
     small = True
     max_num_neighbors = 500             # radius(..., max_num_neighbors=500), models.py:301
 
-    def __init__(self, config, num_spherical=7, num_radial=6, envelope_exponent=5, _pad=True, *, num_atom_types=5):
-        super().__init__(config, num_spherical, num_radial, envelope_exponent, _pad, num_atom_types)
+    def __init__(self, config, num_spherical=7, num_radial=6, envelope_exponent=5, _pad=True, *, num_atom_types=5,
+                 max_atomic_number=None):
+        super().__init__(config, num_spherical, num_radial, envelope_exponent, _pad, num_atom_types, max_atomic_number)
         d = self.dim
         self.embeddings = nn.Parameter(torch.ones((self.num_atom_types, d)))
         self._build_common(num_spherical, num_radial, envelope_exponent)

@@ -368,7 +368,7 @@ class _InputStage(torch.autograd.Function):
             gx = torch.zeros(idx.numel(), D, dtype=torch.float32, device=ref.device) if gx is None else gx.contiguous()
             keep.append(gx)
             tj = lib.TypeRowsJob(None, lib.ptr(idx), idx.numel(), table.size(0), None, lib.ptr(gx),
-                                 lib.ptr(reduce_scratch(ref.device)), lib.ptr(gtable))
+                                 lib.ptr(reduce_scratch(ref.device, table.size(0), D)), lib.ptr(gtable))
         lib.call('pamnet_embed_multi_bwd_f32', ctypes.addressof(jobs), n, ctypes.addressof(tj) if tj is not None else None,
                  lib.stream_of(ref))
         return (None, None) + _ret(direct, g)

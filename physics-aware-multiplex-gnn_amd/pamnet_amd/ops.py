@@ -283,20 +283,35 @@ class _GatherMulAggregate(torch.autograd.Function):
 _SCRATCH = {}
 
 
-def reduce_scratch(dev):
-    """Scratch of pamnet_type_rows_grad_f32 (csrc/reduce.hip), one per (device, stream)."""
+_SCRATCH_BYTES = {}
+
+
+def reduce_scratch(dev, n_types=None, d=None):
+    """Scratch of pamnet_type_rows_grad_f32 (csrc/reduce.hip), one per (device, stream).  With (n_types, d) of a table of
+    more than TYPE_MAX rows it is what pamnet_type_rows_scratch_bytes asks for and grows by need (up to 8 MB at 128 x 256:
+    only a model with such a table ever allocates it); else the fixed 512 KB of the 8-row kernels."""
     import ctypes
     key = (dev, torch.cuda.current_stream(dev).cuda_stream)
     t = _SCRATCH.get(key)
-    if t is None:
-        need = ctypes.c_int64(0)
-        lib.call('pamnet_reduce_scratch_bytes', ctypes.addressof(need))
-        t = _SCRATCH[key] = torch.zeros(int(need.value) // 4, dtype=torch.int32, device=dev)
+    wide = (int(n_types), int(d)) if (n_types is not None and n_types > TYPE_MAX) else None
+    if t is not None and wide is None and t.numel() * 4 >= _SCRATCH_BYTES.get(None, 1 << 62):
+        return t
+    need = _SCRATCH_BYTES.get(wide)
+    if need is None:
+        q = ctypes.c_int64(0)
+        if wide is None:
+            lib.call('pamnet_reduce_scratch_bytes', ctypes.addressof(q))
+        else:
+            lib.call('pamnet_type_rows_scratch_bytes', wide[0], wide[1], ctypes.addressof(q))
+        need = _SCRATCH_BYTES[wide] = int(q.value)
+    if t is None or t.numel() * 4 < need:
+        # (launches already on the stream keep reading the old buffer: the caching allocator orders its reuse after them)
+        t = _SCRATCH[key] = torch.zeros(need // 4, dtype=torch.int32, device=dev)
     return t
 
 
 class _TypeRows(torch.autograd.Function):
-    """out[k] = table[idx[k]] for a table of <= 8 rows (`embeddings[x]`, models.py:107,140).  The backward sums the rows
+    """out[k] = table[idx[k]] for a table of <= 128 rows (`embeddings[x]`, models.py:107,140).  The backward sums the rows
     of the incoming gradient per type in one launch -- no transposed index list to build."""
 
     @staticmethod
@@ -314,16 +329,17 @@ class _TypeRows(torch.autograd.Function):
         rows, d = ctx.shape
         gt = ctx.direct if ctx.direct is not None else torch.empty((rows, d), dtype=g.dtype, device=g.device)
         lib.call('pamnet_type_rows_grad_f32', lib.ptr(g), lib.ptr(ctx.idx), ctx.idx.numel(), rows, d,
-                 lib.ptr(reduce_scratch(g.device)), lib.ptr(gt), lib.stream_of(g))
+                 lib.ptr(reduce_scratch(g.device, rows, d)), lib.ptr(gt), lib.stream_of(g))
         return (None if ctx.direct is not None else gt), None, None
 
 
-TYPE_MAX = 8          # rows of a type table the kernels take (type_rows::TYPE_MAX, csrc/type_rows_core.h)
+TYPE_MAX = 8          # rows of a compact type table, `num_atom_types` (type_rows::TYPE_MAX, csrc/type_rows_core.h)
+TYPE_ROWS_MAX = 128   # rows of a type table the kernels take: tables indexed by atomic number (type_rows::TYPE_ROWS_MAX)
 
 
 def type_rows_supported(table):
     d4 = table.size(1) // 4
-    return table.is_cuda and table.size(0) <= TYPE_MAX and table.size(1) % 4 == 0 and 1 <= d4 <= 64 and (d4 & (d4 - 1)) == 0
+    return table.is_cuda and table.size(0) <= TYPE_ROWS_MAX and table.size(1) % 4 == 0 and 1 <= d4 <= 64 and (d4 & (d4 - 1)) == 0
 
 
 def type_rows(table, idx, direct_grad=None, tape=None):
