@@ -561,6 +561,8 @@ int pamnet_pos_bwd_img_virial_f32(const float* pos, const double* cell_table, co
  * outs/atts: [2L, n] rows ordered (global_0, local_0, global_1, local_1, ...).
  *   node_out[n] = sign[n] * sum_l sum_c outs[l,c,n] * softmax_c(leaky_relu(atts[l,c,n], 0.2))
  *   graph_out[b] = (mean ? 1/|b| : 1) * sum_{n in b} node_out[n];  sign may be NULL (=1).
+ * A graph without nodes gets 0 (sum and mean).  n == 0 with n_graphs > 0 is valid: graph_out[0 .. n_graphs) is written as
+ * zeros and no other pointer is read; the backward with n == 0 writes nothing.
  * ------------------------------------------------------------------------------------------------------------------ */
 int pamnet_fuse_pool_fwd_f32(const float* outs, const float* atts, int64_t n_layer, int64_t n, const float* sign,
                              const int32_t* gptr, int64_t n_graphs, int32_t mean, float* node_out, float* graph_out,
