@@ -557,6 +557,40 @@ int pamnet_pos_bwd_img_virial_f32(const float* pos, const double* cell_table, co
                                   pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Structure relaxation: one FIRE step (Bitzek et al., Phys. Rev. Lett. 97, 170201, 2006; unit masses) of every graph of a
+ * batch, in one launch (csrc/relax.hip; the reference has no optimiser of structures).  Each graph carries its own state, so
+ * its trajectory does not depend on what else the batch holds.
+ *   pos, vel [n, 3] fp32, updated in place;  dpos [n, 3] fp32 = dE/dpos, f = -dpos;  fixed [n] uint8 or NULL: an atom
+ *   with fixed[a] != 0 has f = v = 0, enters no sum and no maximum, and its rows of pos and vel are neither read nor
+ *   written;  gptr [n_graphs + 1]: first atom of every graph (kept inside [0, n]).
+ *   Per graph: dt, a [n_graphs] fp64;  n_pos, steps, status [n_graphs] int32 (status 0 = running, 1 = converged, 2 = failed);
+ *   fmax [n_graphs] fp32 (output).  The caller starts with vel = 0, dt = dt0, a = a0, n_pos = steps = status = 0.
+ *   fmax_tol_g [n_graphs] fp32 or NULL: the convergence threshold of every graph; NULL: fmax_tol for all.
+ * The step of graph g, all sums and maxima over the free atoms of g:
+ *   1. status[g] != 0: nothing that belongs to g is read-modified or written.
+ *   2. F2 = sum |f|^2, fm = max |f| (NaN-propagating); fmax[g] = fm.  F2 not finite: status[g] = 2, nothing else changes.
+ *      Else fm < tolerance: status[g] = 1, nothing else changes (a graph without free atoms has fm = 0).
+ *   3. P = sum f.v, V2 = sum |v|^2.  V2 == 0 (the first step): nothing.  Else P > 0: n_pos += 1; if n_pos > n_min then
+ *      dt = min(dt f_inc, dt_max) and a *= f_a; then v <- (1 - a) v + a sqrt(V2 / F2) f.  Else (P <= 0): v <- 0, a = a0,
+ *      dt *= f_dec, n_pos = 0.
+ *   4. v <- v + dt f.
+ *   5. dr = dt v, s = min(1, max_step / max |dr|) (s = 1 where the maximum is 0), pos <- pos + s dr.  v is not scaled.
+ *   6. steps[g] += 1.
+ * THE ORDER: the graph's decision comes first -- n_pos, dt and a are updated before any atom moves -- so the mixing of step 3
+ * uses the updated a and steps 4 and 5 the updated dt.
+ * Arithmetic in fp64 from the fp32 inputs, one rounding to fp32 at each store of pos and vel.  Sums in a fixed order (a
+ * thread's atoms ascending, wavefront butterfly, the wavefronts in order through LDS), no atomics: the outputs of a graph
+ * are bitwise repeatable and bitwise the same whether it is stepped alone or inside any batch.  One workgroup per graph.
+ * Returns PAMNET_ENULL for a null required pointer; PAMNET_EINVAL for a negative count, n_graphs above 2^31 - 1, n_min < 0, a NaN fmax_tol, or one of
+ * dt_max, max_step, f_inc, f_dec, a0, f_a that is not positive and finite.  n_graphs == 0 launches nothing.  (Part of ABI 18:
+ * nothing existing changed.)
+ * ------------------------------------------------------------------------------------------------------------------ */
+int pamnet_fire_step_f32(float* pos, float* vel, const float* dpos, const uint8_t* fixed, const int32_t* gptr, int64_t n,
+                         int64_t n_graphs, double* dt, double* a, int32_t* n_pos, int32_t* steps, int32_t* status, float* fmax,
+                         const float* fmax_tol_g, double fmax_tol, double dt_max, double max_step, int32_t n_min, double f_inc,
+                         double f_dec, double a0, double f_a, pamnet_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Attention fusion + per-graph pooling  (models.py:206-224)
  * outs/atts: [2L, n] rows ordered (global_0, local_0, global_1, local_1, ...).
  *   node_out[n] = sign[n] * sum_l sum_c outs[l,c,n] * softmax_c(leaky_relu(atts[l,c,n], 0.2))
