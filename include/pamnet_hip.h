@@ -187,9 +187,10 @@ int pamnet_radius_img_fill_i32(const float* pos, const double* cell_table, const
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Per-axis periodicity: slabs, wires and isolated molecules beside bulk cells (part of ABI 18: nothing existing changed).
- * pbc [n_graphs, 3] bytes: graph g repeats along lattice vector k when pbc[3 g + k] != 0.  The two entry points below stand in
- * for their twins; every other periodic entry point takes the table they make as it is.
- *   pamnet_cell_prepare_axes_f64: pamnet_cell_prepare_f64 on the COMPLETED cell.  The vector handed over along an open axis is
+ * pbc [n_graphs, 3] bytes: graph g repeats along lattice vector k when pbc[3 g + k] != 0.  The two entry points below are
+ * pamnet_cell_prepare_f64 / pamnet_cell_images_i32 with that argument -- one kernel serves each pair, the entry points without
+ * pbc are the case of three periodic axes; every other periodic entry point takes the table they make as it is.
+ *   pamnet_cell_prepare_axes_f64: the table of the COMPLETED cell.  The vector handed over along an open axis is
  *     not used (it may be zero, short, or make the matrix singular); in its place stands a unit vector orthogonal to the
  *     periodic ones -- two periodic axes i, j: a_k' = a_i x a_j / |a_i x a_j|; one periodic axis i: a_j' = a_i x e normalised, e
  *     the coordinate unit vector along a_i's component of smallest magnitude (lowest index on ties), and a_k' = a_i x a_j'
@@ -197,8 +198,9 @@ int pamnet_radius_img_fill_i32(const float* pos, const double* cell_table, const
  *     form fractional component k of every open axis k set to +0.0: the image rule then rounds that component to 0 for every
  *     pair, so nothing is wrapped along k.  ORs 128 into *flag when the periodic vectors are degenerate (zero, parallel, not
  *     finite) or the height |det'| / |a_i' x a_j'| of a PERIODIC axis does not exceed 2 * cutoff; open axes are not tested.  A
- *     row with all three flags set gets pamnet_cell_prepare_f64's 18 doubles and verdict bit for bit.
- *   pamnet_cell_images_axes_i32: pamnet_cell_images_i32 on that table with N_k = 0 and no verdict along open axes.
+ *     row with all three flags set is the cell as given: pamnet_cell_prepare_f64's 18 doubles and verdict bit for bit.  A null
+ *     pbc is refused (PAMNET_ENULL).
+ *   pamnet_cell_images_axes_i32: the box of that table with N_k = 0 and no verdict along open axes; null pbc refused likewise.
  * ------------------------------------------------------------------------------------------------------------------ */
 int pamnet_cell_prepare_axes_f64(const float* cell, const uint8_t* pbc, int64_t n_graphs, float cutoff, double* cell_table,
                                  int32_t* flag, pamnet_stream_t stream);

@@ -19,67 +19,39 @@
 
 namespace {
 
-struct V3 {
-    double x, y, z;
+// (V3 and its algebra, load_pos and the policies OpenDiff / PeriodicDiff / ImageDiff: geom_core.h)
+
+// The lists of the backward, as the kernels take them (by value, inside the records below).
+struct Csr {                      // rows by pointer, one (row, col) per entry
+    const int32_t *ptr, *row, *col;
 };
-__device__ __forceinline__ V3 v3(double x, double y, double z) { return V3{x, y, z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3 operator*(double s, V3 a) { return v3(s * a.x, s * a.y, s * a.z); }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-// every product rounded on its own (no fma contraction): for b = -a each component is then exactly 0, so |a x b| = 0
-// takes the exact-zero branch of angle_grads instead of a residue whose direction is noise
-__device__ __forceinline__ V3 cross(V3 a, V3 b) {
-    return v3(__dsub_rn(__dmul_rn(a.y, b.z), __dmul_rn(a.z, b.y)), __dsub_rn(__dmul_rn(a.z, b.x), __dmul_rn(a.x, b.z)),
-              __dsub_rn(__dmul_rn(a.x, b.y), __dmul_rn(a.y, b.x)));
-}
-__device__ __forceinline__ V3 load_pos(const float* __restrict__ pos, int64_t i) {
-    return v3((double)pos[3 * i], (double)pos[3 * i + 1], (double)pos[3 * i + 2]);
-}
-// How the backward turns two atoms into p_a - p_b: the fp64 difference in open space, or the minimum-image displacement of
-// a periodic cell -- geom_core.h min_image, the function the forward's kernels chose the image with, kept in fp64 here.  The
-// image integers do not depend on the positions differentiably, so every derivative below is the open-space one.
-struct OpenDiff {
-    __device__ __forceinline__ void bind(const int32_t* __restrict__, int64_t) {}
-    __device__ __forceinline__ V3 diff(const float* __restrict__ pos, int64_t a, int64_t b) const {
-        return load_pos(pos, a) - load_pos(pos, b);
-    }
-    __device__ __forceinline__ V3 from(V3 pa, const float* __restrict__ pos, int64_t b) const { return pa - load_pos(pos, b); }
-    // global edge q seen from atom a: its row (towards the column b), its column (towards the row b)
-    __device__ __forceinline__ V3 row_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t) const { return from(pa, pos, b); }
-    __device__ __forceinline__ V3 col_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t) const { return from(pa, pos, b); }
+struct CsrT {                     // its transpose: rows by pointer, the entries' positions in the list
+    const int32_t *ptr, *perm;
 };
-struct PeriodicDiff {
-    const double* __restrict__ table;
-    PbcCell t;
-    __device__ __forceinline__ void bind(const int32_t* __restrict__ node_graph, int64_t atom) {
-        t = load_cell(table, node_graph[atom]);
-    }
-    __device__ __forceinline__ V3 diff(const float* __restrict__ pos, int64_t a, int64_t b) const {
-        const Disp d = min_image(t, pos, a, b);
-        return v3(d.x, d.y, d.z);
-    }
-    // pa: an fp32 position held as doubles (load_pos)
-    __device__ __forceinline__ V3 from(V3 pa, const float* __restrict__ pos, int64_t b) const {
-        const Disp d = min_image(t, (float)pa.x, (float)pa.y, (float)pa.z, pos[3 * b], pos[3 * b + 1], pos[3 * b + 2]);
-        return v3(d.x, d.y, d.z);
-    }
-    __device__ __forceinline__ V3 row_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t) const { return from(pa, pos, b); }
-    __device__ __forceinline__ V3 col_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t) const { return from(pa, pos, b); }
+struct BondGradArgs {
+    const float* pos;
+    Space space;
+    Csr l;                        // local edges (ptr unused)
+    const float* ddist;
+    int64_t el;
+    Csr t;                        // triplet / pair rows: ptr by target edge, row = target edge, col = source edge
+    const int32_t* t_kind;
+    CsrT tt;
+    const float* dangle;
+    double* G;                    // [el, 3] out
 };
-// A periodic graph whose GLOBAL list holds every image within the cutoff (pamnet_radius_img_fill_i32): global edge q is the vector
-// v_q = p_row - p_col - img[q] @ cell of its stored image, not a rounded one (geom_core.h image_disp).  Seen from its column the
-// edge is -v_q.  Local edges, and so diff / from, stay minimum-image.
-struct ImageDiff : PeriodicDiff {
-    const int32_t* __restrict__ img;
-    __device__ __forceinline__ V3 row_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t q) const {
-        const Disp d = image_disp(t, (float)pa.x, (float)pa.y, (float)pa.z, pos[3 * b], pos[3 * b + 1], pos[3 * b + 2], img, q);
-        return v3(d.x, d.y, d.z);
-    }
-    __device__ __forceinline__ V3 col_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t q) const {
-        const Disp d = image_disp(t, pos[3 * b], pos[3 * b + 1], pos[3 * b + 2], (float)pa.x, (float)pa.y, (float)pa.z, img, q);
-        return v3(-d.x, -d.y, -d.z);
-    }
+struct PosGradArgs {
+    const float* pos;
+    Space space;
+    int64_t n;
+    Csr g;
+    CsrT gt;
+    const float* ddist_g;
+    Csr l;                        // (row unused)
+    CsrT lt;
+    const double* G;
+    float* dpos;
+    double* atom_work;            // VIRIAL: [n, 9] out
 };
 
 // u_e = p[src] - p[dst] of local edge e (loc: rows = dst, col = src)
@@ -131,7 +103,7 @@ __device__ __forceinline__ void bond_grad(GEOM geom, const int32_t* __restrict__
     const int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (e >= el) return;                                          // (uniform over the wavefront)
-    geom.bind(node_graph, l_row[e]);                              // (every bond of e's rows lies in e's graph)
+    if (node_graph) geom.bind(node_graph[l_row[e]]);              // (every bond of e's rows lies in e's graph)
     const V3 u = bond(geom, pos, l_row, l_col, e);
     V3 acc = v3(0.0, 0.0, 0.0);
     if (lane == 0) {
@@ -159,28 +131,12 @@ __device__ __forceinline__ void bond_grad(GEOM geom, const int32_t* __restrict__
     }
 }
 
-__global__ __launch_bounds__(256) void bond_grad_kernel(const float* __restrict__ pos, const int32_t* __restrict__ l_row,
-                                                        const int32_t* __restrict__ l_col, const float* __restrict__ ddist,
-                                                        int64_t el, const int32_t* __restrict__ t_ptr,
-                                                        const int32_t* __restrict__ t_row, const int32_t* __restrict__ t_col,
-                                                        const int32_t* __restrict__ t_kind, const int32_t* __restrict__ tt_ptr,
-                                                        const int32_t* __restrict__ tt_perm, const float* __restrict__ dangle,
-                                                        double* __restrict__ G) {
-    bond_grad(OpenDiff{}, nullptr, pos, l_row, l_col, ddist, el, t_ptr, t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, G);
-}
-
-__global__ __launch_bounds__(256) void bond_grad_pbc_kernel(const float* __restrict__ pos, const double* __restrict__ cells,
-                                                            const int32_t* __restrict__ node_graph,
-                                                            const int32_t* __restrict__ l_row, const int32_t* __restrict__ l_col,
-                                                            const float* __restrict__ ddist, int64_t el,
-                                                            const int32_t* __restrict__ t_ptr, const int32_t* __restrict__ t_row,
-                                                            const int32_t* __restrict__ t_col, const int32_t* __restrict__ t_kind,
-                                                            const int32_t* __restrict__ tt_ptr,
-                                                            const int32_t* __restrict__ tt_perm,
-                                                            const float* __restrict__ dangle, double* __restrict__ G) {
-    PeriodicDiff geom;
-    geom.table = cells;
-    bond_grad(geom, node_graph, pos, l_row, l_col, ddist, el, t_ptr, t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, G);
+template <class GEOM>
+__global__ __launch_bounds__(256) void bond_grad_kernel(BondGradArgs a) {
+    GEOM geom;
+    geom.attach(a.space);
+    bond_grad(geom, a.space.node_graph, a.pos, a.l.row, a.l.col, a.ddist, a.el, a.t.ptr, a.t.row, a.t.col, a.t_kind, a.tt.ptr,
+              a.tt.perm, a.dangle, a.G);
 }
 
 // One wavefront per atom a, the lanes striding over: the global edges of row a and of column a (transposed list), then the
@@ -200,7 +156,7 @@ __device__ __forceinline__ void pos_grad(GEOM geom, const int32_t* __restrict__ 
     const int64_t a = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (a >= n) return;                                           // (uniform over the wavefront)
-    geom.bind(node_graph, a);
+    if (node_graph) geom.bind(node_graph[a]);
     const V3 pa = load_pos(pos, a);
     V3 acc = v3(0.0, 0.0, 0.0);
     V3 vx = v3(0.0, 0.0, 0.0), vy = vx, vz = vx;                  // VIRIAL: rows of the 3 x 3 sum
@@ -255,59 +211,12 @@ __device__ __forceinline__ void pos_grad(GEOM geom, const int32_t* __restrict__ 
     }
 }
 
-__global__ __launch_bounds__(256) void pos_grad_kernel(const float* __restrict__ pos, int64_t n,
-                                                       const int32_t* __restrict__ g_ptr, const int32_t* __restrict__ g_row,
-                                                       const int32_t* __restrict__ g_col, const int32_t* __restrict__ gt_ptr,
-                                                       const int32_t* __restrict__ gt_perm, const float* __restrict__ ddist_g,
-                                                       const int32_t* __restrict__ l_ptr, const int32_t* __restrict__ lt_ptr,
-                                                       const int32_t* __restrict__ lt_perm, const double* __restrict__ G,
-                                                       float* __restrict__ dpos) {
-    pos_grad<OpenDiff, false>(OpenDiff{}, nullptr, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm, G,
-                              dpos);
-}
-
-__global__ __launch_bounds__(256) void pos_grad_pbc_kernel(const float* __restrict__ pos, const double* __restrict__ cells,
-                                                           const int32_t* __restrict__ node_graph, int64_t n,
-                                                           const int32_t* __restrict__ g_ptr, const int32_t* __restrict__ g_row,
-                                                           const int32_t* __restrict__ g_col, const int32_t* __restrict__ gt_ptr,
-                                                           const int32_t* __restrict__ gt_perm,
-                                                           const float* __restrict__ ddist_g, const int32_t* __restrict__ l_ptr,
-                                                           const int32_t* __restrict__ lt_ptr,
-                                                           const int32_t* __restrict__ lt_perm, const double* __restrict__ G,
-                                                           float* __restrict__ dpos) {
-    PeriodicDiff geom;
-    geom.table = cells;
-    pos_grad<PeriodicDiff, false>(geom, node_graph, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm,
-                                  G, dpos);
-}
-
-__global__ __launch_bounds__(256) void pos_grad_pbc_virial_kernel(
-    const float* __restrict__ pos, const double* __restrict__ cells, const int32_t* __restrict__ node_graph, int64_t n,
-    const int32_t* __restrict__ g_ptr, const int32_t* __restrict__ g_row, const int32_t* __restrict__ g_col,
-    const int32_t* __restrict__ gt_ptr, const int32_t* __restrict__ gt_perm, const float* __restrict__ ddist_g,
-    const int32_t* __restrict__ l_ptr, const int32_t* __restrict__ l_col, const int32_t* __restrict__ lt_ptr,
-    const int32_t* __restrict__ lt_perm, const double* __restrict__ G, float* __restrict__ dpos,
-    double* __restrict__ atom_work) {
-    PeriodicDiff geom;
-    geom.table = cells;
-    pos_grad<PeriodicDiff, true>(geom, node_graph, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm,
-                                 G, dpos, l_col, atom_work);
-}
-
-// The two periodic forms for a global list over all images: g_img [eg, 3] is the image of every global edge.
-template <bool VIRIAL>
-__global__ __launch_bounds__(256) void pos_grad_img_kernel(
-    const float* __restrict__ pos, const double* __restrict__ cells, const int32_t* __restrict__ node_graph, int64_t n,
-    const int32_t* __restrict__ g_ptr, const int32_t* __restrict__ g_row, const int32_t* __restrict__ g_col,
-    const int32_t* __restrict__ g_img, const int32_t* __restrict__ gt_ptr, const int32_t* __restrict__ gt_perm,
-    const float* __restrict__ ddist_g, const int32_t* __restrict__ l_ptr, const int32_t* __restrict__ l_col,
-    const int32_t* __restrict__ lt_ptr, const int32_t* __restrict__ lt_perm, const double* __restrict__ G,
-    float* __restrict__ dpos, double* __restrict__ atom_work) {
-    ImageDiff geom;
-    geom.table = cells;
-    geom.img = g_img;
-    pos_grad<ImageDiff, VIRIAL>(geom, node_graph, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm, G,
-                                dpos, l_col, atom_work);
+template <class GEOM, bool VIRIAL>
+__global__ __launch_bounds__(256) void pos_grad_kernel(PosGradArgs a) {
+    GEOM geom;
+    geom.attach(a.space);
+    pos_grad<GEOM, VIRIAL>(geom, a.space.node_graph, a.pos, a.n, a.g.ptr, a.g.row, a.g.col, a.gt.ptr, a.gt.perm, a.ddist_g, a.l.ptr,
+                           a.lt.ptr, a.lt.perm, a.G, a.dpos, a.l.col, a.atom_work);
 }
 
 // One workgroup of 256 threads per graph g: the threads stride over the atoms gptr[g] .. gptr[g + 1] of atom_work (kept inside
@@ -343,7 +252,69 @@ __global__ __launch_bounds__(256) void virial_reduce_kernel(const double* __rest
     }
 }
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)(n > 0 ? ceil_div(n, 256) : 1); }
+// Everything a position backward reads and writes; the five entry points fill it.
+struct PosBwdArgs {
+    const float* pos;
+    Space space;
+    int64_t n;
+    Csr g;
+    CsrT gt;
+    const float* ddist_g;
+    int64_t eg;
+    Csr l;
+    CsrT lt;
+    const float* ddist_l;
+    int64_t el;
+    Csr t;
+    const int32_t* t_kind;
+    CsrT tt;
+    const float* dangle;
+    int64_t tp;
+    double* bond_work;
+    float* dpos;
+    const int32_t* gptr;          // the virial forms' four, else null / 0
+    int64_t n_graphs;
+    double* atom_work;
+    float* dstrain;
+};
+
+enum class SpaceKind { Open, Periodic, Images };
+
+bool has(const Csr& c) { return c.ptr && c.row && c.col; }
+bool has(const CsrT& c) { return c.ptr && c.perm; }
+
+// bond_grad (when there are local edges) -> pos_grad -> virial_reduce (the virial forms; also without atoms: every graph's
+// atom range is then empty and dstrain becomes zeros).  A null pointer is PAMNET_EINVAL here, judged before n == 0.
+int pos_bwd(const PosBwdArgs& a, SpaceKind kind, bool virial, pamnet_stream_t stream) {
+    if (a.n < 0 || a.eg < 0 || a.el < 0 || a.tp < 0 || a.n_graphs < 0) return PAMNET_EINVAL;
+    if (!a.pos || !has(a.g) || !has(a.gt) || !a.ddist_g || !has(a.l) || !has(a.lt) || !a.ddist_l || !has(a.t) || !a.t_kind ||
+        !has(a.tt) || !a.dangle || !a.bond_work || !a.dpos)
+        return PAMNET_EINVAL;
+    if (kind != SpaceKind::Open && (!a.space.cells || !a.space.node_graph)) return PAMNET_EINVAL;
+    if (kind == SpaceKind::Images && !a.space.img) return PAMNET_EINVAL;
+    if (virial && (!a.gptr || !a.atom_work || !a.dstrain)) return PAMNET_EINVAL;
+    hipStream_t st = as_stream(stream);
+    const bool open = kind == SpaceKind::Open, img = kind == SpaceKind::Images;
+    if (a.n > 0) {
+        if (a.el > 0) {                                           // (local edges are minimum-image in both periodic spaces)
+            const BondGradArgs b{a.pos, a.space, a.l, a.ddist_l, a.el, a.t, a.t_kind, a.tt, a.dangle, a.bond_work};
+            void (*kernel)(BondGradArgs) = open ? bond_grad_kernel<OpenDiff> : bond_grad_kernel<PeriodicDiff>;
+            hipLaunchKernelGGL(kernel, dim3(blocks_for(a.el, 4)), dim3(256), 0, st, b);
+            PAMNET_LAUNCH_CHECK();
+        }
+        const PosGradArgs p{a.pos, a.space, a.n, a.g, a.gt, a.ddist_g, a.l, a.lt, a.bond_work, a.dpos, a.atom_work};
+        void (*kernel)(PosGradArgs) = open     ? pos_grad_kernel<OpenDiff, false>
+                                      : virial ? (img ? pos_grad_kernel<ImageDiff, true> : pos_grad_kernel<PeriodicDiff, true>)
+                                               : (img ? pos_grad_kernel<ImageDiff, false> : pos_grad_kernel<PeriodicDiff, false>);
+        hipLaunchKernelGGL(kernel, dim3(blocks_for(a.n, 4)), dim3(256), 0, st, p);
+        PAMNET_LAUNCH_CHECK();
+    }
+    if (virial && a.n_graphs > 0) {
+        hipLaunchKernelGGL(virial_reduce_kernel, dim3((unsigned)a.n_graphs), dim3(256), 0, st, a.atom_work, a.gptr, a.n, a.dstrain);
+        PAMNET_LAUNCH_CHECK();
+    }
+    return PAMNET_OK;
+}
 
 }  // namespace
 
@@ -354,21 +325,10 @@ extern "C" int pamnet_pos_bwd_f32(const float* pos, int64_t n, const int32_t* g_
                                   const int32_t* t_ptr, const int32_t* t_row, const int32_t* t_col, const int32_t* t_kind,
                                   const int32_t* tt_ptr, const int32_t* tt_perm, const float* dangle, int64_t tp,
                                   double* bond_work, float* dpos, pamnet_stream_t stream) {
-    if (n < 0 || eg < 0 || el < 0 || tp < 0) return PAMNET_EINVAL;
-    if (!pos || !g_ptr || !g_row || !g_col || !gt_ptr || !gt_perm || !ddist_g || !l_ptr || !l_row || !l_col || !lt_ptr ||
-        !lt_perm || !ddist_l || !t_ptr || !t_row || !t_col || !t_kind || !tt_ptr || !tt_perm || !dangle || !bond_work || !dpos)
-        return PAMNET_EINVAL;
-    if (n == 0) return PAMNET_OK;
-    hipStream_t st = as_stream(stream);
-    if (el > 0) {
-        hipLaunchKernelGGL(bond_grad_kernel, dim3(blocks_for(el * 64)), dim3(256), 0, st, pos, l_row, l_col, ddist_l, el, t_ptr,
-                           t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, bond_work);
-        PAMNET_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(pos_grad_kernel, dim3(blocks_for(n * 64)), dim3(256), 0, st, pos, n, g_ptr, g_row, g_col, gt_ptr, gt_perm,
-                       ddist_g, l_ptr, lt_ptr, lt_perm, bond_work, dpos);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
+    const PosBwdArgs a{pos, {}, n, {g_ptr, g_row, g_col}, {gt_ptr, gt_perm}, ddist_g, eg,
+                       {l_ptr, l_row, l_col}, {lt_ptr, lt_perm}, ddist_l, el,
+                       {t_ptr, t_row, t_col}, t_kind, {tt_ptr, tt_perm}, dangle, tp, bond_work, dpos};
+    return pos_bwd(a, SpaceKind::Open, false, stream);
 }
 
 extern "C" int pamnet_pos_bwd_pbc_f32(const float* pos, const double* cell_table, const int32_t* node_graph, int64_t n,
@@ -378,22 +338,10 @@ extern "C" int pamnet_pos_bwd_pbc_f32(const float* pos, const double* cell_table
                                       const float* ddist_l, int64_t el, const int32_t* t_ptr, const int32_t* t_row,
                                       const int32_t* t_col, const int32_t* t_kind, const int32_t* tt_ptr, const int32_t* tt_perm,
                                       const float* dangle, int64_t tp, double* bond_work, float* dpos, pamnet_stream_t stream) {
-    if (n < 0 || eg < 0 || el < 0 || tp < 0) return PAMNET_EINVAL;
-    if (!pos || !cell_table || !node_graph || !g_ptr || !g_row || !g_col || !gt_ptr || !gt_perm || !ddist_g || !l_ptr ||
-        !l_row || !l_col || !lt_ptr || !lt_perm || !ddist_l || !t_ptr || !t_row || !t_col || !t_kind || !tt_ptr || !tt_perm ||
-        !dangle || !bond_work || !dpos)
-        return PAMNET_EINVAL;
-    if (n == 0) return PAMNET_OK;
-    hipStream_t st = as_stream(stream);
-    if (el > 0) {
-        hipLaunchKernelGGL(bond_grad_pbc_kernel, dim3(blocks_for(el * 64)), dim3(256), 0, st, pos, cell_table, node_graph, l_row,
-                           l_col, ddist_l, el, t_ptr, t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, bond_work);
-        PAMNET_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(pos_grad_pbc_kernel, dim3(blocks_for(n * 64)), dim3(256), 0, st, pos, cell_table, node_graph, n, g_ptr,
-                       g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, lt_ptr, lt_perm, bond_work, dpos);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
+    const PosBwdArgs a{pos, {cell_table, node_graph, nullptr}, n, {g_ptr, g_row, g_col}, {gt_ptr, gt_perm}, ddist_g, eg,
+                       {l_ptr, l_row, l_col}, {lt_ptr, lt_perm}, ddist_l, el,
+                       {t_ptr, t_row, t_col}, t_kind, {tt_ptr, tt_perm}, dangle, tp, bond_work, dpos};
+    return pos_bwd(a, SpaceKind::Periodic, false, stream);
 }
 
 extern "C" int pamnet_pos_bwd_pbc_virial_f32(const float* pos, const double* cell_table, const int32_t* node_graph, int64_t n,
@@ -405,59 +353,11 @@ extern "C" int pamnet_pos_bwd_pbc_virial_f32(const float* pos, const double* cel
                                              const int32_t* t_kind, const int32_t* tt_ptr, const int32_t* tt_perm,
                                              const float* dangle, int64_t tp, double* bond_work, float* dpos, const int32_t* gptr,
                                              int64_t n_graphs, double* atom_work, float* dstrain, pamnet_stream_t stream) {
-    if (n < 0 || eg < 0 || el < 0 || tp < 0 || n_graphs < 0) return PAMNET_EINVAL;
-    if (!pos || !cell_table || !node_graph || !g_ptr || !g_row || !g_col || !gt_ptr || !gt_perm || !ddist_g || !l_ptr ||
-        !l_row || !l_col || !lt_ptr || !lt_perm || !ddist_l || !t_ptr || !t_row || !t_col || !t_kind || !tt_ptr || !tt_perm ||
-        !dangle || !bond_work || !dpos || !gptr || !atom_work || !dstrain)
-        return PAMNET_EINVAL;
-    hipStream_t st = as_stream(stream);
-    if (n > 0) {
-        if (el > 0) {
-            hipLaunchKernelGGL(bond_grad_pbc_kernel, dim3(blocks_for(el * 64)), dim3(256), 0, st, pos, cell_table, node_graph,
-                               l_row, l_col, ddist_l, el, t_ptr, t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, bond_work);
-            PAMNET_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(pos_grad_pbc_virial_kernel, dim3(blocks_for(n * 64)), dim3(256), 0, st, pos, cell_table, node_graph, n,
-                           g_ptr, g_row, g_col, gt_ptr, gt_perm, ddist_g, l_ptr, l_col, lt_ptr, lt_perm, bond_work, dpos,
-                           atom_work);
-        PAMNET_LAUNCH_CHECK();
-    }
-    if (n_graphs > 0) {                               // (n == 0: every graph's atom range is empty, dstrain becomes zeros)
-        hipLaunchKernelGGL(virial_reduce_kernel, dim3((unsigned)n_graphs), dim3(256), 0, st, atom_work, gptr, n, dstrain);
-        PAMNET_LAUNCH_CHECK();
-    }
-    return PAMNET_OK;
-}
-
-// Both all-image entry points: atom_work == nullptr is the plain form (the caller has checked its own arguments).
-static int pos_bwd_img(const float* pos, const double* cell_table, const int32_t* node_graph, int64_t n, const int32_t* g_ptr,
-                       const int32_t* g_row, const int32_t* g_col, const int32_t* g_img, const int32_t* gt_ptr,
-                       const int32_t* gt_perm, const float* ddist_g, const int32_t* l_ptr, const int32_t* l_row,
-                       const int32_t* l_col, const int32_t* lt_ptr, const int32_t* lt_perm, const float* ddist_l, int64_t el,
-                       const int32_t* t_ptr, const int32_t* t_row, const int32_t* t_col, const int32_t* t_kind,
-                       const int32_t* tt_ptr, const int32_t* tt_perm, const float* dangle, double* bond_work, float* dpos,
-                       const int32_t* gptr, int64_t n_graphs, double* atom_work, float* dstrain, hipStream_t st) {
-    if (n > 0) {
-        if (el > 0) {
-            hipLaunchKernelGGL(bond_grad_pbc_kernel, dim3(blocks_for(el * 64)), dim3(256), 0, st, pos, cell_table, node_graph,
-                               l_row, l_col, ddist_l, el, t_ptr, t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, bond_work);
-            PAMNET_LAUNCH_CHECK();
-        }
-        if (atom_work)
-            hipLaunchKernelGGL((pos_grad_img_kernel<true>), dim3(blocks_for(n * 64)), dim3(256), 0, st, pos, cell_table, node_graph,
-                               n, g_ptr, g_row, g_col, g_img, gt_ptr, gt_perm, ddist_g, l_ptr, l_col, lt_ptr, lt_perm, bond_work,
-                               dpos, atom_work);
-        else
-            hipLaunchKernelGGL((pos_grad_img_kernel<false>), dim3(blocks_for(n * 64)), dim3(256), 0, st, pos, cell_table, node_graph,
-                               n, g_ptr, g_row, g_col, g_img, gt_ptr, gt_perm, ddist_g, l_ptr, l_col, lt_ptr, lt_perm, bond_work,
-                               dpos, (double*)nullptr);
-        PAMNET_LAUNCH_CHECK();
-    }
-    if (atom_work && n_graphs > 0) {
-        hipLaunchKernelGGL(virial_reduce_kernel, dim3((unsigned)n_graphs), dim3(256), 0, st, atom_work, gptr, n, dstrain);
-        PAMNET_LAUNCH_CHECK();
-    }
-    return PAMNET_OK;
+    const PosBwdArgs a{pos, {cell_table, node_graph, nullptr}, n, {g_ptr, g_row, g_col}, {gt_ptr, gt_perm}, ddist_g, eg,
+                       {l_ptr, l_row, l_col}, {lt_ptr, lt_perm}, ddist_l, el,
+                       {t_ptr, t_row, t_col}, t_kind, {tt_ptr, tt_perm}, dangle, tp, bond_work, dpos,
+                       gptr, n_graphs, atom_work, dstrain};
+    return pos_bwd(a, SpaceKind::Periodic, true, stream);
 }
 
 extern "C" int pamnet_pos_bwd_img_f32(const float* pos, const double* cell_table, const int32_t* node_graph, int64_t n,
@@ -468,14 +368,10 @@ extern "C" int pamnet_pos_bwd_img_f32(const float* pos, const double* cell_table
                                       const int32_t* t_row, const int32_t* t_col, const int32_t* t_kind, const int32_t* tt_ptr,
                                       const int32_t* tt_perm, const float* dangle, int64_t tp, double* bond_work, float* dpos,
                                       pamnet_stream_t stream) {
-    if (n < 0 || eg < 0 || el < 0 || tp < 0) return PAMNET_EINVAL;
-    if (!pos || !cell_table || !node_graph || !g_ptr || !g_row || !g_col || !g_img || !gt_ptr || !gt_perm || !ddist_g || !l_ptr ||
-        !l_row || !l_col || !lt_ptr || !lt_perm || !ddist_l || !t_ptr || !t_row || !t_col || !t_kind || !tt_ptr || !tt_perm ||
-        !dangle || !bond_work || !dpos)
-        return PAMNET_EINVAL;
-    return pos_bwd_img(pos, cell_table, node_graph, n, g_ptr, g_row, g_col, g_img, gt_ptr, gt_perm, ddist_g, l_ptr, l_row, l_col,
-                       lt_ptr, lt_perm, ddist_l, el, t_ptr, t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, bond_work, dpos, nullptr,
-                       0, nullptr, nullptr, as_stream(stream));
+    const PosBwdArgs a{pos, {cell_table, node_graph, g_img}, n, {g_ptr, g_row, g_col}, {gt_ptr, gt_perm}, ddist_g, eg,
+                       {l_ptr, l_row, l_col}, {lt_ptr, lt_perm}, ddist_l, el,
+                       {t_ptr, t_row, t_col}, t_kind, {tt_ptr, tt_perm}, dangle, tp, bond_work, dpos};
+    return pos_bwd(a, SpaceKind::Images, false, stream);
 }
 
 extern "C" int pamnet_pos_bwd_img_virial_f32(const float* pos, const double* cell_table, const int32_t* node_graph, int64_t n,
@@ -488,12 +384,9 @@ extern "C" int pamnet_pos_bwd_img_virial_f32(const float* pos, const double* cel
                                              const int32_t* tt_perm, const float* dangle, int64_t tp, double* bond_work, float* dpos,
                                              const int32_t* gptr, int64_t n_graphs, double* atom_work, float* dstrain,
                                              pamnet_stream_t stream) {
-    if (n < 0 || eg < 0 || el < 0 || tp < 0 || n_graphs < 0) return PAMNET_EINVAL;
-    if (!pos || !cell_table || !node_graph || !g_ptr || !g_row || !g_col || !g_img || !gt_ptr || !gt_perm || !ddist_g || !l_ptr ||
-        !l_row || !l_col || !lt_ptr || !lt_perm || !ddist_l || !t_ptr || !t_row || !t_col || !t_kind || !tt_ptr || !tt_perm ||
-        !dangle || !bond_work || !dpos || !gptr || !atom_work || !dstrain)
-        return PAMNET_EINVAL;
-    return pos_bwd_img(pos, cell_table, node_graph, n, g_ptr, g_row, g_col, g_img, gt_ptr, gt_perm, ddist_g, l_ptr, l_row, l_col,
-                       lt_ptr, lt_perm, ddist_l, el, t_ptr, t_row, t_col, t_kind, tt_ptr, tt_perm, dangle, bond_work, dpos, gptr,
-                       n_graphs, atom_work, dstrain, as_stream(stream));
+    const PosBwdArgs a{pos, {cell_table, node_graph, g_img}, n, {g_ptr, g_row, g_col}, {gt_ptr, gt_perm}, ddist_g, eg,
+                       {l_ptr, l_row, l_col}, {lt_ptr, lt_perm}, ddist_l, el,
+                       {t_ptr, t_row, t_col}, t_kind, {tt_ptr, tt_perm}, dangle, tp, bond_work, dpos,
+                       gptr, n_graphs, atom_work, dstrain};
+    return pos_bwd(a, SpaceKind::Images, true, stream);
 }

@@ -1,5 +1,7 @@
-// Edge lengths and angles of graph construction, shared by the step-by-step kernels (graph.hip) and the molecule-local
-// builder (graph_mol.hip) so that both produce the same floats.
+// The geometry every kernel shares: edge lengths and angles of graph construction (the step-by-step kernels of graph.hip and the
+// molecule-local builder of graph_mol.hip produce the same floats from them), the image rule of periodic cells, the policies
+// that choose between open space and a cell in the construction kernels and in the position backward (forces.hip), and the
+// cell's adjugate and heights.
 #pragma once
 #include "common.h"
 
@@ -99,10 +101,22 @@ __device__ __forceinline__ void nearest_image(const PbcCell& t, float ax, float 
 
 constexpr int IMG_BOX_MAX = 4;        // largest half-width of the candidate box per lattice direction (9^3 images per pair)
 
-// How a kernel of graph construction turns two atoms into a displacement: open space (the raw difference, the arithmetic
-// the kernels always had) or a periodic cell (the image rule, rounded once to fp32).  bind(): once per thread, for the graph
-// its atoms belong to.
+// The batch's space as a kernel argument carries it: pointers only, each null where the policy does not read it.
+struct Space {
+    const double* cells;          // [n_graphs, 18] cell table (periodic policies)
+    const int32_t* node_graph;    // [n] graph of every atom
+    const int32_t* img;           // [eg, 3] image of every global edge (ImageDiff)
+};
+
+// The geometry policies.  A kernel default-constructs its policy, attach()es the launch's Space and bind()s the graph its
+// atoms belong to, once per thread; bind() is where a periodic policy loads the graph's 18 doubles, so they never travel
+// as a kernel argument.  Two families on purpose: graph construction needs the fp32 LENGTH the reference computes (rounded
+// once from the image rule), the backward needs the fp64 VECTOR the derivative is taken along.
+
+// Graph construction: open space (the raw difference, the arithmetic the kernels always had) or a periodic cell (the image
+// rule, rounded once to fp32).
 struct OpenSpace {
+    __device__ __forceinline__ void attach(const Space&) {}
     __device__ __forceinline__ void bind(int) {}
     __device__ __forceinline__ float dist(const float* __restrict__ pos, int64_t a, int64_t b) const { return dist3(pos, a, b); }
     __device__ __forceinline__ float dist(float ax, float ay, float az, float bx, float by, float bz) const {
@@ -117,6 +131,7 @@ struct OpenSpace {
 struct Periodic {
     const double* __restrict__ table;
     PbcCell t;
+    __device__ __forceinline__ void attach(const Space& s) { table = s.cells; }
     __device__ __forceinline__ void bind(int g) { t = load_cell(table, g); }
     __device__ __forceinline__ float dist(const float* __restrict__ pos, int64_t a, int64_t b) const {
         const Disp d = min_image(t, pos, a, b);
@@ -132,3 +147,93 @@ struct Periodic {
         x = (float)d.x, y = (float)d.y, z = (float)d.z;
     }
 };
+
+// The backward (forces.hip): p_a - p_b in fp64 -- the exact difference in open space, or the minimum-image displacement of a
+// periodic cell: min_image, the function the forward's kernels chose the image with, not rounded to fp32 here.  The image
+// integers do not depend on the positions differentiably, so every derivative is the open-space one.
+struct V3 {
+    double x, y, z;
+};
+__device__ __forceinline__ V3 v3(double x, double y, double z) { return V3{x, y, z}; }
+__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
+__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
+__device__ __forceinline__ V3 operator*(double s, V3 a) { return v3(s * a.x, s * a.y, s * a.z); }
+__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+// every product rounded on its own (no fma contraction): for b = -a each component is then exactly 0, so |a x b| = 0
+// takes the exact-zero branch of angle_grads instead of a residue whose direction is noise
+__device__ __forceinline__ V3 cross(V3 a, V3 b) {
+    return v3(__dsub_rn(__dmul_rn(a.y, b.z), __dmul_rn(a.z, b.y)), __dsub_rn(__dmul_rn(a.z, b.x), __dmul_rn(a.x, b.z)),
+              __dsub_rn(__dmul_rn(a.x, b.y), __dmul_rn(a.y, b.x)));
+}
+__device__ __forceinline__ V3 load_pos(const float* __restrict__ pos, int64_t i) {
+    return v3((double)pos[3 * i], (double)pos[3 * i + 1], (double)pos[3 * i + 2]);
+}
+
+struct OpenDiff {
+    __device__ __forceinline__ void attach(const Space&) {}
+    __device__ __forceinline__ void bind(int) {}
+    __device__ __forceinline__ V3 diff(const float* __restrict__ pos, int64_t a, int64_t b) const {
+        return load_pos(pos, a) - load_pos(pos, b);
+    }
+    __device__ __forceinline__ V3 from(V3 pa, const float* __restrict__ pos, int64_t b) const { return pa - load_pos(pos, b); }
+    // global edge q seen from atom a: its row (towards the column b), its column (towards the row b)
+    __device__ __forceinline__ V3 row_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t) const { return from(pa, pos, b); }
+    __device__ __forceinline__ V3 col_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t) const { return from(pa, pos, b); }
+};
+struct PeriodicDiff {
+    const double* __restrict__ table;
+    PbcCell t;
+    __device__ __forceinline__ void attach(const Space& s) { table = s.cells; }
+    __device__ __forceinline__ void bind(int g) { t = load_cell(table, g); }
+    __device__ __forceinline__ V3 diff(const float* __restrict__ pos, int64_t a, int64_t b) const {
+        const Disp d = min_image(t, pos, a, b);
+        return v3(d.x, d.y, d.z);
+    }
+    // pa: an fp32 position held as doubles (load_pos)
+    __device__ __forceinline__ V3 from(V3 pa, const float* __restrict__ pos, int64_t b) const {
+        const Disp d = min_image(t, (float)pa.x, (float)pa.y, (float)pa.z, pos[3 * b], pos[3 * b + 1], pos[3 * b + 2]);
+        return v3(d.x, d.y, d.z);
+    }
+    __device__ __forceinline__ V3 row_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t) const { return from(pa, pos, b); }
+    __device__ __forceinline__ V3 col_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t) const { return from(pa, pos, b); }
+};
+// A periodic graph whose GLOBAL list holds every image within the cutoff (pamnet_radius_img_fill_i32): global edge q is the vector
+// v_q = p_row - p_col - img[q] @ cell of its stored image, not a rounded one (image_disp).  Seen from its column the edge is
+// -v_q.  Local edges, and so diff / from, stay minimum-image.
+struct ImageDiff : PeriodicDiff {
+    const int32_t* __restrict__ img;
+    __device__ __forceinline__ void attach(const Space& s) { table = s.cells, img = s.img; }
+    __device__ __forceinline__ V3 row_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t q) const {
+        const Disp d = image_disp(t, (float)pa.x, (float)pa.y, (float)pa.z, pos[3 * b], pos[3 * b + 1], pos[3 * b + 2], img, q);
+        return v3(d.x, d.y, d.z);
+    }
+    __device__ __forceinline__ V3 col_edge(V3 pa, const float* __restrict__ pos, int64_t b, int64_t q) const {
+        const Disp d = image_disp(t, pos[3 * b], pos[3 * b + 1], pos[3 * b + 2], (float)pa.x, (float)pa.y, (float)pa.z, img, q);
+        return v3(-d.x, -d.y, -d.z);
+    }
+};
+
+// ---- the cell's perpendicular heights ------------------------------------------------------------------------------------
+// x[k] = a_{k+1} x a_{k+2}: column k of the adjugate of the cell a (row k = lattice vector a_k); returns det = a_0 . x[0].
+__device__ __forceinline__ double cell_adjugate(const double* a, double (&x)[3][3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double* u = a + 3 * ((k + 1) % 3);
+        const double* v = a + 3 * ((k + 2) % 3);
+        x[k][0] = u[1] * v[2] - u[2] * v[1];
+        x[k][1] = u[2] * v[0] - u[0] * v[2];
+        x[k][2] = u[0] * v[1] - u[1] * v[0];
+    }
+    const double det = a[0] * x[0][0] + a[1] * x[0][1] + a[2] * x[0][2];
+    return det;
+}
+
+// h_k = |det| / |a_{k+1} x a_{k+2}|: the cell's extent perpendicular to the faces that lattice direction k crosses.  The
+// one height rule: the cell table judges h_k > 2 * cutoff with it, the image box takes N_k = ceil(cutoff / h_k) from it.
+__device__ __forceinline__ double cell_height(const double (&x)[3][3], double det, int k) {
+    const double area = sqrt(x[k][0] * x[k][0] + x[k][1] * x[k][1] + x[k][2] * x[k][2]);
+    return fabs(det) / area;
+}
+
+// workgroups of 256 threads for n items, `per` items a workgroup (a wavefront per item: per = 4); never an empty grid
+inline unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)(n > 0 ? ceil_div(n, per) : 1); }

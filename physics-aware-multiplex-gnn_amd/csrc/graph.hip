@@ -377,8 +377,31 @@ __global__ __launch_bounds__(SMALL_THREADS) void csr_small_kernel(const int32_t*
 // reference tree -- parity unpinned, as SURVEY 8c records for every third-party boundary.)
 constexpr int CAP_BIT = 64;
 
+// The operands of a radius search, as its kernels take them (by value) and its entry points fill them.
+struct CsrFill {                  // the fill pass's list; all null / 0 in the count pass
+    const int32_t* ptr;           // [n + 1] the scanned counts
+    int32_t* nbr;
+    float* dist;
+    int32_t* row_of;              // nullable
+    int32_t* img;                 // [cap, 3], the all-image search only
+    int64_t cap;                  // see pamnet_radius_fill_i32
+};
+struct RadiusArgs {
+    const float* pos;
+    Space space;                  // cells: null in open space; img: unused (the fill pass WRITES images: out.img)
+    const int32_t* img_box;       // [n_graphs, 3] pamnet_cell_images_i32, the all-image search only
+    const int32_t* gptr;
+    int64_t n, n_graphs;
+    float r;
+    int64_t max_nb;
+    int32_t* count;               // count pass: [n]
+    int32_t* cap_flag;            // count pass, nullable
+    CsrFill out;
+};
+
 // GEOM (geom_core.h): OpenSpace = the raw difference of two positions; Periodic = their minimum-image displacement.  One
-// statement of the search for both: the kernels below only choose the policy.
+// statement of the search for both.  The search bodies take the record's members as __restrict__ parameters (a struct
+// member carries no such promise), the kernels below hand them over.
 template <bool FILL, class GEOM>
 __device__ __forceinline__ void radius_search(GEOM geom, const float* __restrict__ pos,
                                               const int32_t* __restrict__ node_graph,
@@ -416,28 +439,12 @@ __device__ __forceinline__ void radius_search(GEOM geom, const float* __restrict
     if (!FILL) count[i] = c;
 }
 
-template <bool FILL>
-__global__ __launch_bounds__(256) void radius_kernel(const float* __restrict__ pos,
-                                                     const int32_t* __restrict__ node_graph,
-                                                     const int32_t* __restrict__ gptr, int64_t n, float r,
-                                                     int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
-                                                     int32_t* __restrict__ nbr, float* __restrict__ dist, int64_t cap,
-                                                     int32_t* __restrict__ row_of, int max_nb,
-                                                     int32_t* __restrict__ cap_flag) {
-    radius_search<FILL>(OpenSpace{}, pos, node_graph, gptr, n, r, count, ptr, nbr, dist, cap, row_of, max_nb, cap_flag);
-}
-
-template <bool FILL>
-__global__ __launch_bounds__(256) void radius_pbc_kernel(const float* __restrict__ pos, const double* __restrict__ cells,
-                                                         const int32_t* __restrict__ node_graph,
-                                                         const int32_t* __restrict__ gptr, int64_t n, float r,
-                                                         int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
-                                                         int32_t* __restrict__ nbr, float* __restrict__ dist, int64_t cap,
-                                                         int32_t* __restrict__ row_of, int max_nb,
-                                                         int32_t* __restrict__ cap_flag) {
-    Periodic geom;
-    geom.table = cells;
-    radius_search<FILL>(geom, pos, node_graph, gptr, n, r, count, ptr, nbr, dist, cap, row_of, max_nb, cap_flag);
+template <bool FILL, class GEOM>
+__global__ __launch_bounds__(256) void radius_kernel(RadiusArgs a) {
+    GEOM geom;
+    geom.attach(a.space);
+    radius_search<FILL>(geom, a.pos, a.space.node_graph, a.gptr, a.n, a.r, a.count, a.out.ptr, a.out.nbr, a.out.dist, a.out.cap,
+                        a.out.row_of, (int)a.max_nb, a.cap_flag);
 }
 
 // The same search with one WAVEFRONT per node, for graphs of hundreds of nodes (PDBbind complexes: ~600 atoms): the lanes
@@ -493,29 +500,12 @@ __device__ __forceinline__ void radius_wave_search(GEOM geom, const float* __res
     if (!FILL && lane == 0) count[i] = c;
 }
 
-template <bool FILL>
-__global__ __launch_bounds__(256) void radius_wave_kernel(const float* __restrict__ pos,
-                                                          const int32_t* __restrict__ node_graph,
-                                                          const int32_t* __restrict__ gptr, int64_t n, float r,
-                                                          int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
-                                                          int32_t* __restrict__ nbr, float* __restrict__ dist,
-                                                          int64_t cap, int32_t* __restrict__ row_of, int max_nb,
-                                                          int32_t* __restrict__ cap_flag) {
-    radius_wave_search<FILL>(OpenSpace{}, pos, node_graph, gptr, n, r, count, ptr, nbr, dist, cap, row_of, max_nb, cap_flag);
-}
-
-template <bool FILL>
-__global__ __launch_bounds__(256) void radius_wave_pbc_kernel(const float* __restrict__ pos,
-                                                              const double* __restrict__ cells,
-                                                              const int32_t* __restrict__ node_graph,
-                                                              const int32_t* __restrict__ gptr, int64_t n, float r,
-                                                              int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
-                                                              int32_t* __restrict__ nbr, float* __restrict__ dist,
-                                                              int64_t cap, int32_t* __restrict__ row_of, int max_nb,
-                                                              int32_t* __restrict__ cap_flag) {
-    Periodic geom;
-    geom.table = cells;
-    radius_wave_search<FILL>(geom, pos, node_graph, gptr, n, r, count, ptr, nbr, dist, cap, row_of, max_nb, cap_flag);
+template <bool FILL, class GEOM>
+__global__ __launch_bounds__(256) void radius_wave_kernel(RadiusArgs a) {
+    GEOM geom;
+    geom.attach(a.space);
+    radius_wave_search<FILL>(geom, a.pos, a.space.node_graph, a.gptr, a.n, a.r, a.count, a.out.ptr, a.out.nbr, a.out.dist,
+                             a.out.cap, a.out.row_of, (int)a.max_nb, a.cap_flag);
 }
 
 // ---- the radius search over ALL images of a periodic cell (the global graph of cells below twice the cutoff) ---------------
@@ -528,16 +518,16 @@ __global__ __launch_bounds__(256) void radius_wave_pbc_kernel(const float* __res
 // mixed radix: no division by M inside the loop.  The length is Periodic::dist's arithmetic on the given image: image_disp rounded
 // once to fp32, then dist3_xyz against the origin; (i, j, n) and (j, i, -n) carry bitwise equal lengths.
 // No row is cut: a multigraph with a cut row is not symmetric.  max_nb > 0 only raises CAP_BIT (count pass) for a row whose hits,
-// the query itself counted as in the twins, exceed it.
+// the query itself counted as in the other searches, exceed it.
 template <bool FILL>
-__global__ __launch_bounds__(256) void radius_img_kernel(const float* __restrict__ pos, const double* __restrict__ cells,
-                                                         const int32_t* __restrict__ img_box,
-                                                         const int32_t* __restrict__ node_graph,
-                                                         const int32_t* __restrict__ gptr, int64_t n, float r,
-                                                         int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
-                                                         int32_t* __restrict__ nbr, float* __restrict__ dist, int64_t cap,
-                                                         int32_t* __restrict__ row_of, int32_t* __restrict__ img, int max_nb,
-                                                         int32_t* __restrict__ cap_flag) {
+__device__ __forceinline__ void radius_img_search(const float* __restrict__ pos, const double* __restrict__ cells,
+                                                  const int32_t* __restrict__ img_box,
+                                                  const int32_t* __restrict__ node_graph,
+                                                  const int32_t* __restrict__ gptr, int64_t n, float r,
+                                                  int32_t* __restrict__ count, const int32_t* __restrict__ ptr,
+                                                  int32_t* __restrict__ nbr, float* __restrict__ dist, int64_t cap,
+                                                  int32_t* __restrict__ row_of, int32_t* __restrict__ img, int max_nb,
+                                                  int32_t* __restrict__ cap_flag) {
     const int lane = threadIdx.x & 63;
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (i >= n) return;                                           // (uniform over the wavefront)
@@ -588,8 +578,46 @@ __global__ __launch_bounds__(256) void radius_img_kernel(const float* __restrict
     }
 }
 
+template <bool FILL>
+__global__ __launch_bounds__(256) void radius_img_kernel(RadiusArgs a) {
+    radius_img_search<FILL>(a.pos, a.space.cells, a.img_box, a.space.node_graph, a.gptr, a.n, a.r, a.count, a.out.ptr, a.out.nbr,
+                            a.out.dist, a.out.cap, a.out.row_of, a.out.img, (int)a.max_nb, a.cap_flag);
+}
+
 // graphs this large on average take the wavefront-per-node form (QM9 molecules: ~18 atoms -> one thread per node)
 constexpr int64_t RADIUS_WAVE_MIN_NODES = 96;
+
+struct AllImages {};              // radius_launch's third space: radius_img_kernel, which walks its own candidates
+
+// Sizes first; no nodes: nothing is read; then the pointers the policy and the pass read.
+template <class GEOM>
+int radius_check(const RadiusArgs& a, bool fill) {
+    constexpr bool open = std::is_same<GEOM, OpenSpace>::value, images = std::is_same<GEOM, AllImages>::value;
+    if (a.n < 0 || (fill && a.out.cap < 0) || a.n_graphs < 0 || a.max_nb < 0 || a.max_nb > 0x7fffffff) return PAMNET_EINVAL;
+    if (a.n == 0) return PAMNET_OK;
+    if (!a.pos || (!open && !a.space.cells) || (images && !a.img_box) || !a.space.node_graph || !a.gptr) return PAMNET_ENULL;
+    if (fill ? (!a.out.ptr || !a.out.nbr || !a.out.dist || (images && !a.out.img)) : !a.count) return PAMNET_ENULL;
+    return PAMNET_OK;
+}
+
+// Either pass of a radius search in GEOM: a wavefront per node for large graphs (always, over all images), else a thread.
+template <class GEOM>
+int radius_launch(const RadiusArgs& a, bool fill, pamnet_stream_t stream) {
+    const int rc = radius_check<GEOM>(a, fill);
+    if (rc != PAMNET_OK || a.n == 0) return rc;
+    void (*kernel)(RadiusArgs);
+    bool wave = true;
+    if constexpr (std::is_same<GEOM, AllImages>::value) {
+        kernel = fill ? radius_img_kernel<true> : radius_img_kernel<false>;
+    } else {
+        wave = a.n_graphs > 0 && a.n >= RADIUS_WAVE_MIN_NODES * a.n_graphs;
+        kernel = wave ? (fill ? radius_wave_kernel<true, GEOM> : radius_wave_kernel<false, GEOM>)
+                      : (fill ? radius_kernel<true, GEOM> : radius_kernel<false, GEOM>);
+    }
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(a.n, wave ? 4 : 256)), dim3(256), 0, as_stream(stream), a);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
 
 __device__ __forceinline__ bool pair_less(float da, int ja, float db, int jb) {
     return (da < db) || (da == db && ja < jb);
@@ -1083,112 +1111,48 @@ __device__ __forceinline__ void triplet_fill(GEOM geom, const int32_t* __restric
     }
 }
 
-__global__ __launch_bounds__(256) void triplet_fill_kernel(const float* __restrict__ pos,
-                                                           const int32_t* __restrict__ lptr,
-                                                           const int32_t* __restrict__ src,
-                                                           const int32_t* __restrict__ dst, int64_t n_edges,
-                                                           int with_triplets, const int32_t* __restrict__ tp_ptr,
-                                                           int32_t* __restrict__ tp_idx, int32_t* __restrict__ tp_edge,
-                                                           float* __restrict__ tp_angle, int32_t* __restrict__ tp_kind,
-                                                           int64_t cap) {
-    triplet_fill(OpenSpace{}, nullptr, pos, lptr, src, dst, n_edges, with_triplets, tp_ptr, tp_idx, tp_edge, tp_angle, tp_kind,
-                 cap);
+struct TripletArgs {
+    const float* pos;
+    Space space;                  // cells, node_graph: null in open space
+    const int32_t *lptr, *src, *dst;
+    int64_t n_edges;
+    int with_triplets;
+    const int32_t* tp_ptr;
+    int32_t *tp_idx, *tp_edge;
+    float* tp_angle;
+    int32_t* tp_kind;
+    int64_t cap;
+};
+
+template <class GEOM>
+__global__ __launch_bounds__(256) void triplet_fill_kernel(TripletArgs a) {
+    GEOM geom;
+    geom.attach(a.space);
+    triplet_fill(geom, a.space.node_graph, a.pos, a.lptr, a.src, a.dst, a.n_edges, a.with_triplets, a.tp_ptr, a.tp_idx, a.tp_edge,
+                 a.tp_angle, a.tp_kind, a.cap);
 }
 
-__global__ __launch_bounds__(256) void triplet_fill_pbc_kernel(const float* __restrict__ pos, const double* __restrict__ cells,
-                                                               const int32_t* __restrict__ node_graph,
-                                                               const int32_t* __restrict__ lptr,
-                                                               const int32_t* __restrict__ src,
-                                                               const int32_t* __restrict__ dst, int64_t n_edges,
-                                                               int with_triplets, const int32_t* __restrict__ tp_ptr,
-                                                               int32_t* __restrict__ tp_idx, int32_t* __restrict__ tp_edge,
-                                                               float* __restrict__ tp_angle, int32_t* __restrict__ tp_kind,
-                                                               int64_t cap) {
-    Periodic geom;
-    geom.table = cells;
-    triplet_fill(geom, node_graph, pos, lptr, src, dst, n_edges, with_triplets, tp_ptr, tp_idx, tp_edge, tp_angle, tp_kind, cap);
+template <class GEOM>
+int triplet_fill_launch(const TripletArgs& a, pamnet_stream_t stream) {
+    constexpr bool open = std::is_same<GEOM, OpenSpace>::value;
+    if (a.n_edges < 0 || a.cap < 0) return PAMNET_EINVAL;
+    if (a.n_edges == 0) return PAMNET_OK;
+    if (!a.pos || (!open && (!a.space.cells || !a.space.node_graph)) || !a.lptr || !a.src || !a.dst || !a.tp_ptr || !a.tp_idx ||
+        !a.tp_edge || !a.tp_angle || !a.tp_kind)
+        return PAMNET_ENULL;
+    hipLaunchKernelGGL(triplet_fill_kernel<GEOM>, dim3(blocks_for(a.n_edges)), dim3(256), 0, as_stream(stream), a);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
 }
 
-// One thread per graph: the cell (row k = lattice vector a_k) and its inverse by adjugate, in fp64, into the graph's row of
-// the table; PBC_BIT when the cell is singular, not finite, or one of its perpendicular heights |det| / |a_i x a_j| does not
-// exceed 2 * cutoff (a pair could then have two images within the cutoff).  A singular cell gets a zero inverse (image 0:
-// the open-space distances), so that whatever runs before the host reads the flag stays finite.
-__global__ __launch_bounds__(256) void cell_prepare_kernel(const float* __restrict__ cell, int64_t n_graphs, double cutoff,
-                                                           double* __restrict__ table, int32_t* __restrict__ flag) {
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_graphs) return;
-    double a[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) a[k] = (double)cell[9 * g + k];
-    // x[k] = a_{k+1} x a_{k+2}: column k of the adjugate; det = a_0 . x[0]
-    double x[3][3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double* u = a + 3 * ((k + 1) % 3);
-        const double* v = a + 3 * ((k + 2) % 3);
-        x[k][0] = u[1] * v[2] - u[2] * v[1];
-        x[k][1] = u[2] * v[0] - u[0] * v[2];
-        x[k][2] = u[0] * v[1] - u[1] * v[0];
-    }
-    const double det = a[0] * x[0][0] + a[1] * x[0][1] + a[2] * x[0][2];
-    bool ok = isfinite(det) && det != 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double area = sqrt(x[k][0] * x[k][0] + x[k][1] * x[k][1] + x[k][2] * x[k][2]);
-        ok = ok && (fabs(det) / area > 2.0 * cutoff);         // (NaN compares false)
-    }
-    const bool invertible = isfinite(det) && det != 0.0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) table[PBC_ROW * g + k] = a[k];
-#pragma unroll
-    for (int m = 0; m < 3; ++m)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) table[PBC_ROW * g + 9 + 3 * m + k] = invertible ? x[k][m] / det : 0.0;
-    if (!ok) atomicOr(flag, PBC_BIT);
-}
-
-// One thread per graph: the half-widths of the all-image search's candidate box, N_k = ceil(cutoff / h_k) with h_k = |det| /
-// |a_{k+1} x a_{k+2}| the perpendicular height along lattice direction k, in fp64 from the table's cell.  An image within the
-// cutoff has |f_k - n_k| <= cutoff / h_k for the fractional displacement f, so |rint(f_k) - n_k| <= floor(cutoff / h_k + 1/2) <=
-// N_k: the box holds every image the search must find.  A cell that needs N_k > IMG_BOX_MAX (or has no heights at all) raises
-// PBC_BIT and gets an empty box, so whatever runs before the host reads the flag stays short.
-__global__ __launch_bounds__(256) void cell_images_kernel(const double* __restrict__ table, int64_t n_graphs, double cutoff,
-                                                          int32_t* __restrict__ img_box, int32_t* __restrict__ flag) {
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_graphs) return;
-    const double* a = table + PBC_ROW * g;
-    double x[3][3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double* u = a + 3 * ((k + 1) % 3);
-        const double* v = a + 3 * ((k + 2) % 3);
-        x[k][0] = u[1] * v[2] - u[2] * v[1];
-        x[k][1] = u[2] * v[0] - u[0] * v[2];
-        x[k][2] = u[0] * v[1] - u[1] * v[0];
-    }
-    const double det = a[0] * x[0][0] + a[1] * x[0][1] + a[2] * x[0][2];
-    int N[3];
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double area = sqrt(x[k][0] * x[k][0] + x[k][1] * x[k][1] + x[k][2] * x[k][2]);
-        const double need = ceil(cutoff / (fabs(det) / area));
-        ok = ok && (need <= (double)IMG_BOX_MAX);             // (NaN compares false)
-        N[k] = ok ? (int)need : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) img_box[3 * g + k] = ok ? N[k] : 0;
-    if (!ok) atomicOr(flag, PBC_BIT);
-}
-
-// ---- per-axis periodicity: the same table for slabs, wires and isolated molecules --------------------------------------------
-// pbc [n_graphs, 3] bytes: graph g repeats along its lattice vector k when pbc[3 g + k] is not zero.  The user's vector along
-// an open axis is not read beyond the load: the cell is COMPLETED with unit vectors orthogonal to the periodic ones, the inverse
-// of the completed cell is formed by cell_prepare_kernel's statements, and the three inverse entries that make fractional
-// component k of an open axis k are overwritten with +0.0 -- so min_image / nearest_image round that component to 0 for every
-// pair and no kernel that reads the table ever wraps along k.  Because the completed vectors are orthogonal to the periodic
-// ones, the remaining columns of the inverse are the reciprocal vectors of the periodic lattice inside its own span: an
-// out-of-plane displacement has no share in the in-plane image.  (A skewed user vector would have one.)
+// ---- the cell table, for crystals, slabs, wires and isolated molecules -----------------------------------------------------
+// pbc [n_graphs, 3] bytes: graph g repeats along its lattice vector k when pbc[3 g + k] is not zero; a null pbc is three
+// periodic axes for every graph.  The user's vector along an open axis is not read beyond the load: the cell is COMPLETED with
+// unit vectors orthogonal to the periodic ones, the completed cell is inverted by adjugate, and the three inverse entries that
+// make fractional component k of an open axis k are written as +0.0 -- so min_image / nearest_image round that component to 0
+// for every pair and no kernel that reads the table ever wraps along k.  Because the completed vectors are orthogonal to the
+// periodic ones, the remaining columns of the inverse are the reciprocal vectors of the periodic lattice inside its own span:
+// an out-of-plane displacement has no share in the in-plane image.  (A skewed user vector would have one.)
 __device__ __forceinline__ void cross3(const double* u, const double* v, double* w) {
     w[0] = u[1] * v[2] - u[2] * v[1];
     w[1] = u[2] * v[0] - u[0] * v[2];
@@ -1203,15 +1167,17 @@ __device__ __forceinline__ bool unit3(const double* w, double* out) {
     return true;
 }
 
-// One thread per graph.  Completion: three periodic axes -- the cell as given; two (i, j; k open) -- a_k' = a_i x a_j
-// normalised; one (i) -- a_j' = a_i x e normalised, e the coordinate unit vector along a_i's component of smallest magnitude
-// (lowest index on ties), a_k' = a_i x a_j' normalised; none -- the identity.  A completion that fails (parallel or zero
-// periodic vectors) leaves coordinate unit vectors on the open axes, a zero inverse and PBC_BIT.  From there on the statements
-// are cell_prepare_kernel's, with the height test on periodic axes only: a row of three set flags gets that kernel's 18 doubles
-// and verdict bit for bit.
-__global__ __launch_bounds__(256) void cell_prepare_axes_kernel(const float* __restrict__ cell, const uint8_t* __restrict__ pbc,
-                                                                int64_t n_graphs, double cutoff, double* __restrict__ table,
-                                                                int32_t* __restrict__ flag) {
+// One thread per graph: the completed cell (row k = lattice vector a_k) and its inverse, in fp64, into the graph's row of the
+// table.  Completion: three periodic axes -- the cell as given; two (i, j; k open) -- a_k' = a_i x a_j normalised; one (i) --
+// a_j' = a_i x e normalised, e the coordinate unit vector along a_i's component of smallest magnitude (lowest index on ties),
+// a_k' = a_i x a_j' normalised; none -- the identity.  A completion that fails (parallel or zero periodic vectors) leaves
+// coordinate unit vectors on the open axes.  PBC_BIT when the completion fails, the cell is singular or not finite, or the
+// height (geom_core.h cell_height) along a periodic axis does not exceed 2 * cutoff (a pair could then have two images within
+// the cutoff).  Such a cell, if not invertible, gets a zero inverse (image 0: the open-space distances), so that whatever runs
+// before the host reads the flag stays finite.
+__global__ __launch_bounds__(256) void cell_prepare_kernel(const float* __restrict__ cell, const uint8_t* __restrict__ pbc,
+                                                           int64_t n_graphs, double cutoff, double* __restrict__ table,
+                                                           int32_t* __restrict__ flag) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_graphs) return;
     double a[9];
@@ -1219,7 +1185,7 @@ __global__ __launch_bounds__(256) void cell_prepare_axes_kernel(const float* __r
     for (int k = 0; k < 9; ++k) a[k] = (double)cell[9 * g + k];
     bool per[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) per[k] = pbc[3 * g + k] != 0;
+    for (int k = 0; k < 3; ++k) per[k] = !pbc || pbc[3 * g + k] != 0;
     const int n_per = (int)per[0] + (int)per[1] + (int)per[2];
     bool complete = true;
 #pragma unroll
@@ -1250,23 +1216,12 @@ __global__ __launch_bounds__(256) void cell_prepare_axes_kernel(const float* __r
             }
         }
     }
-    // x[k] = a_{k+1} x a_{k+2}: column k of the adjugate; det = a_0 . x[0]  (cell_prepare_kernel's statements from here on)
     double x[3][3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double* u = a + 3 * ((k + 1) % 3);
-        const double* v = a + 3 * ((k + 2) % 3);
-        x[k][0] = u[1] * v[2] - u[2] * v[1];
-        x[k][1] = u[2] * v[0] - u[0] * v[2];
-        x[k][2] = u[0] * v[1] - u[1] * v[0];
-    }
-    const double det = a[0] * x[0][0] + a[1] * x[0][1] + a[2] * x[0][2];
+    const double det = cell_adjugate(a, x);
     bool ok = complete && isfinite(det) && det != 0.0;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double area = sqrt(x[k][0] * x[k][0] + x[k][1] * x[k][1] + x[k][2] * x[k][2]);
-        ok = ok && (!per[k] || fabs(det) / area > 2.0 * cutoff);  // (NaN compares false; an open axis has no condition)
-    }
+    for (int k = 0; k < 3; ++k)
+        ok = ok && (!per[k] || cell_height(x, det, k) > 2.0 * cutoff);      // (NaN compares false; an open axis has no condition)
     const bool invertible = complete && isfinite(det) && det != 0.0;
 #pragma unroll
     for (int k = 0; k < 9; ++k) table[PBC_ROW * g + k] = a[k];
@@ -1277,32 +1232,26 @@ __global__ __launch_bounds__(256) void cell_prepare_axes_kernel(const float* __r
     if (!ok) atomicOr(flag, PBC_BIT);
 }
 
-// cell_images_kernel on a table completed by cell_prepare_axes_kernel: N_k = 0 along an open axis (the search tries no image
-// there) and no verdict on it.
-__global__ __launch_bounds__(256) void cell_images_axes_kernel(const double* __restrict__ table, const uint8_t* __restrict__ pbc,
-                                                               int64_t n_graphs, double cutoff, int32_t* __restrict__ img_box,
-                                                               int32_t* __restrict__ flag) {
+// One thread per graph: the half-widths of the all-image search's candidate box, N_k = ceil(cutoff / h_k) with h_k the height
+// along lattice direction k, in fp64 from the table's (completed) cell; N_k = 0 along an open axis of pbc (null: none is open) --
+// the search tries no image there -- and no verdict on it.  An image within the cutoff has |f_k - n_k| <= cutoff / h_k for the
+// fractional displacement f, so |rint(f_k) - n_k| <= floor(cutoff / h_k + 1/2) <= N_k: the box holds every image the search
+// must find.  A cell that needs N_k > IMG_BOX_MAX (or has no heights at all) raises PBC_BIT and gets an empty box, so whatever
+// runs before the host reads the flag stays short.
+__global__ __launch_bounds__(256) void cell_images_kernel(const double* __restrict__ table, const uint8_t* __restrict__ pbc,
+                                                          int64_t n_graphs, double cutoff, int32_t* __restrict__ img_box,
+                                                          int32_t* __restrict__ flag) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_graphs) return;
-    const double* a = table + PBC_ROW * g;
     double x[3][3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double* u = a + 3 * ((k + 1) % 3);
-        const double* v = a + 3 * ((k + 2) % 3);
-        x[k][0] = u[1] * v[2] - u[2] * v[1];
-        x[k][1] = u[2] * v[0] - u[0] * v[2];
-        x[k][2] = u[0] * v[1] - u[1] * v[0];
-    }
-    const double det = a[0] * x[0][0] + a[1] * x[0][1] + a[2] * x[0][2];
+    const double det = cell_adjugate(table + PBC_ROW * g, x);
     int N[3];
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         N[k] = 0;
-        if (pbc[3 * g + k] != 0) {
-            const double area = sqrt(x[k][0] * x[k][0] + x[k][1] * x[k][1] + x[k][2] * x[k][2]);
-            const double need = ceil(cutoff / (fabs(det) / area));
+        if (!pbc || pbc[3 * g + k] != 0) {
+            const double need = ceil(cutoff / cell_height(x, det, k));
             ok = ok && (need <= (double)IMG_BOX_MAX);             // (NaN compares false)
             N[k] = ok ? (int)need : 0;
         }
@@ -1410,7 +1359,6 @@ __global__ __launch_bounds__(256) void triplet_transpose_kernel(const int32_t* _
     }
 }
 
-inline unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)(n > 0 ? ceil_div(n, per) : 1); }
 // PAMNET_SMALL_FORMS=0: always the multi-launch scan / counting sort (the tests compare the two)
 inline bool small_forms() {
     static bool v = [] { const char* e = getenv("PAMNET_SMALL_FORMS"); return !e || atoi(e) != 0; }();
@@ -1543,149 +1491,95 @@ extern "C" int pamnet_expand_rows_i32(const int32_t* ptr, int64_t rows, int32_t*
     return PAMNET_OK;
 }
 
+// The six radius entry points fill a RadiusArgs and name the space; radius_launch checks and launches.
 extern "C" int pamnet_radius_count_i32(const float* pos, const int32_t* node_graph, const int32_t* gptr, int64_t n,
                                        int64_t n_graphs, float r, int64_t max_neighbors, int32_t* count,
                                        int32_t* cap_flag, pamnet_stream_t stream) {
-    if (n < 0 || n_graphs < 0 || max_neighbors < 0 || max_neighbors > 0x7fffffff) return PAMNET_EINVAL;
-    if (n == 0) return PAMNET_OK;
-    if (!pos || !node_graph || !gptr || !count) return PAMNET_ENULL;
-    const int mx = (int)max_neighbors;
-    if (n_graphs > 0 && n >= RADIUS_WAVE_MIN_NODES * n_graphs)
-        hipLaunchKernelGGL((radius_wave_kernel<false>), dim3(blocks_for(n, 4)), dim3(256), 0, as_stream(stream), pos,
-                           node_graph, gptr, n, r, count, (const int32_t*)nullptr, (int32_t*)nullptr, (float*)nullptr,
-                           (int64_t)0, (int32_t*)nullptr, mx, cap_flag);
-    else
-        hipLaunchKernelGGL((radius_kernel<false>), dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), pos, node_graph,
-                           gptr, n, r, count, (const int32_t*)nullptr, (int32_t*)nullptr, (float*)nullptr, (int64_t)0,
-                           (int32_t*)nullptr, mx, cap_flag);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
+    const RadiusArgs a{pos, {nullptr, node_graph, nullptr}, nullptr, gptr, n, n_graphs, r, max_neighbors, count, cap_flag, {}};
+    return radius_launch<OpenSpace>(a, false, stream);
 }
 
 extern "C" int pamnet_radius_fill_i32(const float* pos, const int32_t* node_graph, const int32_t* gptr, int64_t n,
                                       int64_t n_graphs, float r, int64_t max_neighbors, const int32_t* ptr, int32_t* nbr,
                                       float* dist, int32_t* row_of, int64_t cap, pamnet_stream_t stream) {
-    if (n < 0 || cap < 0 || n_graphs < 0 || max_neighbors < 0 || max_neighbors > 0x7fffffff) return PAMNET_EINVAL;
-    if (n == 0) return PAMNET_OK;
-    if (!pos || !node_graph || !gptr || !ptr || !nbr || !dist) return PAMNET_ENULL;
-    const int mx = (int)max_neighbors;
-    if (n_graphs > 0 && n >= RADIUS_WAVE_MIN_NODES * n_graphs)
-        hipLaunchKernelGGL((radius_wave_kernel<true>), dim3(blocks_for(n, 4)), dim3(256), 0, as_stream(stream), pos,
-                           node_graph, gptr, n, r, (int32_t*)nullptr, ptr, nbr, dist, cap, row_of, mx, (int32_t*)nullptr);
-    else
-        hipLaunchKernelGGL((radius_kernel<true>), dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), pos, node_graph,
-                           gptr, n, r, (int32_t*)nullptr, ptr, nbr, dist, cap, row_of, mx, (int32_t*)nullptr);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
-}
-
-extern "C" int pamnet_cell_prepare_f64(const float* cell, int64_t n_graphs, float cutoff, double* table, int32_t* flag,
-                                       pamnet_stream_t stream) {
-    if (n_graphs < 0 || !(cutoff > 0.f) || !(cutoff <= 3.0e38f)) return PAMNET_EINVAL;      // (NaN and inf refused)
-    if (n_graphs == 0) return PAMNET_OK;
-    if (!cell || !table || !flag) return PAMNET_ENULL;
-    hipLaunchKernelGGL(cell_prepare_kernel, dim3(blocks_for(n_graphs)), dim3(256), 0, as_stream(stream), cell, n_graphs,
-                       (double)cutoff, table, flag);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
-}
-
-extern "C" int pamnet_cell_prepare_axes_f64(const float* cell, const uint8_t* pbc, int64_t n_graphs, float cutoff, double* table,
-                                            int32_t* flag, pamnet_stream_t stream) {
-    if (n_graphs < 0 || !(cutoff > 0.f) || !(cutoff <= 3.0e38f)) return PAMNET_EINVAL;      // (NaN and inf refused)
-    if (n_graphs == 0) return PAMNET_OK;
-    if (!cell || !pbc || !table || !flag) return PAMNET_ENULL;
-    hipLaunchKernelGGL(cell_prepare_axes_kernel, dim3(blocks_for(n_graphs)), dim3(256), 0, as_stream(stream), cell, pbc,
-                       n_graphs, (double)cutoff, table, flag);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
+    const RadiusArgs a{pos, {nullptr, node_graph, nullptr}, nullptr, gptr, n, n_graphs, r, max_neighbors, nullptr, nullptr,
+                       {ptr, nbr, dist, row_of, nullptr, cap}};
+    return radius_launch<OpenSpace>(a, true, stream);
 }
 
 extern "C" int pamnet_radius_pbc_count_i32(const float* pos, const double* cell_table, const int32_t* node_graph,
                                            const int32_t* gptr, int64_t n, int64_t n_graphs, float r, int64_t max_neighbors,
                                            int32_t* count, int32_t* cap_flag, pamnet_stream_t stream) {
-    if (n < 0 || n_graphs < 0 || max_neighbors < 0 || max_neighbors > 0x7fffffff) return PAMNET_EINVAL;
-    if (n == 0) return PAMNET_OK;
-    if (!pos || !cell_table || !node_graph || !gptr || !count) return PAMNET_ENULL;
-    const int mx = (int)max_neighbors;
-    if (n_graphs > 0 && n >= RADIUS_WAVE_MIN_NODES * n_graphs)
-        hipLaunchKernelGGL((radius_wave_pbc_kernel<false>), dim3(blocks_for(n, 4)), dim3(256), 0, as_stream(stream), pos,
-                           cell_table, node_graph, gptr, n, r, count, (const int32_t*)nullptr, (int32_t*)nullptr,
-                           (float*)nullptr, (int64_t)0, (int32_t*)nullptr, mx, cap_flag);
-    else
-        hipLaunchKernelGGL((radius_pbc_kernel<false>), dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), pos, cell_table,
-                           node_graph, gptr, n, r, count, (const int32_t*)nullptr, (int32_t*)nullptr, (float*)nullptr,
-                           (int64_t)0, (int32_t*)nullptr, mx, cap_flag);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
+    const RadiusArgs a{pos, {cell_table, node_graph, nullptr}, nullptr, gptr, n, n_graphs, r, max_neighbors, count, cap_flag, {}};
+    return radius_launch<Periodic>(a, false, stream);
 }
 
 extern "C" int pamnet_radius_pbc_fill_i32(const float* pos, const double* cell_table, const int32_t* node_graph,
                                           const int32_t* gptr, int64_t n, int64_t n_graphs, float r, int64_t max_neighbors,
                                           const int32_t* ptr, int32_t* nbr, float* dist, int32_t* row_of, int64_t cap,
                                           pamnet_stream_t stream) {
-    if (n < 0 || cap < 0 || n_graphs < 0 || max_neighbors < 0 || max_neighbors > 0x7fffffff) return PAMNET_EINVAL;
-    if (n == 0) return PAMNET_OK;
-    if (!pos || !cell_table || !node_graph || !gptr || !ptr || !nbr || !dist) return PAMNET_ENULL;
-    const int mx = (int)max_neighbors;
-    if (n_graphs > 0 && n >= RADIUS_WAVE_MIN_NODES * n_graphs)
-        hipLaunchKernelGGL((radius_wave_pbc_kernel<true>), dim3(blocks_for(n, 4)), dim3(256), 0, as_stream(stream), pos,
-                           cell_table, node_graph, gptr, n, r, (int32_t*)nullptr, ptr, nbr, dist, cap, row_of, mx,
-                           (int32_t*)nullptr);
-    else
-        hipLaunchKernelGGL((radius_pbc_kernel<true>), dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), pos, cell_table,
-                           node_graph, gptr, n, r, (int32_t*)nullptr, ptr, nbr, dist, cap, row_of, mx, (int32_t*)nullptr);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
-}
-
-extern "C" int pamnet_cell_images_i32(const double* cell_table, int64_t n_graphs, float cutoff, int32_t* img_box, int32_t* flag,
-                                      pamnet_stream_t stream) {
-    if (n_graphs < 0 || !(cutoff > 0.f) || !(cutoff <= 3.0e38f)) return PAMNET_EINVAL;      // (NaN and inf refused)
-    if (n_graphs == 0) return PAMNET_OK;
-    if (!cell_table || !img_box || !flag) return PAMNET_ENULL;
-    hipLaunchKernelGGL(cell_images_kernel, dim3(blocks_for(n_graphs)), dim3(256), 0, as_stream(stream), cell_table, n_graphs,
-                       (double)cutoff, img_box, flag);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
-}
-
-extern "C" int pamnet_cell_images_axes_i32(const double* cell_table, const uint8_t* pbc, int64_t n_graphs, float cutoff,
-                                           int32_t* img_box, int32_t* flag, pamnet_stream_t stream) {
-    if (n_graphs < 0 || !(cutoff > 0.f) || !(cutoff <= 3.0e38f)) return PAMNET_EINVAL;      // (NaN and inf refused)
-    if (n_graphs == 0) return PAMNET_OK;
-    if (!cell_table || !pbc || !img_box || !flag) return PAMNET_ENULL;
-    hipLaunchKernelGGL(cell_images_axes_kernel, dim3(blocks_for(n_graphs)), dim3(256), 0, as_stream(stream), cell_table, pbc,
-                       n_graphs, (double)cutoff, img_box, flag);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
+    const RadiusArgs a{pos, {cell_table, node_graph, nullptr}, nullptr, gptr, n, n_graphs, r, max_neighbors, nullptr, nullptr,
+                       {ptr, nbr, dist, row_of, nullptr, cap}};
+    return radius_launch<Periodic>(a, true, stream);
 }
 
 extern "C" int pamnet_radius_img_count_i32(const float* pos, const double* cell_table, const int32_t* img_box,
                                            const int32_t* node_graph, const int32_t* gptr, int64_t n, int64_t n_graphs, float r,
                                            int64_t max_neighbors, int32_t* count, int32_t* cap_flag, pamnet_stream_t stream) {
-    if (n < 0 || n_graphs < 0 || max_neighbors < 0 || max_neighbors > 0x7fffffff) return PAMNET_EINVAL;
-    if (n == 0) return PAMNET_OK;
-    if (!pos || !cell_table || !img_box || !node_graph || !gptr || !count) return PAMNET_ENULL;
-    hipLaunchKernelGGL((radius_img_kernel<false>), dim3(blocks_for(n, 4)), dim3(256), 0, as_stream(stream), pos, cell_table,
-                       img_box, node_graph, gptr, n, r, count, (const int32_t*)nullptr, (int32_t*)nullptr, (float*)nullptr,
-                       (int64_t)0, (int32_t*)nullptr, (int32_t*)nullptr, (int)max_neighbors, cap_flag);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
+    const RadiusArgs a{pos, {cell_table, node_graph, nullptr}, img_box, gptr, n, n_graphs, r, max_neighbors, count, cap_flag, {}};
+    return radius_launch<AllImages>(a, false, stream);
 }
 
 extern "C" int pamnet_radius_img_fill_i32(const float* pos, const double* cell_table, const int32_t* img_box,
                                           const int32_t* node_graph, const int32_t* gptr, int64_t n, int64_t n_graphs, float r,
                                           int64_t max_neighbors, const int32_t* ptr, int32_t* nbr, float* dist, int32_t* row_of,
                                           int32_t* img, int64_t cap, pamnet_stream_t stream) {
-    if (n < 0 || cap < 0 || n_graphs < 0 || max_neighbors < 0 || max_neighbors > 0x7fffffff) return PAMNET_EINVAL;
-    if (n == 0) return PAMNET_OK;
-    if (!pos || !cell_table || !img_box || !node_graph || !gptr || !ptr || !nbr || !dist || !img) return PAMNET_ENULL;
-    hipLaunchKernelGGL((radius_img_kernel<true>), dim3(blocks_for(n, 4)), dim3(256), 0, as_stream(stream), pos, cell_table,
-                       img_box, node_graph, gptr, n, r, (int32_t*)nullptr, ptr, nbr, dist, cap, row_of, img, (int)max_neighbors,
-                       (int32_t*)nullptr);
+    const RadiusArgs a{pos, {cell_table, node_graph, nullptr}, img_box, gptr, n, n_graphs, r, max_neighbors, nullptr, nullptr,
+                       {ptr, nbr, dist, row_of, img, cap}};
+    return radius_launch<AllImages>(a, true, stream);
+}
+
+// The cell table and the image box: a null pbc is three periodic axes, which the _axes_ entry points (`axes`) refuse.
+static int cell_prepare(const float* cell, const uint8_t* pbc, bool axes, int64_t n_graphs, float cutoff, double* table,
+                        int32_t* flag, pamnet_stream_t stream) {
+    if (n_graphs < 0 || !(cutoff > 0.f) || !(cutoff <= 3.0e38f)) return PAMNET_EINVAL;      // (NaN and inf refused)
+    if (n_graphs == 0) return PAMNET_OK;
+    if (!cell || (axes && !pbc) || !table || !flag) return PAMNET_ENULL;
+    hipLaunchKernelGGL(cell_prepare_kernel, dim3(blocks_for(n_graphs)), dim3(256), 0, as_stream(stream), cell, pbc, n_graphs,
+                       (double)cutoff, table, flag);
     PAMNET_LAUNCH_CHECK();
     return PAMNET_OK;
+}
+
+static int cell_images(const double* cell_table, const uint8_t* pbc, bool axes, int64_t n_graphs, float cutoff, int32_t* img_box,
+                       int32_t* flag, pamnet_stream_t stream) {
+    if (n_graphs < 0 || !(cutoff > 0.f) || !(cutoff <= 3.0e38f)) return PAMNET_EINVAL;      // (NaN and inf refused)
+    if (n_graphs == 0) return PAMNET_OK;
+    if (!cell_table || (axes && !pbc) || !img_box || !flag) return PAMNET_ENULL;
+    hipLaunchKernelGGL(cell_images_kernel, dim3(blocks_for(n_graphs)), dim3(256), 0, as_stream(stream), cell_table, pbc, n_graphs,
+                       (double)cutoff, img_box, flag);
+    PAMNET_LAUNCH_CHECK();
+    return PAMNET_OK;
+}
+
+extern "C" int pamnet_cell_prepare_f64(const float* cell, int64_t n_graphs, float cutoff, double* table, int32_t* flag,
+                                       pamnet_stream_t stream) {
+    return cell_prepare(cell, nullptr, false, n_graphs, cutoff, table, flag, stream);
+}
+
+extern "C" int pamnet_cell_prepare_axes_f64(const float* cell, const uint8_t* pbc, int64_t n_graphs, float cutoff, double* table,
+                                            int32_t* flag, pamnet_stream_t stream) {
+    return cell_prepare(cell, pbc, true, n_graphs, cutoff, table, flag, stream);
+}
+
+extern "C" int pamnet_cell_images_i32(const double* cell_table, int64_t n_graphs, float cutoff, int32_t* img_box, int32_t* flag,
+                                      pamnet_stream_t stream) {
+    return cell_images(cell_table, nullptr, false, n_graphs, cutoff, img_box, flag, stream);
+}
+
+extern "C" int pamnet_cell_images_axes_i32(const double* cell_table, const uint8_t* pbc, int64_t n_graphs, float cutoff,
+                                           int32_t* img_box, int32_t* flag, pamnet_stream_t stream) {
+    return cell_images(cell_table, pbc, true, n_graphs, cutoff, img_box, flag, stream);
 }
 
 extern "C" int pamnet_knn_i32(const float* pos, const int32_t* node_graph, const int32_t* gptr, int64_t n, int32_t k,
@@ -1862,28 +1756,17 @@ extern "C" int pamnet_triplet_fill_f32(const float* pos, const int32_t* lptr, co
                                        int64_t n_edges, int32_t with_triplets, const int32_t* tp_ptr, int32_t* tp_idx,
                                        int32_t* tp_edge, float* tp_angle, int32_t* tp_kind, int64_t cap,
                                        pamnet_stream_t stream) {
-    if (n_edges < 0 || cap < 0) return PAMNET_EINVAL;
-    if (n_edges == 0) return PAMNET_OK;
-    if (!pos || !lptr || !src || !dst || !tp_ptr || !tp_idx || !tp_edge || !tp_angle || !tp_kind) return PAMNET_ENULL;
-    hipLaunchKernelGGL(triplet_fill_kernel, dim3(blocks_for(n_edges)), dim3(256), 0, as_stream(stream), pos, lptr, src,
-                       dst, n_edges, (int)with_triplets, tp_ptr, tp_idx, tp_edge, tp_angle, tp_kind, cap);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
+    const TripletArgs a{pos, {}, lptr, src, dst, n_edges, (int)with_triplets, tp_ptr, tp_idx, tp_edge, tp_angle, tp_kind, cap};
+    return triplet_fill_launch<OpenSpace>(a, stream);
 }
 
 extern "C" int pamnet_triplet_fill_pbc_f32(const float* pos, const double* cell_table, const int32_t* node_graph,
                                            const int32_t* lptr, const int32_t* src, const int32_t* dst, int64_t n_edges,
                                            int32_t with_triplets, const int32_t* tp_ptr, int32_t* tp_idx, int32_t* tp_edge,
                                            float* tp_angle, int32_t* tp_kind, int64_t cap, pamnet_stream_t stream) {
-    if (n_edges < 0 || cap < 0) return PAMNET_EINVAL;
-    if (n_edges == 0) return PAMNET_OK;
-    if (!pos || !cell_table || !node_graph || !lptr || !src || !dst || !tp_ptr || !tp_idx || !tp_edge || !tp_angle || !tp_kind)
-        return PAMNET_ENULL;
-    hipLaunchKernelGGL(triplet_fill_pbc_kernel, dim3(blocks_for(n_edges)), dim3(256), 0, as_stream(stream), pos, cell_table,
-                       node_graph, lptr, src, dst, n_edges, (int)with_triplets, tp_ptr, tp_idx, tp_edge, tp_angle, tp_kind,
-                       cap);
-    PAMNET_LAUNCH_CHECK();
-    return PAMNET_OK;
+    const TripletArgs a{pos, {cell_table, node_graph, nullptr}, lptr, src, dst, n_edges, (int)with_triplets, tp_ptr, tp_idx,
+                        tp_edge, tp_angle, tp_kind, cap};
+    return triplet_fill_launch<Periodic>(a, stream);
 }
 
 // ---- transposed CSR of a symmetric graph = the reverse-edge index --------------------------------------------------------

@@ -384,7 +384,7 @@ def test_header_declares_the_axes_entry_points_at_abi_18():
 
 
 def test_axes_kernels_are_scratch_free(tmp_path):
-    """(No GPU: hipcc cross-compiles csrc/graph.hip for gfx950.)  Compiler's resource report of the two new kernels, by the
+    """(No GPU: hipcc cross-compiles csrc/graph.hip for gfx950.)  Compiler's resource report of the cell-table and image-box kernels, by the
     protocol of tests/test_build_resources.py."""
     import os
     import re
@@ -398,7 +398,7 @@ def test_axes_kernels_are_scratch_free(tmp_path):
                                                 '-Rpass-analysis=kernel-resource-usage'], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     blocks = {b.split()[0]: b for b in re.split(r'remark: Function Name: ', r.stderr)[1:]}
-    for kernel in ('cell_prepare_axes_kernel', 'cell_images_axes_kernel'):
+    for kernel in ('cell_prepare_kernel', 'cell_images_kernel'):
         found = [b for name, b in blocks.items() if kernel in name]
         assert len(found) == 1, kernel
         assert int(re.search(r'ScratchSize \[bytes/lane\]: (\d+)', found[0]).group(1)) == 0, kernel
