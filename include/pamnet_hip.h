@@ -593,6 +593,61 @@ int pamnet_fire_step_f32(float* pos, float* vel, const float* dpos, const uint8_
                          double f_dec, double a0, double f_a, pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Molecular dynamics: one step of every graph of a batch in one launch, and Maxwell-Boltzmann velocities (csrc/md.hip; the
+ * reference has no integrator).  Each graph carries its own step counter, status and seed, and optionally its own time step,
+ * temperature and friction, so its trajectory does not depend on what else the batch holds.  Units are the caller's.
+ *   pos, vel [n, 3] fp32, updated in place;  dpos [n, 3] fp32 = dE/dpos, f = -dpos;  mass [n] fp32 (positive) or NULL: unit
+ *   masses;  fixed [n] uint8 or NULL: an atom with fixed[a] != 0 enters no sum and its rows of pos and vel are neither read
+ *   nor written;  gptr [n_graphs + 1]: first atom of every graph (kept inside [0, n]).
+ *   Per graph: seed [n_graphs] int64;  steps, status [n_graphs] int32 (status 0 = running, 2 = failed; a graph whose status is
+ *   not 0 is left alone);  ke [n_graphs] fp64 (output).  dt_g, kT_g, gamma_g [n_graphs] fp64 or NULL: NULL means the scalar
+ *   dt / kT / gamma holds for every graph (as fmax_tol_g / fmax_tol above); the scalar beside a given array is not looked at.
+ *   Values inside the arrays are the caller's to keep sensible: dt > 0, kT >= 0; a graph whose gamma is not > 0 has no thermostat.
+ *
+ * THE GENERATOR, shared by both entry points: Philox4x32-10 (Salmon et al., SC 2011; multipliers 0xD2511F53, 0xCD9E8D57, key
+ * increments 0x9E3779B9, 0xBB67AE85).  Key = (low 32 bits, high 32 bits) of seed[g].  Counter = (i, step, stream, 0): i the atom's
+ * offset inside its graph (a - gptr[g], fixed atoms counted), step the graph's step counter, stream 0 for the thermostat and 1
+ * for the initial velocities.  From the four outputs x0 .. x3: u_j = (x_j + 0.5) 2^-32 in fp64, r0 = sqrt(-2 ln u0),
+ * r1 = sqrt(-2 ln u2), and the atom's three normals are xi = (r0 cos 2 pi u1, r0 sin 2 pi u1, r1 cos 2 pi u3).  Nothing else feeds the
+ * noise: it depends on the graph's seed, its step count and the atom's offset only.
+ *
+ * pamnet_md_step_f32: BAOAB (Leimkuhler & Matthews, J. Chem. Phys. 138, 174102, 2013) with one force evaluation per step; the
+ * closing half kick of step n - 1 is fused into the launch of step n.  Per graph g, the sums over its free atoms:
+ *   1. status[g] != 0: nothing that belongs to g is read-modified or written.
+ *   2. v_n = v + kick_in (dt / 2) f / m: the velocities that belong to pos.
+ *   3. F2 = sum |f|^2, KE = 1/2 sum m |v_n|^2; ke[g] = KE.  F2 or KE not finite: status[g] = 2, nothing else of g is written.
+ *   4. advance == 0: vel <- fp32(v_n); steps[g] stays.  Done.
+ *   5. v1 = v_n + (dt / 2) f / m.  gamma > 0: v2 = c1 v1 + c2 sqrt(kT / m) xi with c1 = exp(-gamma dt), c2 = sqrt(1 - c1^2) and
+ *      xi from (seed[g], steps[g], stream 0, i).  Else v2 = v1 and neither seed nor generator is touched: velocity Verlet,
+ *      exactly.  pos <- fp32(pos + (dt / 2) (v1 + v2)); vel <- fp32(v2).
+ *   6. steps[g] += 1.
+ * A trajectory is: (kick_in 0, advance 1) after the first evaluation, (1, 1) after every later one, and (1, 0) after the
+ * evaluation at the last positions, which leaves vel and ke[g] belonging to pos.  Two passes: the sums, then the stores.
+ *
+ * pamnet_md_init_velocities_f32: per graph g, over its free atoms (rows of fixed atoms are not written):
+ *   1. v = sqrt(kT / m) xi(seed[g], step 0, stream 1, i).
+ *   2. remove_com: v -= sum m v / sum m.
+ *   3. rescale: dof = 3 n_free - 3 remove_com; if dof > 0 and KE = 1/2 sum m |v|^2 > 0: v *= sqrt(dof kT / (2 KE)).
+ *   4. vel <- fp32(v); ke[g] = the kinetic energy of v, in fp64 before that rounding.
+ * Three passes (momentum, kinetic energy, stores); the normals are regenerated in each.
+ *
+ * Both: arithmetic in fp64 from the fp32 inputs, one rounding to fp32 at each store of pos and vel.  Sums in a fixed order (a
+ * thread's atoms ascending, wavefront butterfly, the wavefronts in order through LDS), no atomics: the outputs of a graph are
+ * bitwise repeatable and bitwise the same whether it is handled alone or inside any batch.  One workgroup per graph.
+ * Returns PAMNET_EINVAL for a negative count, n_graphs above 2^31 - 1, a flag (kick_in, advance, remove_com, rescale) other
+ * than 0 / 1, and, where the per-graph array is NULL, a scalar dt that is not positive and finite or a scalar kT / gamma that is
+ * negative or not finite; PAMNET_ENULL for a null required pointer: mass, fixed, dt_g, kT_g and gamma_g may be NULL, and the
+ * step's seed where gamma_g is NULL and gamma == 0.  n_graphs == 0 launches nothing.  (Part of ABI 18: nothing existing changed.)
+ * ------------------------------------------------------------------------------------------------------------------ */
+int pamnet_md_step_f32(float* pos, float* vel, const float* dpos, const float* mass, const uint8_t* fixed, const int32_t* gptr,
+                       int64_t n, int64_t n_graphs, const int64_t* seed, int32_t* steps, int32_t* status, double* ke,
+                       const double* dt_g, const double* kT_g, const double* gamma_g, double dt, double kT, double gamma,
+                       int32_t kick_in, int32_t advance, pamnet_stream_t stream);
+int pamnet_md_init_velocities_f32(float* vel, const float* mass, const uint8_t* fixed, const int32_t* gptr, int64_t n,
+                                  int64_t n_graphs, const int64_t* seed, const double* kT_g, double kT, int32_t remove_com,
+                                  int32_t rescale, double* ke, pamnet_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Attention fusion + per-graph pooling  (models.py:206-224)
  * outs/atts: [2L, n] rows ordered (global_0, local_0, global_1, local_1, ...).
  *   node_out[n] = sign[n] * sum_l sum_c outs[l,c,n] * softmax_c(leaky_relu(atts[l,c,n], 0.2))

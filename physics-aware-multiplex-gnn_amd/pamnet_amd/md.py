@@ -1,0 +1,203 @@
+"""Batched molecular dynamics on the device: NVE (velocity Verlet) and Langevin (BAOAB, Leimkuhler & Matthews, J. Chem. Phys. 138,
+174102, 2013) over the forces of a model.
+
+    from pamnet_amd.md import run
+    res = run(model, data, steps=1000, dt=0.1, masses=m, kT=0.025, gamma=0.1, seed=seeds, record_every=10)
+
+Every graph of the batch carries its own step counter, status and seed (csrc/md.hip pamnet_md_step_f32, one launch per step;
+include/pamnet_hip.h states the rule and the generator).  The noise is counter-based -- Philox4x32-10 keyed by the graph's seed,
+counted by the atom's offset in its graph and the graph's step -- so a structure's trajectory does not depend on its batch-mates
+and is bitwise repeatable.  The loop takes no decision on the host.  There is no CPU path.
+
+Units are the caller's: with energies in eV, lengths in Angstrom and masses in amu the time unit is 10.1805 fs (dt = 0.1 is about
+1 fs), and kT is in eV."""
+import torch
+
+from . import graph as G
+from . import lib
+from .relax import _checked, _evaluate
+
+STATE = ('seed', 'steps', 'status', 'ke')
+RUNNING, FAILED = 0, 2
+
+
+class MDResult(object):
+    """pos, vel [N, 3] fp32 (new tensors), energy [G] and forces [N, 3] of one evaluation at `pos`, kinetic [G] fp64 (of `vel`),
+    steps int32 [G] (the steps a graph moved), failed bool [G], frames [F, N, 3] fp32 / epot, ekin [F, G] fp64 (record_every > 0,
+    else None), trace (trace=True: one dict per launch, else None).  All on the device."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def new_state(n, n_graphs, device, seed=0):
+    """(vel [n, 3] fp32 zeros, state) for pamnet_md_step_f32: state = dict of seed (int64), steps, status (int32), ke (fp64), each
+    [n_graphs].  seed: an int -- graph g gets seed + g -- or an int64 tensor [n_graphs] on the device."""
+    if isinstance(seed, torch.Tensor):
+        if seed.dtype != torch.int64 or tuple(seed.shape) != (n_graphs,) or seed.device != torch.device(device):
+            raise ValueError('a per-graph `seed` is an int64 tensor [num_graphs] = [%d] on the device of `pos`; got %s %s on %s'
+                             % (n_graphs, seed.dtype, tuple(seed.shape), seed.device))
+        seed = seed.contiguous()
+    else:
+        try:
+            seed = int(seed) + torch.arange(n_graphs, dtype=torch.int64, device=device)
+        except (TypeError, ValueError):
+            raise ValueError('`seed` is an int, or an int64 tensor [num_graphs] on the device of `pos`; got %r' % (type(seed),))
+    state = dict(seed=seed, steps=torch.zeros(n_graphs, dtype=torch.int32, device=device),
+                 status=torch.zeros(n_graphs, dtype=torch.int32, device=device),
+                 ke=torch.zeros(n_graphs, dtype=torch.float64, device=device))
+    return torch.zeros(n, 3, dtype=torch.float32, device=device), state
+
+
+def _split(v):
+    """A per-graph tensor or a scalar -> (pointer or None, the scalar the entry point takes beside it)."""
+    return (lib.ptr(v), 0.0) if isinstance(v, torch.Tensor) else (None, float(v))
+
+
+def md_step(pos, vel, dpos, gptr, state, dt, kT=0.0, gamma=0.0, mass=None, fixed=None, kick_in=1, advance=1):
+    """One launch of pamnet_md_step_f32, in place on pos, vel and state (no synchronisation).  pos, vel, dpos: fp32 [n, 3]; gptr:
+    int32 [n_graphs + 1]; mass: fp32 [n] or None; fixed: uint8 / bool [n] or None; dt, kT, gamma: a float, or fp64 [n_graphs];
+    state['seed'] may be None where gamma is the float 0."""
+    (dt_g, dt), (kT_g, kT), (gamma_g, gamma) = _split(dt), _split(kT), _split(gamma)
+    lib.call('pamnet_md_step_f32', lib.ptr(pos), lib.ptr(vel), lib.ptr(dpos), lib.ptr(mass), lib.ptr(fixed), lib.ptr(gptr),
+             pos.size(0), gptr.numel() - 1, lib.ptr(state['seed']), lib.ptr(state['steps']), lib.ptr(state['status']),
+             lib.ptr(state['ke']), dt_g, kT_g, gamma_g, dt, kT, gamma, int(kick_in), int(advance), lib.stream_of(pos))
+
+
+def init_velocities(vel, gptr, seed, kT, ke, mass=None, fixed=None, remove_com=True, rescale=False):
+    """One launch of pamnet_md_init_velocities_f32: Maxwell-Boltzmann velocities at kT (a float, or fp64 [n_graphs]) into the rows
+    of the free atoms of vel (fp32 [n, 3]), the kinetic energies into ke (fp64 [n_graphs]).  seed: int64 [n_graphs]."""
+    kT_g, kT = _split(kT)
+    lib.call('pamnet_md_init_velocities_f32', lib.ptr(vel), lib.ptr(mass), lib.ptr(fixed), lib.ptr(gptr), vel.size(0),
+             gptr.numel() - 1, lib.ptr(seed), kT_g, kT, int(bool(remove_com)), int(bool(rescale)), lib.ptr(ke), lib.stream_of(vel))
+
+
+def temperature(ekin, n_free, remove_com=True):
+    """kT = 2 KE / dof with dof = 3 n_free - 3 (remove_com); floats, arrays or tensors, per graph."""
+    return 2.0 * ekin / (3 * n_free - (3 if remove_com else 0))
+
+
+def _per_graph(name, v, n_graphs, device, positive):
+    """A float, or an fp64 tensor [num_graphs] on the device of pos -> (the value to hand on, its validity as a 0-dim device bool
+    or None).  A float is checked here."""
+    if isinstance(v, torch.Tensor):
+        if v.dtype != torch.float64 or tuple(v.shape) != (n_graphs,) or v.device != device:
+            raise ValueError('a per-graph `%s` is a float64 tensor [num_graphs] = [%d] on the device of `pos`; got %s %s on %s'
+                             % (name, n_graphs, v.dtype, tuple(v.shape), v.device))
+        v = v.contiguous()
+        return v, (torch.isfinite(v) & ((v > 0) if positive else (v >= 0))).all()
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        raise ValueError('`%s` is a float, or a float64 tensor [num_graphs] on the device of `pos`; got %r' % (name, type(v)))
+    if not ((v > 0.0 if positive else v >= 0.0) and v != float('inf')):
+        raise ValueError('`%s` must be %s and finite; got %r' % (name, 'positive' if positive else 'non-negative', v))
+    return v, None
+
+
+def run(model, data, steps, dt, masses=None, kT=None, gamma=0.0, seed=0, fixed=None, velocities=None, remove_com=True,
+        record_every=0, check_every=0, trace=False):
+    """Move every graph of `data` for `steps` steps of length `dt`: velocity Verlet where gamma is 0, Langevin dynamics (BAOAB) at
+    temperature kT and friction gamma elsewhere.  One model evaluation and one launch of the integrator per step.
+
+    model:  any callable with model(data) -> [G] that is differentiable with respect to `data.pos`, as for relax(): PAMNet /
+            PAMNet_s on the QM9 schema (bonded, bond-free, periodic with `cell` / `pbc` / `cell_images` / `mol_local`, MoleculeStore
+            batches), or a plain torch module.  The graph is rebuilt by every evaluation; positions are never wrapped.
+    data:   the batch; `data.pos` is never written and no parameter .grad is touched (see relax()).
+    dt, kT, gamma: a float, or an fp64 tensor [G] on the device (one value per graph).  gamma > 0 needs kT.  Units are the
+            caller's: with eV, Angstrom and amu the time unit is 10.1805 fs.
+    masses: fp32 [N] on the device, positive; None: unit masses.
+    seed:   an int: graph g gets seed + g, so its noise depends on its place in the batch.  Only an int64 tensor [G] on the device
+            -- one seed per structure, chosen by the caller -- makes a graph's noise, and with it its trajectory, independent of
+            where in which batch it runs.
+    fixed:  bool [N] on the device (True: the atom does not move), or None.
+    velocities: fp32 [N, 3] on the device (not written); None: Maxwell-Boltzmann velocities at kT (the centre-of-mass motion
+            removed if `remove_com`, not rescaled), or zeros where kT is None.
+    record_every: k > 0: the steps 0, k, 2k, ... <= steps are recorded at the full step (x_n and the velocities v_n that belong to
+            it) into res.frames [F, N, 3], res.epot and res.ekin [F, G] with F = steps // k + 1, by device-side copies.  Records
+            that an early stop (check_every) did not reach stay zero.
+    check_every: k > 0: the status vector is read every k steps, to stop once every graph has failed (a non-finite force or
+            velocity).  0 (default): never -- everything is enqueued without a synchronisation of the driver's own.
+    trace:  for tests and debugging: one dict per launch with clones of pos, dE/dpos, vel and the state before and after it.
+
+    The first launch opens step 0 (kick_in = 0), every later one closes the step before and opens the next, and one more
+    evaluation and a closing launch (advance = 0) end the run: res.vel, res.kinetic, res.energy and res.forces all belong to
+    res.pos.  A failed graph stops moving but is still evaluated."""
+    try:
+        pos, batch, n_graphs, _, fixed8 = _checked(model, data, 0.0, fixed)
+    except ValueError as e:
+        raise ValueError('md.run takes what relax() takes: %s' % (e,)) from None
+    device, n = pos.device, pos.size(0)
+    steps, record_every, check_every = int(steps), int(record_every), int(check_every)
+    if steps < 0 or record_every < 0 or check_every < 0:
+        raise ValueError('`steps`, `record_every` and `check_every` are non-negative; got %d, %d, %d'
+                         % (steps, record_every, check_every))
+    thermostat = isinstance(gamma, torch.Tensor) or (isinstance(gamma, (int, float)) and gamma > 0)
+    if thermostat and kT is None:
+        raise ValueError('a thermostat (`gamma` > 0, or per graph) needs its temperature: pass `kT`')
+    checks = {}
+    dt, checks['dt'] = _per_graph('dt', dt, n_graphs, device, True)
+    gamma, checks['gamma'] = _per_graph('gamma', gamma, n_graphs, device, False)
+    kT_k, checks['kT'] = _per_graph('kT', 0.0 if kT is None else kT, n_graphs, device, False)
+    if masses is not None:
+        if (not isinstance(masses, torch.Tensor) or masses.dtype != torch.float32 or tuple(masses.shape) != (n,)
+                or masses.device != device):
+            raise ValueError('`masses` is a float32 tensor [N] = [%d] on the device of `pos`; got %s'
+                             % (n, '%s %s on %s' % (masses.dtype, tuple(masses.shape), masses.device)
+                                if isinstance(masses, torch.Tensor) else type(masses)))
+        masses = masses.contiguous()
+        checks['masses'] = (torch.isfinite(masses) & (masses > 0)).all()
+    if velocities is not None and (not isinstance(velocities, torch.Tensor) or velocities.dtype != torch.float32
+                                   or tuple(velocities.shape) != (n, 3) or velocities.device != device):
+        raise ValueError('`velocities` is a float32 tensor [N, 3] = [%d, 3] on the device of `pos`; got %s'
+                         % (n, '%s %s on %s' % (velocities.dtype, tuple(velocities.shape), velocities.device)
+                            if isinstance(velocities, torch.Tensor) else type(velocities)))
+    vel, state = new_state(n, n_graphs, device, seed)
+    names = [k for k, v in checks.items() if v is not None]
+    if names:                                     # (as num_graphs: one read at set-up, for every tensor of values at once)
+        ok = torch.stack([checks[k] for k in names]).tolist()
+        bad = [k for k, good in zip(names, ok) if not good]
+        if bad:
+            raise ValueError('%s must be finite and positive (kT, gamma: non-negative) in every entry'
+                             % ' and '.join('`%s`' % k for k in bad))
+    cur = pos.detach().to(torch.float32).clone().contiguous()
+    gptr, _ = G.csr_from_keys(batch.to(torch.int32).contiguous(), n_graphs)
+    if velocities is not None:
+        vel = velocities.detach().clone().contiguous()
+    elif kT is not None:
+        init_velocities(vel, gptr, state['seed'], kT_k, state['ke'], masses, fixed8, remove_com=remove_com)
+    frames = epot = ekin = None
+    if record_every:
+        n_rec = steps // record_every + 1
+        frames = torch.zeros(n_rec, n, 3, dtype=torch.float32, device=device)
+        epot = torch.zeros(n_rec, n_graphs, dtype=torch.float64, device=device)
+        ekin = torch.zeros(n_rec, n_graphs, dtype=torch.float64, device=device)
+    log = [] if trace else None
+
+    def launch(it, kick_in, advance):
+        """Evaluate at cur, then one launch; step `it` is recorded at its full step: cur before the launch, ke after it."""
+        e, de = _evaluate(model, data, cur)
+        rec = record_every and it % record_every == 0
+        if rec:
+            frames[it // record_every].copy_(cur)
+            epot[it // record_every].copy_(e.reshape(-1))
+        if trace:
+            t = dict(pos=cur.clone(), dE=de.clone(), v_before=vel.clone(), kick_in=kick_in, advance=advance,
+                     state_before={k: state[k].clone() for k in STATE})
+        md_step(cur, vel, de, gptr, state, dt, kT_k, gamma, masses, fixed8, kick_in, advance)
+        if rec:
+            ekin[it // record_every].copy_(state['ke'])
+        if trace:
+            t.update(pos_after=cur.clone(), v_after=vel.clone(), state_after={k: state[k].clone() for k in STATE})
+            log.append(t)
+        return e, de
+
+    done = 0
+    for it in range(steps):
+        launch(it, 1 if it else 0, 1)
+        done = it + 1
+        if check_every and done % check_every == 0 and not bool((state['status'] == RUNNING).any()):
+            break
+    energy, de = launch(done, 1 if done else 0, 0)  # one more evaluation: energy, forces, vel and ke belong to the final geometry
+    return MDResult(pos=cur, vel=vel, energy=energy, kinetic=state['ke'], forces=-de, steps=state['steps'],
+                    failed=state['status'] == FAILED, frames=frames, epot=epot, ekin=ekin, trace=log)
