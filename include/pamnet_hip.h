@@ -593,6 +593,59 @@ int pamnet_fire_step_f32(float* pos, float* vel, const float* dpos, const uint8_
                          double f_dec, double a0, double f_a, pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Cell relaxation: one FIRE step over the atoms AND the cell of every graph of a batch, in one launch (csrc/relax_cell.hip).
+ * The unit-cell-filter formulation (Tadmor et al., Phys. Rev. B 59, 235, 1999; ASE's UnitCellFilter, whose deformation gradient
+ * is the transpose of this one) in the project's row-vector convention, pos -> pos (I + eps), cell -> cell (I + eps):
+ *   per graph a reference cell cell0 (rows = lattice vectors, never written) and a deformation gradient F (starts at I);
+ *   the current cell is C = cell0 F, the generalised atom coordinates are x~ = pos F^-1, the generalised cell coordinate is
+ *   L F with L the graph's cell factor.  vel holds the generalised velocities v~ of the atoms, vcell those of L F.
+ * Arguments beyond those of pamnet_fire_step_f32 (all [n_graphs, 9] row-major 3 x 3 unless noted):
+ *   dstrain fp32: the virial W = dE/d eps at zero strain;  cell0 fp32, read only;  cell fp32, written: fp32(cell0 F) of the new
+ *   geometry;  F, vcell fp64: state (the caller starts with F = I, vcell = 0);  cell_dof [n_graphs] uint8 or NULL: 0 = the
+ *   graph keeps its cell, NULL = every graph relaxes its cell;  cell_factor [n_graphs] fp64: L (positive; the caller's to keep
+ *   so);  pressure_g [n_graphs] fp64 or NULL: NULL means the scalar pressure p holds for every graph, and likewise smax_tol_g
+ *   [n_graphs] fp32 / smax_tol, the stress threshold (as fmax_tol_g / fmax_tol: the scalar beside a given array is not looked
+ *   at);  hydrostatic: 0 / 1, for the whole launch;  smax [n_graphs] fp32 (output, beside fmax).
+ * The step of graph g with cell_dof[g] != 0; "free" = the atoms of g that are not fixed, f = -dpos, M^T = transpose:
+ *   0. status[g] != 0: nothing that belongs to g is read-modified or written.
+ *   1. V = |det(cell0 F)|.  S = (W + W^T) / 2 + p V I.  hydrostatic: S <- (tr S / 3) I.  sm = max_ij |S_ij| / V (NaN-propagating).
+ *   2. fm = max |f| over the free atoms.  Atom force g_a = f_a F^T, cell force g_c = -(F^-T S) / L (nine entries).
+ *   3. F2 = sum_free |g_a|^2 + sum g_c^2, the nine cell terms added after the sum over the atoms, in index order (and so for P
+ *      and V2 below).  F2 or V not finite, or V == 0: status[g] = 2, fmax[g] = sqrt(F2), smax[g] = sm, nothing else is written.
+ *      Else fm < fmax tolerance and sm < smax tolerance: status[g] = 1, fmax[g] = fm, smax[g] = sm, nothing else is written.
+ *   4. P = sum g_a . v~_a + sum g_c v_c, V2 = sum |v~_a|^2 + sum v_c^2, and the decision of pamnet_fire_step_f32, step 3,
+ *      verbatim: V2 == 0: nothing.  Else P > 0: n_pos += 1; if n_pos > n_min then dt = min(dt f_inc, dt_max) and a *= f_a; then
+ *      c_v = 1 - a, c_f = a sqrt(V2 / F2).  Else c_v = 0 (c_f = 0), a = a0, dt *= f_dec, n_pos = 0.  (n_pos, dt, a first.)
+ *   5. v~ <- (c_v v~ + c_f g) + dt g, for the rows of the free atoms and the three rows of the cell alike.
+ *   6. s = min(1, max_step / m), m the largest norm among the rows dt v~_a of the free atoms and the three rows of dt v_c (s = 1
+ *      where m is 0): the cell moves by at most max_step / L in strain per step.
+ *   7. F_new = F + s dt v_c / L.  det F_new not positive and finite: status[g] = 2, fmax[g] = fm, smax[g] = sm, nothing else is
+ *      written.
+ *   8. D = F^-1 F_new.
+ *   9. Every atom of g, fixed ones included: pos_a <- pos_a D, and for a free atom + s dt v~_a F_new (one rounding).  A fixed
+ *      atom keeps its generalised coordinate and so follows the cell; its row of vel is neither read nor written.  vel <- v~.
+ *  10. cell[g] = fp32(cell0 F_new), F[g] = F_new, vcell[g] = v_c (not scaled), steps[g] += 1; fmax[g] = fm, smax[g] = sm, and
+ *      dt, a, n_pos are written.
+ * A graph with cell_dof[g] == 0 takes the rule of pamnet_fire_step_f32 exactly: its pos, vel, dt, a, n_pos, steps, status and
+ * fmax are bitwise what that entry point gives (convergence on fm alone; its fixed atoms do not move), and its cell, F, vcell
+ * and smax are not written; dstrain, cell0, cell_factor and the pressure of that graph are not read.
+ * Arithmetic in fp64 from the fp32 inputs, one rounding at each fp32 store; sums in the fixed order of pamnet_fire_step_f32,
+ * every thread of the graph's workgroup forming the 3 x 3 algebra and the decision alike; no atomics: the outputs of a graph
+ * are bitwise repeatable and bitwise the same alone or inside any batch.  One workgroup per graph.
+ * Returns PAMNET_ENULL for a null required pointer (fixed, cell_dof, fmax_tol_g, smax_tol_g, pressure_g may be NULL);
+ * PAMNET_EINVAL for a negative count, n_graphs above 2^31 - 1, n_min < 0, hydrostatic other than 0 / 1, a NaN fmax_tol or
+ * smax_tol, a pressure that is not finite, or one of dt_max, max_step, f_inc, f_dec, a0, f_a that is not positive and finite.
+ * n_graphs == 0 launches nothing.  (Part of ABI 18: nothing existing changed.)
+ * ------------------------------------------------------------------------------------------------------------------ */
+int pamnet_fire_cell_step_f32(float* pos, float* vel, const float* dpos, const float* dstrain, const uint8_t* fixed,
+                              const int32_t* gptr, int64_t n, int64_t n_graphs, const float* cell0, float* cell, double* F,
+                              double* vcell, const uint8_t* cell_dof, const double* cell_factor, double* dt, double* a,
+                              int32_t* n_pos, int32_t* steps, int32_t* status, float* fmax, float* smax,
+                              const float* fmax_tol_g, const float* smax_tol_g, const double* pressure_g, double fmax_tol,
+                              double smax_tol, double pressure, int32_t hydrostatic, double dt_max, double max_step,
+                              int32_t n_min, double f_inc, double f_dec, double a0, double f_a, pamnet_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Molecular dynamics: one step of every graph of a batch in one launch, and Maxwell-Boltzmann velocities (csrc/md.hip; the
  * reference has no integrator).  Each graph carries its own step counter, status and seed, and optionally its own time step,
  * temperature and friction, so its trajectory does not depend on what else the batch holds.  Units are the caller's.
