@@ -701,6 +701,59 @@ int pamnet_md_init_velocities_f32(float* vel, const float* mass, const uint8_t* 
                                   int32_t rescale, double* ke, pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Constant-pressure molecular dynamics (isotropic NPT): the BAOAB step above with the stochastic cell rescaling barostat
+ * (Bernetti & Bussi, J. Chem. Phys. 153, 114107, 2020; GROMACS's c-rescale) fused into the same launch (csrc/md_npt.hip; the
+ * reference has no integrator).  The barostat is first order and carries no cell velocity: its state per graph is one fp64
+ * number, eps = ln(V / V0), V0 = |det cell0|.  It samples the isothermal-isobaric ensemble to first order in dt; with kT = 0 it
+ * is a deterministic Berendsen-like relaxation towards the target pressure.
+ * Conventions are those of pamnet_fire_cell_step_f32: row vectors, pos -> pos (I + e), cell -> cell (I + e), and the virial
+ * W = dE/de at zero strain.  Arguments beyond those of pamnet_md_step_f32:
+ *   dstrain [n_graphs, 9] fp32: W;  cell0 [n_graphs, 9] fp32, read only;  cell [n_graphs, 9] fp32, written: the cell of the new
+ *   geometry;  eps [n_graphs] fp64: state (the caller starts with 0);  cell_dof [n_graphs] uint8 or NULL: 0 = the graph has no
+ *   barostat, NULL = every graph has one;  pint, vol [n_graphs] fp64 (outputs beside ke);  pressure_g, rate_g [n_graphs] fp64
+ *   or NULL: NULL means the scalar pressure P0 / rate holds for every graph (the scalar beside a given array is not looked
+ *   at).  rate = beta_T / tau_p, the isothermal compressibility over the coupling time, positive (in an array: the caller's
+ *   to keep so).  Units are the caller's: pressure in energy / length^3.
+ * The step of graph g with cell_dof[g] != 0; "free" = the atoms of g that are not fixed, f = -dpos:
+ *   1. status[g] != 0: nothing that belongs to g is read-modified or written.
+ *   2. v_n = v + kick_in (dt / 2) f / m.
+ *   3. F2 = sum |f|^2 and KE = 1/2 sum m |v_n|^2 over the free atoms, in the fixed order of pamnet_md_step_f32;
+ *      trW = (W00 + W11) + W22;  V = |det cell0[g]| exp(eps[g]);  P_int = (2 KE - trW) / (3 V).
+ *      ke[g] = KE, pint[g] = P_int, vol[g] = V: they belong to pos, also when advance == 0.
+ *      F2, KE, trW or V not finite, or V == 0: status[g] = 2, nothing else of g is written.
+ *   4. d = -rate (P0 - P_int) dt + sqrt(2 kT rate dt / V) xi_c, the change of eps.  xi_c is the first normal of THE GENERATOR
+ *      above at counter (0, steps[g], 2, 0) under the graph's key: stream 2 is the barostat's (0: the thermostat, 1: the
+ *      initial velocities).  Where kT == 0 the noise term is exactly 0 and the generator is not run.  d is formed from the sums
+ *      of step 3 alone, before any store.  d not finite: status[g] = 2, nothing else of g is written.
+ *      advance == 0: vel <- fp32(v_n); eps, cell, pos and steps[g] stay.  Done.
+ *   5. v1, v2 and the thermostat noise exactly as step 5 of pamnet_md_step_f32.  With s = exp(d / 3):
+ *      a free atom:  pos <- fp32(s (pos + (dt / 2) (v1 + v2))),  vel <- fp32(v2 / s);
+ *      a fixed atom: pos <- fp32(s pos): it keeps its fractional coordinates, as under pamnet_fire_cell_step_f32; its row of vel
+ *      is neither read nor written.
+ *      eps[g] += d;  cell[g] = fp32(cell0[g] exp(eps_new / 3)), always from cell0: the cell accumulates no fp32 rounding.
+ *   6. steps[g] += 1.
+ * The pressure of step n (at x_n, v_n) scales the geometry that step n produces, so the next evaluation sees positions and a
+ * cell that belong together and forces are never used on a geometry they were not computed for.  The drift of eps has no
+ * kT / V term: in eps = ln V the diffusion coefficient is kT beta_T / (V tau_p), and its eps-derivative cancels against the
+ * Jacobian V of the eps-measure.
+ * A graph with cell_dof[g] == 0 takes the rule of pamnet_md_step_f32 exactly: its pos, vel, ke, steps and status are bitwise
+ * what that entry point gives; its eps, cell, pint and vol are not written; its dstrain, cell0, pressure and rate are not read.
+ * Arithmetic, order of the sums and form as pamnet_md_step_f32; the determinant, d and s are formed by every thread of the
+ * graph's workgroup alike.  No atomics: the outputs of a graph are bitwise repeatable and the same alone or inside any batch.
+ * Returns PAMNET_EINVAL as pamnet_md_step_f32, and, where the per-graph array is NULL, for a scalar pressure that is not finite
+ * or a scalar rate that is not positive and finite; PAMNET_ENULL for a null required pointer: mass, fixed, cell_dof and the
+ * five _g arrays may be NULL, and seed only where neither thermostat nor barostat noise can occur (gamma_g and kT_g NULL,
+ * gamma == 0 and kT == 0).  n_graphs == 0 launches nothing.  (Part of ABI 18: nothing existing changed.)
+ * ------------------------------------------------------------------------------------------------------------------ */
+int pamnet_md_npt_step_f32(float* pos, float* vel, const float* dpos, const float* dstrain, const float* mass,
+                           const uint8_t* fixed, const int32_t* gptr, int64_t n, int64_t n_graphs, const float* cell0,
+                           float* cell, double* eps, const uint8_t* cell_dof, const int64_t* seed, int32_t* steps,
+                           int32_t* status, double* ke, double* pint, double* vol, const double* dt_g, const double* kT_g,
+                           const double* gamma_g, const double* pressure_g, const double* rate_g, double dt, double kT,
+                           double gamma, double pressure, double rate, int32_t kick_in, int32_t advance,
+                           pamnet_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Attention fusion + per-graph pooling  (models.py:206-224)
  * outs/atts: [2L, n] rows ordered (global_0, local_0, global_1, local_1, ...).
  *   node_out[n] = sign[n] * sum_l sum_c outs[l,c,n] * softmax_c(leaky_relu(atts[l,c,n], 0.2))

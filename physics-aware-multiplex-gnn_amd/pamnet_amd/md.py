@@ -9,22 +9,33 @@ include/pamnet_hip.h states the rule and the generator).  The noise is counter-b
 counted by the atom's offset in its graph and the graph's step -- so a structure's trajectory does not depend on its batch-mates
 and is bitwise repeatable.  The loop takes no decision on the host.  There is no CPU path.
 
+    from pamnet_amd.md import run_npt
+    res = run_npt(model, data, steps=1000, dt=0.1, kT=0.025, pressure=6.2415e-7, tau_p=50.0, compressibility=8.0, gamma=0.1)
+
+is the same dynamics at constant pressure (isotropic NPT): the stochastic cell rescaling barostat (Bernetti & Bussi, J. Chem.
+Phys. 153, 114107, 2020) fused into the step launch (csrc/md_npt.hip pamnet_md_npt_step_f32), under the same guarantees.
+
 Units are the caller's: with energies in eV, lengths in Angstrom and masses in amu the time unit is 10.1805 fs (dt = 0.1 is about
-1 fs), and kT is in eV."""
+1 fs), kT is in eV and a pressure in eV / A^3 (160.2177 GPa; 1 bar = 6.2415e-7)."""
 import torch
 
 from . import graph as G
 from . import lib
-from .relax import _checked, _evaluate
+from .relax import _cell_dof, _checked, _det3, _evaluate, _evaluate_cell
 
 STATE = ('seed', 'steps', 'status', 'ke')
+NPT_STATE = STATE + ('eps', 'pint', 'vol')         # per-graph scalars of the constant-pressure step (cell travels beside them)
 RUNNING, FAILED = 0, 2
 
 
 class MDResult(object):
     """pos, vel [N, 3] fp32 (new tensors), energy [G] and forces [N, 3] of one evaluation at `pos`, kinetic [G] fp64 (of `vel`),
     steps int32 [G] (the steps a graph moved), failed bool [G], frames [F, N, 3] fp32 / epot, ekin [F, G] fp64 (record_every > 0,
-    else None), trace (trace=True: one dict per launch, else None).  All on the device."""
+    else None), trace (trace=True: one dict per launch, else None).  All on the device.
+    run_npt adds: cell [G, 3, 3] fp32 (a new tensor), eps [G] fp64 (ln of the volume over the starting volume), volume and pressure
+    [G] fp64 (the kernel's V and P_int = (2 KE - tr W) / (3 V) of `pos`, `vel` and `cell`; a graph without a barostat keeps
+    |det cell| and NaN), virial [G, 3, 3] fp32 (W = dE/d strain) and stress = W / volume of the same evaluation; with record_every
+    cells [F, G, 3, 3] fp32 and volumes, pressures [F, G] fp64."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -72,6 +83,31 @@ def init_velocities(vel, gptr, seed, kT, ke, mass=None, fixed=None, remove_com=T
              gptr.numel() - 1, lib.ptr(seed), kT_g, kT, int(bool(remove_com)), int(bool(rescale)), lib.ptr(ke), lib.stream_of(vel))
 
 
+def new_npt_state(n, n_graphs, device, cell0, seed=0):
+    """(vel, state) of new_state plus eps (fp64 zeros), pint (fp64 NaN) and vol (fp64 |det cell0|), each [n_graphs]: the state of
+    pamnet_md_npt_step_f32.  cell0: fp32 [n_graphs, 3, 3]."""
+    vel, state = new_state(n, n_graphs, device, seed)
+    state['eps'] = torch.zeros(n_graphs, dtype=torch.float64, device=device)
+    state['pint'] = torch.full((n_graphs,), float('nan'), dtype=torch.float64, device=device)
+    state['vol'] = _det3(cell0.to(torch.float64)).abs().contiguous()
+    return vel, state
+
+
+def npt_step(pos, vel, dpos, dstrain, gptr, cell0, cell, state, dt, kT, pressure, rate, gamma=0.0, mass=None, fixed=None,
+             cell_dof=None, kick_in=1, advance=1):
+    """One launch of pamnet_md_npt_step_f32, in place on pos, vel, cell and state (no synchronisation).  Beyond md_step: dstrain
+    (the virial), cell0 (read only), cell: fp32 [n_graphs, 3, 3]; state: new_npt_state's; pressure, rate: a float, or fp64
+    [n_graphs]; cell_dof: uint8 / bool [n_graphs] or None (every graph has a barostat; a graph with 0 takes the step of md_step).
+    state['seed'] may be None where gamma and kT are the float 0."""
+    (dt_g, dt), (kT_g, kT), (gamma_g, gamma) = _split(dt), _split(kT), _split(gamma)
+    (p_g, pressure), (rate_g, rate) = _split(pressure), _split(rate)
+    lib.call('pamnet_md_npt_step_f32', lib.ptr(pos), lib.ptr(vel), lib.ptr(dpos), lib.ptr(dstrain), lib.ptr(mass), lib.ptr(fixed),
+             lib.ptr(gptr), pos.size(0), gptr.numel() - 1, lib.ptr(cell0), lib.ptr(cell), lib.ptr(state['eps']), lib.ptr(cell_dof),
+             lib.ptr(state['seed']), lib.ptr(state['steps']), lib.ptr(state['status']), lib.ptr(state['ke']),
+             lib.ptr(state['pint']), lib.ptr(state['vol']), dt_g, kT_g, gamma_g, p_g, rate_g, dt, kT, gamma, pressure, rate,
+             int(kick_in), int(advance), lib.stream_of(pos))
+
+
 def temperature(ekin, n_free, remove_com=True):
     """kT = 2 KE / dof with dof = 3 n_free - 3 (remove_com); floats, arrays or tensors, per graph."""
     return 2.0 * ekin / (3 * n_free - (3 if remove_com else 0))
@@ -79,17 +115,23 @@ def temperature(ekin, n_free, remove_com=True):
 
 def _per_graph(name, v, n_graphs, device, positive):
     """A float, or an fp64 tensor [num_graphs] on the device of pos -> (the value to hand on, its validity as a 0-dim device bool
-    or None).  A float is checked here."""
+    or None).  A float is checked here.  positive: True (> 0), False (>= 0) or None (any finite value)."""
     if isinstance(v, torch.Tensor):
         if v.dtype != torch.float64 or tuple(v.shape) != (n_graphs,) or v.device != device:
             raise ValueError('a per-graph `%s` is a float64 tensor [num_graphs] = [%d] on the device of `pos`; got %s %s on %s'
                              % (name, n_graphs, v.dtype, tuple(v.shape), v.device))
         v = v.contiguous()
+        if positive is None:
+            return v, torch.isfinite(v).all()
         return v, (torch.isfinite(v) & ((v > 0) if positive else (v >= 0))).all()
     try:
         v = float(v)
     except (TypeError, ValueError):
         raise ValueError('`%s` is a float, or a float64 tensor [num_graphs] on the device of `pos`; got %r' % (name, type(v)))
+    if positive is None:
+        if v != v or v in (float('inf'), float('-inf')):
+            raise ValueError('`%s` must be finite; got %r' % (name, v))
+        return v, None
     if not ((v > 0.0 if positive else v >= 0.0) and v != float('inf')):
         raise ValueError('`%s` must be %s and finite; got %r' % (name, 'positive' if positive else 'non-negative', v))
     return v, None
@@ -201,3 +243,143 @@ def run(model, data, steps, dt, masses=None, kT=None, gamma=0.0, seed=0, fixed=N
     energy, de = launch(done, 1 if done else 0, 0)  # one more evaluation: energy, forces, vel and ke belong to the final geometry
     return MDResult(pos=cur, vel=vel, energy=energy, kinetic=state['ke'], forces=-de, steps=state['steps'],
                     failed=state['status'] == FAILED, frames=frames, epot=epot, ekin=ekin, trace=log)
+
+
+def run_npt(model, data, steps, dt, kT, pressure, tau_p, compressibility, masses=None, gamma=0.0, seed=0, fixed=None,
+            velocities=None, remove_com=True, cell_dof=None, record_every=0, check_every=0, trace=False):
+    """Move every graph of a periodic batch for `steps` steps of length `dt` at the temperature kT and the pressure `pressure`:
+    the BAOAB step of run() with the isotropic stochastic cell rescaling barostat (Bernetti & Bussi 2020) in the same launch
+    (include/pamnet_hip.h states the rule).  One model evaluation -- with `strain` attached, for the virial -- and one launch per
+    step; no decision on the host.
+
+    model:  as for run(), and differentiable with respect to `data.strain` as well, as for relax_cell(): PAMNet / PAMNet_s on
+            periodic batches, or a plain torch module that applies (I + data.strain[g]) to the positions and the cell of graph g.
+            The graph build's own conditions on the cell heights apply to every evaluation; the driver adds none.
+    data:   the batch, with `data.cell` fp32 [G, 3, 3] (row k = lattice vector a_k); neither `data.pos` nor `data.cell` is written.
+    dt, kT, gamma, masses, seed, fixed, velocities, remove_com, record_every, check_every: as for run().  kT is required: it
+            sets the barostat's noise.  kT = 0 gives a deterministic relaxation of the volume towards `pressure`.  A fixed atom
+            of a graph with a barostat keeps its fractional coordinates: it follows the cell.
+    pressure: P0, a float or fp64 [G] on the device, finite, in the caller's energy / length^3 (with eV and Angstrom:
+            160.2177 GPa; 1 bar = 6.2415e-7).
+    tau_p, compressibility: the coupling time and the isothermal compressibility beta_T (1 / pressure), floats or fp64 [G] on the
+            device, positive.  Only rate = compressibility / tau_p enters the rule; the explicit update wants
+            rate x bulk modulus x dt well below 1.
+    cell_dof: bool [G] on the device: False = the graph has no barostat and takes exactly the step of run().  None: a graph has
+            one where all three axes of `data.pbc` are periodic (everywhere where the batch has no `pbc`).  True on a graph with
+            an open axis is refused.
+    trace:  as for run(); a record also holds W and cell, and the states hold eps, pint and vol; cell_after beside pos_after.
+
+    The launch sequence and the records are those of run(): res.vel, res.kinetic, res.pressure, res.volume, res.energy,
+    res.forces, res.virial and res.stress all belong to res.pos and res.cell.  With record_every, res.cells, res.volumes and
+    res.pressures are recorded beside frames, epot and ekin."""
+    try:
+        pos, batch, n_graphs, _, fixed8 = _checked(model, data, 0.0, fixed)
+    except ValueError as e:
+        raise ValueError('md.run_npt takes what relax() takes: %s' % (e,)) from None
+    device, n = pos.device, pos.size(0)
+    cell_in = getattr(data, 'cell', None)
+    if cell_in is None:
+        raise ValueError('run_npt needs `data.cell` (fp32 [num_graphs, 3, 3], row k = lattice vector a_k): the batch has no `cell`, '
+                         'and a structure in open space has no volume to couple to a pressure; run() moves it at fixed shape')
+    if (not isinstance(cell_in, torch.Tensor) or cell_in.dtype != torch.float32 or tuple(cell_in.shape) != (n_graphs, 3, 3)
+            or cell_in.device != device):
+        raise ValueError('`data.cell` is a float32 tensor [num_graphs, 3, 3] = [%d, 3, 3] on the device of `pos`; got %s'
+                         % (n_graphs, '%s %s on %s' % (cell_in.dtype, tuple(cell_in.shape), cell_in.device)
+                            if isinstance(cell_in, torch.Tensor) else type(cell_in)))
+    steps, record_every, check_every = int(steps), int(record_every), int(check_every)
+    if steps < 0 or record_every < 0 or check_every < 0:
+        raise ValueError('`steps`, `record_every` and `check_every` are non-negative; got %d, %d, %d'
+                         % (steps, record_every, check_every))
+    if kT is None:
+        raise ValueError('constant-pressure dynamics needs its temperature: pass `kT` (it sets the noise of the barostat; kT = 0 '
+                         'relaxes the volume without noise)')
+    checks = {}
+    dt, checks['dt'] = _per_graph('dt', dt, n_graphs, device, True)
+    gamma, checks['gamma'] = _per_graph('gamma', gamma, n_graphs, device, False)
+    kT, checks['kT'] = _per_graph('kT', kT, n_graphs, device, False)
+    pressure, checks['pressure'] = _per_graph('pressure', pressure, n_graphs, device, None)
+    tau_p, checks['tau_p'] = _per_graph('tau_p', tau_p, n_graphs, device, True)
+    compressibility, checks['compressibility'] = _per_graph('compressibility', compressibility, n_graphs, device, True)
+    rate = compressibility / tau_p                # (a float, or fp64 [G] on the device)
+    if isinstance(rate, torch.Tensor):
+        rate = rate.contiguous()
+    elif not (rate > 0.0 and rate != float('inf')):
+        raise ValueError('`compressibility` / `tau_p` must be positive and finite; got %r' % (rate,))
+    if masses is not None:
+        if (not isinstance(masses, torch.Tensor) or masses.dtype != torch.float32 or tuple(masses.shape) != (n,)
+                or masses.device != device):
+            raise ValueError('`masses` is a float32 tensor [N] = [%d] on the device of `pos`; got %s'
+                             % (n, '%s %s on %s' % (masses.dtype, tuple(masses.shape), masses.device)
+                                if isinstance(masses, torch.Tensor) else type(masses)))
+        masses = masses.contiguous()
+        checks['masses'] = (torch.isfinite(masses) & (masses > 0)).all()
+    if velocities is not None and (not isinstance(velocities, torch.Tensor) or velocities.dtype != torch.float32
+                                   or tuple(velocities.shape) != (n, 3) or velocities.device != device):
+        raise ValueError('`velocities` is a float32 tensor [N, 3] = [%d, 3] on the device of `pos`; got %s'
+                         % (n, '%s %s on %s' % (velocities.dtype, tuple(velocities.shape), velocities.device)
+                            if isinstance(velocities, torch.Tensor) else type(velocities)))
+    dof8 = _cell_dof(data, cell_dof, n_graphs, device, checks, 'has a barostat on')
+    cell0 = cell_in.detach().clone().contiguous()
+    cell = cell0.clone()
+    vel, state = new_npt_state(n, n_graphs, device, cell0, seed)
+    names = [k for k, v in checks.items() if v is not None]
+    if names:                                     # (as run: one read at set-up, for every tensor of values at once)
+        ok = torch.stack([checks[k] for k in names]).tolist()
+        bad = [k for k, good in zip(names, ok) if not good]
+        if 'cell_dof' in bad:
+            raise ValueError('`cell_dof` is True on a graph with an open axis (`data.pbc`): a cell with an open axis has no volume '
+                             'to couple to a pressure; leave that graph False, or run the structure as fully periodic')
+        if bad:
+            raise ValueError('%s must be finite and positive (kT, gamma: non-negative; pressure: any sign) in every entry'
+                             % ' and '.join('`%s`' % k for k in bad))
+    cur = pos.detach().to(torch.float32).clone().contiguous()
+    gptr, _ = G.csr_from_keys(batch.to(torch.int32).contiguous(), n_graphs)
+    if velocities is not None:
+        vel = velocities.detach().clone().contiguous()
+    else:
+        init_velocities(vel, gptr, state['seed'], kT, state['ke'], masses, fixed8, remove_com=remove_com)
+    frames = epot = ekin = cells = volumes = pressures = None
+    if record_every:
+        n_rec = steps // record_every + 1
+        f64 = dict(dtype=torch.float64, device=device)
+        frames = torch.zeros(n_rec, n, 3, dtype=torch.float32, device=device)
+        cells = torch.zeros(n_rec, n_graphs, 3, 3, dtype=torch.float32, device=device)
+        epot, ekin = torch.zeros(n_rec, n_graphs, **f64), torch.zeros(n_rec, n_graphs, **f64)
+        volumes, pressures = torch.zeros(n_rec, n_graphs, **f64), torch.zeros(n_rec, n_graphs, **f64)
+    log = [] if trace else None
+    snap = lambda: {k: state[k].clone() for k in NPT_STATE}
+
+    def launch(it, kick_in, advance):
+        """Evaluate at cur and cell, then one launch; step `it` is recorded at its full step: cur and cell before the launch, ke,
+        pint and vol (which the launch forms for that geometry) after it."""
+        e, de, w = _evaluate_cell(model, data, cur, cell)
+        rec = record_every and it % record_every == 0
+        if rec:
+            frames[it // record_every].copy_(cur)
+            cells[it // record_every].copy_(cell)
+            epot[it // record_every].copy_(e.reshape(-1))
+        if trace:
+            t = dict(pos=cur.clone(), dE=de.clone(), W=w.clone(), cell=cell.clone(), v_before=vel.clone(), kick_in=kick_in,
+                     advance=advance, state_before=snap())
+        npt_step(cur, vel, de, w, gptr, cell0, cell, state, dt, kT, pressure, rate, gamma, masses, fixed8, dof8, kick_in, advance)
+        if rec:
+            ekin[it // record_every].copy_(state['ke'])
+            volumes[it // record_every].copy_(state['vol'])
+            pressures[it // record_every].copy_(state['pint'])
+        if trace:
+            t.update(pos_after=cur.clone(), v_after=vel.clone(), cell_after=cell.clone(), state_after=snap())
+            log.append(t)
+        return e, de, w
+
+    done = 0
+    for it in range(steps):
+        launch(it, 1 if it else 0, 1)
+        done = it + 1
+        if check_every and done % check_every == 0 and not bool((state['status'] == RUNNING).any()):
+            break
+    energy, de, w = launch(done, 1 if done else 0, 0)   # one more evaluation: everything belongs to the final geometry
+    volume = state['vol']
+    return MDResult(pos=cur, vel=vel, cell=cell, eps=state['eps'], energy=energy, kinetic=state['ke'], forces=-de, virial=w,
+                    stress=(w.to(torch.float64) / volume[:, None, None]).to(torch.float32), volume=volume, pressure=state['pint'],
+                    steps=state['steps'], failed=state['status'] == FAILED, frames=frames, epot=epot, ekin=ekin, cells=cells,
+                    volumes=volumes, pressures=pressures, trace=log)

@@ -237,6 +237,41 @@ def _evaluate_cell(model, data, cur, cell):
     return e.detach(), de.contiguous(), w.contiguous()
 
 
+def _cell_dof(data, cell_dof, n_graphs, device, checks, verb):
+    """The per-graph cell switch of relax_cell and md.run_npt as uint8 [num_graphs], or None where every graph moves its cell.
+    cell_dof None: a graph moves its cell where all three axes of `data.pbc` are periodic.  A given mask is checked against
+    `data.pbc` on the device: its validity goes into checks['cell_dof'] for the caller's one read at set-up (False: True on a
+    graph with an open axis, which the caller refuses).  verb: what the graph does with its cell, for the message."""
+    pbc = getattr(data, 'pbc', None)
+    if isinstance(pbc, torch.Tensor):
+        if pbc.dtype != torch.bool or tuple(pbc.shape) != (n_graphs, 3) or pbc.device != device:
+            raise ValueError('`data.pbc` is a torch.bool tensor [num_graphs, 3] = [%d, 3] on the device of `pos`, or a tuple of '
+                             'three bools; got %s %s on %s' % (n_graphs, pbc.dtype, tuple(pbc.shape), pbc.device))
+        periodic = pbc.all(1)
+    elif pbc is None:
+        periodic = None
+    else:
+        try:
+            periodic = all(bool(v) for v in pbc) and len(pbc) == 3
+        except TypeError:
+            raise ValueError('`data.pbc` is a torch.bool tensor [num_graphs, 3] or a tuple of three bools; got %r' % (pbc,))
+    if cell_dof is None:
+        dof8 = None if periodic is None or periodic is True else (
+            periodic.to(torch.uint8) if isinstance(periodic, torch.Tensor) else torch.zeros(n_graphs, dtype=torch.uint8, device=device))
+    else:
+        if (not isinstance(cell_dof, torch.Tensor) or cell_dof.dtype != torch.bool or tuple(cell_dof.shape) != (n_graphs,)
+                or cell_dof.device != device):
+            raise ValueError('`cell_dof` is a torch.bool tensor [num_graphs] = [%d] on the device of `pos` (True: the graph %s '
+                             'its cell); got %s' % (n_graphs, verb, '%s %s on %s' % (cell_dof.dtype, tuple(cell_dof.shape), cell_dof.device)
+                                                    if isinstance(cell_dof, torch.Tensor) else type(cell_dof)))
+        if isinstance(periodic, torch.Tensor):
+            checks['cell_dof'] = ~(cell_dof & ~periodic).any()
+        elif periodic is False:
+            checks['cell_dof'] = ~cell_dof.any()
+        dof8 = cell_dof.to(torch.uint8).contiguous()
+    return dof8
+
+
 def relax_cell(model, data, fmax=0.05, smax=0.005, pressure=0.0, hydrostatic=False, cell_dof=None, cell_factor=None, fixed=None,
                max_steps=200, check_every=10, trace=False, **fire_params):
     """Relax the atoms and the cell of every graph of a periodic batch until its largest force on a free atom is below `fmax` and
@@ -301,33 +336,7 @@ def relax_cell(model, data, fmax=0.05, smax=0.005, pressure=0.0, hydrostatic=Fal
         else:
             factor = torch.full((n_graphs,), factor, dtype=torch.float64, device=device)
     factor = factor.contiguous()
-    pbc = getattr(data, 'pbc', None)
-    if isinstance(pbc, torch.Tensor):
-        if pbc.dtype != torch.bool or tuple(pbc.shape) != (n_graphs, 3) or pbc.device != device:
-            raise ValueError('`data.pbc` is a torch.bool tensor [num_graphs, 3] = [%d, 3] on the device of `pos`, or a tuple of '
-                             'three bools; got %s %s on %s' % (n_graphs, pbc.dtype, tuple(pbc.shape), pbc.device))
-        periodic = pbc.all(1)
-    elif pbc is None:
-        periodic = None
-    else:
-        try:
-            periodic = all(bool(v) for v in pbc) and len(pbc) == 3
-        except TypeError:
-            raise ValueError('`data.pbc` is a torch.bool tensor [num_graphs, 3] or a tuple of three bools; got %r' % (pbc,))
-    if cell_dof is None:
-        dof8 = None if periodic is None or periodic is True else (
-            periodic.to(torch.uint8) if isinstance(periodic, torch.Tensor) else torch.zeros(n_graphs, dtype=torch.uint8, device=device))
-    else:
-        if (not isinstance(cell_dof, torch.Tensor) or cell_dof.dtype != torch.bool or tuple(cell_dof.shape) != (n_graphs,)
-                or cell_dof.device != device):
-            raise ValueError('`cell_dof` is a torch.bool tensor [num_graphs] = [%d] on the device of `pos` (True: the graph relaxes '
-                             'its cell); got %s' % (n_graphs, '%s %s on %s' % (cell_dof.dtype, tuple(cell_dof.shape), cell_dof.device)
-                                                    if isinstance(cell_dof, torch.Tensor) else type(cell_dof)))
-        if isinstance(periodic, torch.Tensor):
-            checks['cell_dof'] = ~(cell_dof & ~periodic).any()
-        elif periodic is False:
-            checks['cell_dof'] = ~cell_dof.any()
-        dof8 = cell_dof.to(torch.uint8).contiguous()
+    dof8 = _cell_dof(data, cell_dof, n_graphs, device, checks, 'relaxes')
     names = list(checks)
     if names:                                     # (as md.run: one read at set-up, for every tensor of values at once)
         ok = torch.stack([checks[k] for k in names]).tolist()
