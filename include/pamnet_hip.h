@@ -646,6 +646,53 @@ int pamnet_fire_cell_step_f32(float* pos, float* vel, const float* dpos, const f
                               int32_t n_min, double f_inc, double f_dec, double a0, double f_a, pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Nudged elastic band: the projected force of every image of every band of a batch, in one launch (csrc/neb.hip; the
+ * reference has no path method).  Improved tangent: Henkelman & Jonsson, J. Chem. Phys. 113, 9978 (2000); climbing image:
+ * Henkelman, Uberuaga & Jonsson, J. Chem. Phys. 113, 9901 (2000).  An image is a graph; a band is a run of consecutive graphs.
+ *   pos, dpos [n, 3] fp32: positions (unwrapped: the entry point takes no cell) and dE/dpos, F = -dpos;  energy [n_graphs]
+ *   fp32;  fixed [n] uint8 or NULL;  gptr [n_graphs + 1]: first atom of every graph (kept inside [0, n]);  band_ptr
+ *   [n_bands + 1]: band b is the graphs band_ptr[b] .. band_ptr[b + 1] - 1 (kept inside [0, n_graphs));  band_of [n_graphs]:
+ *   the band of every graph (a graph whose entry is outside [0, n_bands) is left alone);  band_status [n_bands] int32 or NULL:
+ *   nonzero = nothing that belongs to an image of the band is written (the status vector of pamnet_fire_step_f32 over the
+ *   bands);  climb [n_bands] uint8 or NULL: nonzero = the band has a climbing image;  k_b [n_bands] fp64 or NULL: the spring
+ *   constant of every band; NULL: k for all (the scalar beside a given array is not looked at).
+ *   Outputs: dneb [n, 3] fp32 = -F_neb, in the sign convention of dpos, so that it feeds pamnet_fire_step_f32 unchanged (it
+ *   must not alias dpos);  seg [n_graphs] fp64 or NULL: |d-|, the distance to the previous image of the band, 0 on a band's
+ *   first image;  fpar [n_graphs] fp64 or NULL: F . t^, 0 on a band's first and last image.
+ * The rule of image i = graph g of band b.  Its neighbours -/+ are the graphs g - 1 / g + 1, atoms matched by their offset
+ * inside the graph.  An atom of g is free where fixed[a] == 0 (the image's own row decides).  All sums run over the free atoms
+ * of g; the rows of pos and dpos of a fixed atom, and the neighbours' rows at its offset, are never read; its row of dneb is 0.
+ *   1. The first and the last image of a band write 0 to all their rows of dneb.  (A band of one or two images is all
+ *      endpoints.)  The last image still reports seg.
+ *   2. An interior image whose atom count differs from either neighbour's: every free row of dneb is NaN, fpar = seg = NaN.  On
+ *      a band's last image seg is NaN where the count differs from the previous image's.
+ *   3. d+ = R_{i+1} - R_i, d- = R_i - R_{i-1}.  The six sums Spp = |d+|^2, Smm = |d-|^2, Spm = d+ . d-, Fp = F . d+,
+ *      Fm = F . d-, F2 = |F|^2.  seg = sqrt(Smm).
+ *   4. E-, E0, E+ = the fp32 energies widened to fp64.  Any of them or any of the six sums not finite: every free row of dneb
+ *      is NaN and fpar = NaN (so that pamnet_fire_step_f32 fails the band).
+ *   5. The tangent t = cp d+ + cm d-:  E+ > E0 > E-: (cp, cm) = (1, 0).  E+ < E0 < E-: (0, 1).  Otherwise, with
+ *      hi = max(|E+ - E0|, |E- - E0|) and lo = the min of the two: E+ > E-: (hi, lo), else (lo, hi).
+ *      |t|^2 = cp^2 Spp + 2 cp cm Spm + cm^2 Smm and F . t = cp Fp + cm Fm.  |t|^2 > 0: t^ = t / |t| and fpar = F . t / |t|;
+ *      else t^ = 0 and fpar = 0: the image feels its plain force.
+ *   6. The climbing image of a band with climb[b] != 0 is its interior image of largest energy, found by scanning the interior
+ *      images upward with `>` from -infinity: a tie goes to the lowest index, a NaN or -infinity never climbs.  On it
+ *      F_neb = F - 2 fpar t^.
+ *   7. Every other interior image: F_neb = F - fpar t^ + k (sqrt(Spp) - sqrt(Smm)) t^.
+ * Arithmetic in fp64 from the fp32 inputs, one rounding at each store of dneb.  Sums in the fixed order of
+ * pamnet_fire_step_f32 (a thread's atoms ascending, wavefront butterfly, the wavefronts in order through LDS); every thread of
+ * the image's workgroup forms the decision and scans the band's energies itself; no atomics and nothing exchanged between
+ * workgroups: the outputs of a band are bitwise repeatable and bitwise the same alone or inside any batch.  One workgroup per
+ * image.
+ * Returns PAMNET_ENULL for a null required pointer (fixed, band_status, climb, k_b, seg and fpar may be NULL); PAMNET_EINVAL for
+ * a negative count, n_graphs or n_bands above 2^31 - 1, or, where k_b is NULL, a k that is negative or NaN.  n_graphs == 0
+ * launches nothing.  (Part of ABI 18: nothing existing changed.)
+ * ------------------------------------------------------------------------------------------------------------------ */
+int pamnet_neb_force_f32(const float* pos, const float* dpos, const float* energy, const uint8_t* fixed, const int32_t* gptr,
+                         int64_t n, int64_t n_graphs, const int32_t* band_ptr, const int32_t* band_of, int64_t n_bands,
+                         const int32_t* band_status, const uint8_t* climb, const double* k_b, double k, float* dneb,
+                         double* seg, double* fpar, pamnet_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Molecular dynamics: one step of every graph of a batch in one launch, and Maxwell-Boltzmann velocities (csrc/md.hip; the
  * reference has no integrator).  Each graph carries its own step counter, status and seed, and optionally its own time step,
  * temperature and friction, so its trajectory does not depend on what else the batch holds.  Units are the caller's.
