@@ -693,6 +693,79 @@ int pamnet_neb_force_f32(const float* pos, const float* dpos, const float* energ
                          double* seg, double* fpar, pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Vibrational analysis: mass-weighted Hessians by central differences of dE/dpos, and their eigenvalues and eigenvectors
+ * (csrc/vib.hip, csrc/eig.hip; the reference has neither second derivatives nor an eigensolver).  The model has no second
+ * derivatives, so the displaced copies of a structure are graphs of one batch and one evaluation differentiates many of them.
+ *
+ * THE LAYOUT, shared by the three entry points.  Graph g has F_g free atoms, their batch-wide atom indices ascending in
+ * free_idx[fptr[g] .. fptr[g + 1]) (both int32).  Its matrix has dimension d_g = 3 F_g and is stored row-major at moff[g] in a
+ * packed fp64 array; moff is int64 [n_graphs + 1], the prefix sum of d_g^2, and dptr is int64 [n_graphs + 1], the prefix sum of
+ * d_g.  Row and column 3 f + c is free atom f, component c.  Rows of fixed atoms do not exist.
+ * ONE EVALUATION handles `pairs` = r central-difference pairs per graph: the evaluated batch is 2 r copies of the original
+ * batch of n atoms and n_graphs graphs, copy-major: copy 2 c is the + and copy 2 c + 1 the - displacement of pair c; graph g
+ * of copy k is graph k n_graphs + g, its atoms start at k n + gptr[g].  In evaluation t, pair c of graph g has job
+ * j = t r + c: where j < 3 F_g it displaces component j % 3 of free atom f = j / 3, a = free_idx[fptr[g] + f]; otherwise the
+ * pair is idle.
+ *
+ * pamnet_vib_displace_f32: writes pos_out [2 r n, 3] fp32 in one launch.  Every copy is pos0 [n, 3], bit for bit, except the
+ * one displaced coordinate of an active pair: x+- = (float)((double)x0 +- delta).  Idle pairs are plain copies.  gptr
+ * [n_graphs + 1] int32: first atom of every graph (kept inside [0, n]; rows of pos_out that belong to no graph are not
+ * written).  One workgroup per (graph, copy); each element is stored once.
+ *
+ * pamnet_vib_rows_f64: reads dpos [2 r n, 3] fp32 (the evaluation's dE/dpos), pos0 and masses (fp32 [n], or NULL: unit
+ * masses), and for every active pair stores row 3 f + c of graph g's matrix in h, once:
+ *   h(3 f + c, 3 f' + c') = ((double)dE+[a', c'] - (double)dE-[a', c']) / ((double)x+ - (double)x-) / sqrt((double)m_a (double)m_a')
+ * with a' = free_idx[fptr[g] + f'], dE+- the rows of copies 2 c and 2 c + 1, and x+- recomputed exactly as by the displace
+ * launch: the divisor is the displacement as it was realised in fp32, not 2 delta.  Nothing is written for an idle pair.  No
+ * atomics, no accumulation: over the sweep t = 0 .. ceil(3 max F_g / r) - 1 every element of every matrix is stored exactly
+ * once.  An entry of free_idx outside [0, n) is not followed (its elements are NaN).  One workgroup per (graph, pair).
+ *
+ * Both return PAMNET_ENULL for a null required pointer (masses may be NULL); PAMNET_EINVAL for a negative n, n_graphs or t,
+ * n_graphs above 2^31 - 1, pairs < 1 or above 32767, or a delta that is not positive and finite.  n_graphs == 0 or n == 0
+ * launches nothing.
+ *
+ * pamnet_sym_eig_f64: eigenvalues and eigenvectors of n_mat packed symmetric matrices, one workgroup per matrix, by cyclic
+ * Jacobi in fp64.  a, v: packed fp64 of moff[n_mat] elements; w: fp64 of dptr[n_mat]; status, sweeps: int32 [n_mat].  For a
+ * matrix of dimension d (1 <= d <= 192):
+ *   Input.    A_pq <- (a_pq + a_qp) / 2 (finite-difference Hessians are not exactly symmetric; this is part of the rule); A0 is
+ *             this matrix.  V <- I.  a is the workspace: its contents are unspecified on return.
+ *   Schedule. m = d rounded up to even.  A sweep is the rounds rho = 0 .. m - 2; round rho holds the m / 2 disjoint pairs
+ *             (m - 1, rho) and ((rho + k) mod (m - 1), (rho - k) mod (m - 1)) for k = 1 .. m / 2 - 1, each ordered as p < q.  A
+ *             pair with q >= d is a bye.  Every pair p < q < d occurs exactly once per sweep.
+ *   Rotation. All rotations of a round are formed from the matrix as it stands at the start of the round, with a_pq the
+ *             element of the upper triangle.  a_pq == 0: no rotation.  Otherwise theta = (a_qq - a_pp) / (2 a_pq),
+ *             t = sign(theta) / (|theta| + sqrt(theta^2 + 1)) with sign(0) = +1, c = 1 / sqrt(t^2 + 1), s = t c.  First all
+ *             column updates, (a_rp, a_rq) <- (c a_rp - s a_rq, s a_rp + c a_rq) for every row r and every pair; then all row
+ *             updates, (a_pr, a_qr) <- (c a_pr - s a_qr, s a_pr + c a_qr) for every column r, after which a_pp = a_pp - t a_pq,
+ *             a_qq = a_qq + t a_pq (from the values at the start of the round) and a_pq = a_qp = 0 are set exactly.  The rows
+ *             p and q of V are rotated like the rows of A.
+ *   Stop.     After each sweep off = sqrt(sum_{p != q} a_pq^2); the solver stops when off <= tol |A0|_F or after max_sweeps
+ *             sweeps.  (So at least one sweep is taken; a diagonal matrix takes one without a rotation.)  Both sums are taken
+ *             in a fixed order -- a thread's elements ascending, the wavefront butterfly, the wavefronts in order through LDS --
+ *             and every thread of the workgroup reads the same number, so every exit is uniform.
+ *   Output.   w[dptr[g] ..] ascending: eigenvalue k of the final diagonal goes to the position that counts the entries below
+ *             it, ties by the diagonal index.  Row k of the matrix at v + moff[g] is the unit eigenvector of w[k]; its
+ *             component of largest magnitude is positive, the lowest index on a tie.  sweeps[g] = the sweeps taken.
+ *             status[g] = 0 converged; 1 max_sweeps reached (w and v are still written); 2 a non-finite entry in the input (w
+ *             and v of that matrix are NaN, sweeps[g] = 0); 3 d > 192 (nothing else of that matrix is written).  d <= 0: nothing
+ *             is written at all.  d = 1 is one sweep of one bye: w = a, v = 1.
+ * No atomics, nothing exchanged between workgroups, every element of a phase computed by one thread: the results of a matrix
+ * are bitwise repeatable and bitwise the same alone or inside any batch, at any position.  A and V are worked on in place in
+ * global memory (192^2 fp64 is 288 KiB, more than the 160 KiB of LDS), with workgroup barriers between the parameter, column
+ * and row phases of a round; the round's rotations go through LDS, and so does A itself where d <= 96 (72 KiB, reserved by every
+ * launch; the same arithmetic, the same bits).  192 = 3 x 64 is the 64-atom bound of the per-cell graph builder.
+ * Returns PAMNET_ENULL for a null pointer; PAMNET_EINVAL for n_mat negative or above 2^31 - 1, a tol that is negative or NaN,
+ * or max_sweeps < 1.  n_mat == 0 launches nothing.  (All three: part of ABI 18: nothing existing changed.)
+ * ------------------------------------------------------------------------------------------------------------------ */
+int pamnet_vib_displace_f32(const float* pos0, const int32_t* gptr, const int32_t* fptr, const int32_t* free_idx, int64_t n,
+                            int64_t n_graphs, int64_t pairs, int64_t t, double delta, float* pos_out, pamnet_stream_t stream);
+int pamnet_vib_rows_f64(const float* dpos, const float* pos0, const float* masses, const int32_t* fptr, const int32_t* free_idx,
+                        const int64_t* moff, int64_t n, int64_t n_graphs, int64_t pairs, int64_t t, double delta, double* h,
+                        pamnet_stream_t stream);
+int pamnet_sym_eig_f64(double* a, double* v, double* w, int32_t* status, int32_t* sweeps, const int64_t* moff,
+                       const int64_t* dptr, int64_t n_mat, double tol, int32_t max_sweeps, pamnet_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Molecular dynamics: one step of every graph of a batch in one launch, and Maxwell-Boltzmann velocities (csrc/md.hip; the
  * reference has no integrator).  Each graph carries its own step counter, status and seed, and optionally its own time step,
  * temperature and friction, so its trajectory does not depend on what else the batch holds.  Units are the caller's.
