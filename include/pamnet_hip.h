@@ -593,6 +593,56 @@ int pamnet_fire_step_f32(float* pos, float* vel, const float* dpos, const uint8_
                          double f_dec, double a0, double f_a, pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Structure relaxation, quasi-Newton: one limited-memory BFGS step (Nocedal, Math. Comp. 35, 773, 1980; the two-loop recursion
+ * with the scaled initial matrix gamma I of Liu and Nocedal, Math. Program. 45, 503, 1989; no line search) of every graph of
+ * a batch, in one launch (csrc/lbfgs.hip).  Every piece of optimiser state -- the history of pairs, its ring position, the
+ * curvature test, the scaling, the descent check and the step cap -- is per graph, so a graph's trajectory does not depend on
+ * what else the batch holds.
+ *   pos [n, 3] fp32, updated in place;  dpos [n, 3] fp32 = gr = dE/dpos;  fixed, gptr, fmax_tol_g / fmax_tol, status, steps, fmax:
+ *   as for pamnet_fire_step_f32.  An atom with fixed[a] != 0 enters no sum and no maximum, and its rows of pos, prev_pos,
+ *   prev_dpos, hist_s, hist_y and work are neither read nor written.
+ *   memory: m, the pairs a graph keeps, 1 .. 32, one value per launch (it is the leading extent of hist_s / hist_y and the row
+ *   length of rho, so it stays the same over a relaxation).
+ *   prev_pos, prev_dpos [n, 3] fp32: the positions and the gradient of the graph's last step.
+ *   hist_s, hist_y [m, n, 3] fp64: ring slot k of atom a is row k n + a.  work [n, 3] fp64: the vector of the two-loop
+ *   recursion (q, then z); its contents on return are unspecified.
+ *   Per graph: rho [n_graphs, m] fp64 (1 / y.s of the pair in each slot);  gamma [n_graphs] fp64;  head (the slot the next pair
+ *   goes to), count (the pairs held), has_prev, skipped, resets [n_graphs] int32.  The caller starts with all of them 0 (a
+ *   head outside [0, m) is taken modulo m and a count outside [0, m] clamped, so that no slot index leaves the arrays).
+ * The step of graph g, all sums and maxima over the free atoms of g, |.| of an atom the norm of its three components:
+ *   1. status[g] != 0: nothing that belongs to g is read-modified or written.
+ *   2. F2 = sum |gr|^2, fm = max |gr|; fmax[g] = fm.  F2 not finite: status[g] = 2 and fmax[g] = sqrt(F2) (NaN or +inf, as
+ *      pamnet_fire_step_f32 reports it), nothing else changes.  Else fm < tolerance: status[g] = 1, nothing else changes (a
+ *      graph without free atoms has fm = 0).
+ *   3. If has_prev[g]: s = pos - prev_pos and y = gr - prev_dpos, one fp64 subtraction per component from the fp32 operands;
+ *      ss = sum s.s, yy = sum y.y, ys = sum s.y.  If ys > skip_tol sqrt(ss yy): s and y are stored in slot head[g] of hist_s /
+ *      hist_y, rho[g][head] = 1 / ys, gamma[g] = ys / yy, head = (head + 1) mod m, count = min(count + 1, m).  Otherwise (a NaN
+ *      included) skipped[g] += 1 and the history stays as it is.  skipped is diagnostic only.
+ *   4. The two-loop recursion over the count pairs held, pair j = 0 .. count - 1 in slot (head - 1 - j) mod m (newest first):
+ *      q = gr;  for j = 0 .. count - 1: a_j = rho_j (s_j . q), q -= a_j y_j;  z = h0 q with h0 = gamma[g] if count > 0, else
+ *      1 / alpha;  for j = count - 1 .. 0 (oldest first): b = rho_j (y_j . z), z += (a_j - b) s_j.
+ *   5. D = sum z . gr.  If not D > 0 (a NaN included): the history is cleared, count = head = 0 (has_prev and gamma stay; gamma
+ *      is not read while count = 0), z = gr / alpha, resets[g] += 1, and the largest |z| is taken as fm / alpha.
+ *   6. L = max |z|, c = L > max_step ? max_step / L : 1;  prev_pos <- pos, prev_dpos <- gr, has_prev = 1;
+ *      pos <- (float)(pos - c z);  steps[g] += 1.
+ * The next step's s is the difference of the fp32 positions as they were stored: the history sees the move that was made,
+ * rounding and cap included.
+ * Arithmetic in fp64 from the fp32 inputs, one rounding to fp32 at the store of pos.  Sums in the fixed order of
+ * pamnet_fire_step_f32 (a thread's atoms ascending, wavefront butterfly, the wavefronts in order through LDS), no atomics, and an
+ * atom's rows of hist_s, hist_y and work are touched by one thread only: the outputs of a graph are bitwise repeatable and
+ * bitwise the same whether it is stepped alone or inside any batch.  One workgroup per graph, 2 count + 2 workgroup
+ * reductions.
+ * Returns PAMNET_ENULL for a null required pointer (fixed and fmax_tol_g may be null); PAMNET_EINVAL for a negative count,
+ * n_graphs above 2^31 - 1, memory outside 1 .. 32, a NaN fmax_tol, alpha or max_step not positive and finite, or skip_tol
+ * negative or not finite.  n_graphs == 0 launches nothing.  (Part of ABI 18: nothing existing changed.)
+ * ------------------------------------------------------------------------------------------------------------------ */
+int pamnet_lbfgs_step_f32(float* pos, const float* dpos, const uint8_t* fixed, const int32_t* gptr, int64_t n, int64_t n_graphs,
+                          float* prev_pos, float* prev_dpos, double* hist_s, double* hist_y, double* work, double* rho,
+                          double* gamma, int32_t* head, int32_t* count, int32_t* has_prev, int32_t* skipped, int32_t* resets,
+                          int32_t* steps, int32_t* status, float* fmax, const float* fmax_tol_g, double fmax_tol, int32_t memory,
+                          double alpha, double max_step, double skip_tol, pamnet_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Cell relaxation: one FIRE step over the atoms AND the cell of every graph of a batch, in one launch (csrc/relax_cell.hip).
  * The unit-cell-filter formulation (Tadmor et al., Phys. Rev. B 59, 235, 1999; ASE's UnitCellFilter, whose deformation gradient
  * is the transpose of this one) in the project's row-vector convention, pos -> pos (I + eps), cell -> cell (I + eps):

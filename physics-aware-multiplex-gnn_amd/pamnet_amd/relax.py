@@ -8,6 +8,12 @@ cap (csrc/relax.hip pamnet_fire_step_f32, one launch per step; include/pamnet_hi
 trajectory does not depend on its batch-mates, and it is bitwise repeatable.  The loop takes no decision on the host: the only
 device -> host read of the driver is the status vector, every `check_every` steps.  There is no CPU path.
 
+    from pamnet_amd.relax import relax_lbfgs
+    res = relax_lbfgs(model, data, fmax=0.05, max_steps=200, fixed=bottom_layer, memory=10)
+
+is the same loop with limited-memory BFGS steps (csrc/lbfgs.hip pamnet_lbfgs_step_f32): fewer evaluations per relaxation, every
+piece of optimiser state -- history, curvature test, scaling, descent check, cap -- per graph, under the same guarantees.
+
     from pamnet_amd.relax import relax_cell
     res = relax_cell(model, data, fmax=0.05, smax=0.005, pressure=0.0)
 
@@ -34,7 +40,9 @@ class RelaxResult(object):
     relax_cell adds: cell [G, 3, 3] fp32 (a new tensor), F [G, 3, 3] fp64 (cell = cell0 F), virial [G, 3, 3] fp32 (W = dE/d strain)
     and stress = W / volume of the same evaluation at `pos` and `cell`, volume [G] fp64 (|det cell|; a graph whose cell is
     singular, such as an open molecule's zero cell, has volume 0 and a non-finite stress), smax [G] fp32 (the largest
-    |S_ij| / volume of the graph's last step)."""
+    |S_ij| / volume of the graph's last step).
+    relax_lbfgs adds: skipped, resets int32 [G] (the pairs a graph refused for their curvature; the times it fell back to
+    steepest descent)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -170,6 +178,108 @@ def relax(model, data, fmax=0.05, max_steps=200, fixed=None, check_every=10, tra
     energy, de = _evaluate(model, data, cur)      # one more evaluation: energy and forces belong to the returned geometry
     return RelaxResult(pos=cur, energy=energy, forces=-de, converged=state['status'] == CONVERGED,
                        failed=state['status'] == FAILED, steps=state['steps'], fmax=state['fmax'], trace=steps_log)
+
+
+# ------------------------------------------------------------------------------------------------------------- L-BFGS
+LBFGS_DEFAULTS = dict(memory=10, alpha=70.0, max_step=0.2, skip_tol=1e-8)
+MAX_MEMORY = 32
+LBFGS_SCALARS = ('rho', 'gamma', 'head', 'count', 'has_prev', 'skipped', 'resets', 'steps', 'status', 'fmax')   # per graph
+LBFGS_ARRAYS = ('prev_pos', 'prev_dpos', 'hist_s', 'hist_y', 'work')                                            # per atom
+LBFGS_STATE = LBFGS_ARRAYS + LBFGS_SCALARS
+
+
+def _lbfgs_params(given):
+    """LBFGS_DEFAULTS with the caller's values; a name the rule does not have is a TypeError, a memory outside 1 .. 32 a
+    ValueError."""
+    unknown = sorted(set(given) - set(LBFGS_DEFAULTS))
+    if unknown:
+        raise TypeError('unknown L-BFGS parameter(s) %s: the rule has %s' % (', '.join(unknown), ', '.join(sorted(LBFGS_DEFAULTS))))
+    p = dict(LBFGS_DEFAULTS)
+    p.update(given)
+    m = p['memory']
+    if isinstance(m, bool) or int(m) != m or not 1 <= int(m) <= MAX_MEMORY:
+        raise ValueError('`memory` (the pairs every graph keeps) is an integer from 1 to %d; got %r' % (MAX_MEMORY, m))
+    p['memory'] = int(m)
+    return p
+
+
+def new_lbfgs_state(n, n_graphs, device, memory=LBFGS_DEFAULTS['memory']):
+    """The state of pamnet_lbfgs_step_f32, all zeros: prev_pos, prev_dpos (fp32 [n, 3]), hist_s, hist_y (fp64 [memory, n, 3]),
+    work (fp64 [n, 3]), rho (fp64 [n_graphs, memory]), gamma (fp64 [n_graphs]), head, count, has_prev, skipped, resets, steps,
+    status (int32 [n_graphs]) and fmax (fp32 [n_graphs]).  The memory is part of the state: its arrays are shaped by it."""
+    memory = _lbfgs_params(dict(memory=memory))['memory']
+    f32, f64, i32 = (dict(dtype=t, device=device) for t in (torch.float32, torch.float64, torch.int32))
+    state = dict(prev_pos=torch.zeros(n, 3, **f32), prev_dpos=torch.zeros(n, 3, **f32), hist_s=torch.zeros(memory, n, 3, **f64),
+                 hist_y=torch.zeros(memory, n, 3, **f64), work=torch.zeros(n, 3, **f64), rho=torch.zeros(n_graphs, memory, **f64),
+                 gamma=torch.zeros(n_graphs, **f64), fmax=torch.zeros(n_graphs, **f32))
+    for k in ('head', 'count', 'has_prev', 'skipped', 'resets', 'steps', 'status'):
+        state[k] = torch.zeros(n_graphs, **i32)
+    return state
+
+
+def lbfgs_step(pos, dpos, gptr, state, fmax_tol, fixed=None, **lbfgs_params):
+    """One L-BFGS step of every running graph, in place on pos and state (one launch, no synchronisation).  pos, dpos: fp32
+    [n, 3]; gptr: int32 [n_graphs + 1]; state: new_lbfgs_state's, whose history fixes the memory (a `memory` given here must be
+    that one); fixed: uint8 / bool [n] or None; fmax_tol: a float, or fp32 [n_graphs]."""
+    stream = lib.stream_of(pos)
+    memory = int(state['hist_s'].size(0))
+    if 'memory' in lbfgs_params and lbfgs_params['memory'] != memory:
+        raise ValueError('the state was made for memory = %d; got memory = %r' % (memory, lbfgs_params['memory']))
+    p = _lbfgs_params(dict(lbfgs_params, memory=memory))
+    n, n_graphs = pos.size(0), gptr.numel() - 1
+    if (tuple(state['hist_s'].shape) != (memory, n, 3) or tuple(state['hist_y'].shape) != (memory, n, 3)
+            or tuple(state['rho'].shape) != (n_graphs, memory)):
+        raise ValueError('the state does not belong to this batch: hist_s %s, hist_y %s, rho %s for n = %d, n_graphs = %d, '
+                         'memory = %d' % (tuple(state['hist_s'].shape), tuple(state['hist_y'].shape), tuple(state['rho'].shape), n,
+                                          n_graphs, memory))
+    tol_g, tol = _split(fmax_tol)
+    lib.call('pamnet_lbfgs_step_f32', lib.ptr(pos), lib.ptr(dpos), lib.ptr(fixed), lib.ptr(gptr), n, n_graphs,
+             lib.ptr(state['prev_pos']), lib.ptr(state['prev_dpos']), lib.ptr(state['hist_s']), lib.ptr(state['hist_y']),
+             lib.ptr(state['work']), lib.ptr(state['rho']), lib.ptr(state['gamma']), lib.ptr(state['head']),
+             lib.ptr(state['count']), lib.ptr(state['has_prev']), lib.ptr(state['skipped']), lib.ptr(state['resets']),
+             lib.ptr(state['steps']), lib.ptr(state['status']), lib.ptr(state['fmax']), tol_g, tol, memory, float(p['alpha']),
+             float(p['max_step']), float(p['skip_tol']), stream)
+
+
+def relax_lbfgs(model, data, fmax=0.05, max_steps=200, fixed=None, check_every=10, trace=False, **lbfgs_params):
+    """relax() with limited-memory BFGS steps in place of FIRE's (csrc/lbfgs.hip pamnet_lbfgs_step_f32, one launch per step;
+    include/pamnet_hip.h states the rule): the two-loop recursion over the last `memory` pairs (s, y) of every graph, the initial
+    matrix scaled by y.s / y.y, a pair kept only where its curvature is positive, steepest descent scaled by 1 / alpha on the
+    first step and wherever the direction is not a descent direction, and a cap on the largest displacement of an atom -- no
+    line search.  Every piece of that state is per graph, so a structure's trajectory does not depend on its batch-mates and
+    is bitwise repeatable; the price of a relaxation is its number of evaluations, which this lowers.
+
+    model, data, fmax, max_steps, fixed, check_every: as for relax().
+    trace:  keep, per step, clones of pos before and after the step, dE/dpos and the whole state (LBFGS_STATE, the history
+            included) before and after, in res.trace.
+    lbfgs_params: memory (1 .. 32), alpha, max_step, skip_tol (LBFGS_DEFAULTS).  alpha = 70 is ASE's value, a convention for eV
+            and Angstrom as fmax = 0.05 is: the first step moves an atom by its force / alpha.
+
+    Returns a RelaxResult with the fields of relax() and skipped / resets, int32 [G]: the pairs a graph refused for their
+    curvature and the times it fell back to steepest descent.  Converged and failed graphs stop moving but are still evaluated;
+    the only device -> host read is the status vector, every `check_every` steps (0: never).  One more evaluation at the end."""
+    p = _lbfgs_params(lbfgs_params)
+    pos, batch, n_graphs, tol, fixed8 = _checked(model, data, fmax, fixed)
+    kernel_params = {k: v for k, v in p.items() if k != 'memory'}
+    cur = pos.detach().to(torch.float32).clone().contiguous()
+    gptr, _ = G.csr_from_keys(batch.to(torch.int32).contiguous(), n_graphs)
+    state = new_lbfgs_state(cur.size(0), n_graphs, cur.device, p['memory'])
+    snap = lambda: {k: state[k].clone() for k in LBFGS_STATE}
+    steps_log = [] if trace else None
+    for it in range(int(max_steps)):
+        _, de = _evaluate(model, data, cur)
+        if trace:
+            rec = dict(pos=cur.clone(), dE=de.clone(), state_before=snap())
+        lbfgs_step(cur, de, gptr, state, tol, fixed8, **kernel_params)
+        if trace:
+            rec.update(pos_after=cur.clone(), state_after=snap())
+            steps_log.append(rec)
+        if check_every and (it + 1) % int(check_every) == 0 and not bool((state['status'] == RUNNING).any()):
+            break
+    energy, de = _evaluate(model, data, cur)      # one more evaluation: energy and forces belong to the returned geometry
+    return RelaxResult(pos=cur, energy=energy, forces=-de, converged=state['status'] == CONVERGED,
+                       failed=state['status'] == FAILED, steps=state['steps'], fmax=state['fmax'], skipped=state['skipped'],
+                       resets=state['resets'], trace=steps_log)
 
 
 # ----------------------------------------------------------------------------------------------------- cell relaxation
