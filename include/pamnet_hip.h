@@ -924,6 +924,65 @@ int pamnet_md_npt_step_f32(float* pos, float* vel, const float* dpos, const floa
                            pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Constrained molecular dynamics: the BAOAB step of pamnet_md_step_f32 under distance constraints |x_i - x_j| = d -- g-BAOAB
+ * (Leimkuhler & Matthews, Proc. R. Soc. A 472, 20160138, 2016) with one geodesic sub-step per half drift, SHAKE for the
+ * positions and RATTLE for the velocities (csrc/md_constraints.hip; the reference has no integrator).
+ * Arguments beyond those of pamnet_md_step_f32:
+ *   cons_i, cons_j [n_cons] int32: the two atom rows of a constraint, both inside one graph;  cons_d [n_cons] fp64: its length;
+ *   gcol [n_graphs + 1] int32, colptr [K + 1] int32: a two-level CSR -- graph g owns the colours gcol[g] .. gcol[g + 1], colour
+ *   k the constraints colptr[k] .. colptr[k + 1].  The constraints are sorted by (graph, colour), and no two constraints of a
+ *   colour share an atom (the caller colours them; pamnet_amd.md.Constraints does).  work [9 n] fp64: workspace (x0, x, v).
+ *   sweeps [n_graphs] int32, output: the most sweeps any solve of this launch took for the graph (0 without constraints).
+ *   tol: the convergence bound of both solves;  max_sweeps: the sweeps a solve may take.
+ * With w_a = 0 for a fixed atom and 1 / m_a otherwise, and a fixed atom's velocity taken as 0:
+ *   RATTLE_V:  a sweep visits the constraints in the order (colour, position): r = x_i - x_j, u = v_i - v_j,
+ *     err = |r.u| dt / d^2, kappa = r.u / ((w_i + w_j) r.r), v_i -= w_i kappa r, v_j += w_j kappa r.  The solve has converged
+ *     after the first sweep in which every err, measured as the sweep reaches the constraint, is <= tol.
+ *   SHAKE (x0: the positions before the drift):  s = x_i - x_j, r0 = x0_i - x0_j, err = |s.s - d^2| / (2 d^2),
+ *     g = (s.s - d^2) / (2 (w_i + w_j) (s.r0)), x_i -= w_i g r0, x_j += w_j g r0; converged as above.
+ *   A solve is broken by an err that is not finite, by s.r0 <= 0 and by a row outside the graph, and has failed after
+ *   max_sweeps sweeps without convergence.  A constraint with w_i + w_j == 0 is measured but not corrected.
+ * The step of a graph g with constraints, f = -dpos, sums over its free atoms in the order of pamnet_md_step_f32:
+ *   1. status[g] != 0: nothing that belongs to g is read-modified or written.
+ *   2. v = v + kick_in (dt / 2) f / m;  F2 = sum |f|^2, KE = 1/2 sum m |v|^2.  Either not finite: ke[g] = KE, status[g] = 2,
+ *      nothing else of g changes (sweeps[g] = 0).
+ *   3. kick_in: RATTLE_V, and KE = 1/2 sum m |v|^2 again.  ke[g] = KE (not finite: status[g] = 2).
+ *   4. advance == 0: vel <- fp32(v) if kick_in; done.
+ *   5. v += (dt / 2) f / m, RATTLE_V;   x0 = x, x += (dt / 2) v, SHAKE, v = (x - x0) / (dt / 2), RATTLE_V;
+ *      gamma > 0: v = c1 v + c2 sqrt(kT / m) xi with c1, c2 and xi exactly those of pamnet_md_step_f32, RATTLE_V;
+ *      the half drift with SHAKE and RATTLE_V once more.
+ *   6. pos <- fp32(x), vel <- fp32(v) for the free atoms; steps[g] += 1.
+ *   Any solve that fails: status[g] = 3, sweeps[g] is written, and pos, vel and steps of g stay bit for bit (ke[g] may hold
+ *   the KE of step 3).  Positions are never wrapped: differences are plain, a constrained pair sits in one image.
+ * A graph without constraints takes the rule of pamnet_md_step_f32 exactly: its pos, vel, ke, steps and status are bitwise
+ * what that entry point gives.  One workgroup per graph, every loop count uniform over it, fp64, fixed order, no atomics: the
+ * outputs of a graph are bitwise repeatable and the same alone or inside any batch.
+ *
+ * pamnet_md_project_constraints_f32: per graph g with status[g] == 0 and constraints, x = pos, v = vel (0 for a fixed atom):
+ *   do_pos: SHAKE with x0 = x (r0 is the current difference);  do_vel: RATTLE_V at the projected x with the graph's dt.
+ *   Then pos <- fp32(x) (do_pos) and vel <- fp32(v), ke[g] = 1/2 sum m |v|^2 (do_vel) for the free atoms; sweeps[g] as above.
+ *   A solve that fails: status[g] = 3, pos and vel stay.  A graph without constraints: ke[g] of vel as it stands (do_vel).
+ *
+ * Both return PAMNET_EINVAL as pamnet_md_step_f32 (the projection: dt only where do_vel), and for n_cons < 0, a tol that is
+ * not positive and finite, max_sweeps < 1 and a flag other than 0 / 1; PAMNET_ENULL for a null required pointer: sweeps always,
+ * cons_i, cons_j, cons_d, gcol, colptr and work where n_cons > 0 (with n_cons == 0 no graph has constraints and none of them
+ * is read); the projection needs vel and ke only where do_vel.  Rows inside cons_i / cons_j are the caller's to keep inside
+ * their graph.  (Part of ABI 18: nothing existing changed.)
+ * ------------------------------------------------------------------------------------------------------------------ */
+int pamnet_md_constrained_step_f32(float* pos, float* vel, const float* dpos, const float* mass, const uint8_t* fixed,
+                                   const int32_t* gptr, int64_t n, int64_t n_graphs, const int64_t* seed, int32_t* steps,
+                                   int32_t* status, double* ke, const double* dt_g, const double* kT_g, const double* gamma_g,
+                                   double dt, double kT, double gamma, int32_t kick_in, int32_t advance, const int32_t* cons_i,
+                                   const int32_t* cons_j, const double* cons_d, const int32_t* gcol, const int32_t* colptr,
+                                   int64_t n_cons, double* work, int32_t* sweeps, double tol, int32_t max_sweeps,
+                                   pamnet_stream_t stream);
+int pamnet_md_project_constraints_f32(float* pos, float* vel, const float* mass, const uint8_t* fixed, const int32_t* gptr,
+                                      int64_t n, int64_t n_graphs, int32_t* status, double* ke, const double* dt_g, double dt,
+                                      const int32_t* cons_i, const int32_t* cons_j, const double* cons_d, const int32_t* gcol,
+                                      const int32_t* colptr, int64_t n_cons, double* work, int32_t* sweeps, double tol,
+                                      int32_t max_sweeps, int32_t do_pos, int32_t do_vel, pamnet_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Attention fusion + per-graph pooling  (models.py:206-224)
  * outs/atts: [2L, n] rows ordered (global_0, local_0, global_1, local_1, ...).
  *   node_out[n] = sign[n] * sum_l sum_c outs[l,c,n] * softmax_c(leaky_relu(atts[l,c,n], 0.2))

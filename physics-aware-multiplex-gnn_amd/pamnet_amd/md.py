@@ -15,6 +15,13 @@ and is bitwise repeatable.  The loop takes no decision on the host.  There is no
 is the same dynamics at constant pressure (isotropic NPT): the stochastic cell rescaling barostat (Bernetti & Bussi, J. Chem.
 Phys. 153, 114107, 2020) fused into the step launch (csrc/md_npt.hip pamnet_md_npt_step_f32), under the same guarantees.
 
+    from pamnet_amd import md
+    cons = md.Constraints(data, md.bond_constraints(data.edge_index, data.x == 0))      # every X-H bond at its current length
+    res = md.run(model, data, steps=1000, dt=0.2, masses=m, kT=0.025, gamma=0.1, seed=seeds, constraints=cons)
+
+holds bond lengths fixed (g-BAOAB: SHAKE / RATTLE sweeps over constraints coloured once on the host, inside the step launch:
+csrc/md_constraints.hip pamnet_md_constrained_step_f32), which lets dt be doubled where X-H vibrations capped it.
+
 Units are the caller's: with energies in eV, lengths in Angstrom and masses in amu the time unit is 10.1805 fs (dt = 0.1 is about
 1 fs), kT is in eV and a pressure in eV / A^3 (160.2177 GPa; 1 bar = 6.2415e-7)."""
 import torch
@@ -25,13 +32,16 @@ from .relax import _cell_dof, _checked, _det3, _evaluate, _evaluate_cell
 
 STATE = ('seed', 'steps', 'status', 'ke')
 NPT_STATE = STATE + ('eps', 'pint', 'vol')         # per-graph scalars of the constant-pressure step (cell travels beside them)
+CONSTRAINED_STATE = STATE + ('sweeps',)            # of the constrained step: the most sweeps a solve of the launch took
 RUNNING, FAILED = 0, 2
+UNCONVERGED = 3                                   # (a constraint solve of the graph did not converge)
 
 
 class MDResult(object):
     """pos, vel [N, 3] fp32 (new tensors), energy [G] and forces [N, 3] of one evaluation at `pos`, kinetic [G] fp64 (of `vel`),
     steps int32 [G] (the steps a graph moved), failed bool [G], frames [F, N, 3] fp32 / epot, ekin [F, G] fp64 (record_every > 0,
     else None), trace (trace=True: one dict per launch, else None).  All on the device.
+    run with constraints adds: unconverged bool [G] (a constraint solve of the graph failed: status 3), sweeps int32 [G].
     run_npt adds: cell [G, 3, 3] fp32 (a new tensor), eps [G] fp64 (ln of the volume over the starting volume), volume and pressure
     [G] fp64 (the kernel's V and P_int = (2 KE - tr W) / (3 V) of `pos`, `vel` and `cell`; a graph without a barostat keeps
     |det cell| and NaN), virial [G, 3, 3] fp32 (W = dE/d strain) and stress = W / volume of the same evaluation; with record_every
@@ -108,9 +118,155 @@ def npt_step(pos, vel, dpos, dstrain, gptr, cell0, cell, state, dt, kT, pressure
              int(kick_in), int(advance), lib.stream_of(pos))
 
 
-def temperature(ekin, n_free, remove_com=True):
-    """kT = 2 KE / dof with dof = 3 n_free - 3 (remove_com); floats, arrays or tensors, per graph."""
-    return 2.0 * ekin / (3 * n_free - (3 if remove_com else 0))
+def temperature(ekin, n_free, remove_com=True, n_constraints=0):
+    """kT = 2 KE / dof with dof = 3 n_free - 3 (remove_com) - n_constraints; floats, arrays or tensors, per graph."""
+    return 2.0 * ekin / (3 * n_free - (3 if remove_com else 0) - n_constraints)
+
+
+def colour_constraints(pairs, graph):
+    """Greedy colouring on the host, in the order given: constraint k takes the smallest colour that no earlier constraint with
+    one of its atoms took, so a graph's colours depend on its own list only.  pairs: int [C, 2], graph: int [C] (numpy).
+    Returns (colour [C], order [C]): `order` sorts the constraints by (graph, colour), stably."""
+    import numpy as np
+    pairs, graph = np.asarray(pairs, dtype=np.int64).reshape(-1, 2), np.asarray(graph, dtype=np.int64).reshape(-1)
+    colour, used = np.zeros(len(pairs), dtype=np.int64), {}
+    for k, (i, j) in enumerate(pairs.tolist()):
+        taken = used.get(i, 0) | used.get(j, 0)   # (bit c set: colour c is taken at one of the two atoms)
+        c = (~taken & (taken + 1)).bit_length() - 1
+        colour[k] = c
+        used[i], used[j] = used.get(i, 0) | (1 << c), used.get(j, 0) | (1 << c)
+    return colour, np.lexsort((colour, graph))
+
+
+class Constraints(object):
+    """Distance constraints |x_i - x_j| = d of a batch, checked, coloured and sorted once (one read of the host at set-up), for
+    constrained_step / project_constraints / run(constraints=...).
+
+    data_or_batch: the batch (`batch`, `pos`, and `num_graphs` if it has it), or its `batch` tensor [N] alone.
+    pairs:   int64 [C, 2], atom rows; both atoms of a pair in one graph, i != j, no pair twice (in either order).
+    lengths: fp64 [C], positive and finite; None: the current distances of `data.pos`.
+    Holds, on the device of the batch and sorted by (graph, colour): i, j (int32 [C]), d (fp64 [C]), gcol (int32 [G + 1]: the
+    colours of a graph), colptr (int32 [K + 1]: the constraints of a colour); n_per_graph (int64 [G]); and on the host pairs,
+    colour and graph of the sorted constraints and `order`, their places in the caller's list."""
+
+    def __init__(self, data_or_batch, pairs, lengths=None):
+        import numpy as np
+        batch = data_or_batch if isinstance(data_or_batch, torch.Tensor) else getattr(data_or_batch, 'batch', None)
+        pos = None if isinstance(data_or_batch, torch.Tensor) else getattr(data_or_batch, 'pos', None)
+        if not isinstance(batch, torch.Tensor) or batch.dim() != 1:
+            raise ValueError('Constraints needs the batch, or its `batch` tensor [N] (the sorted graph id of every atom)')
+        device, n = batch.device, batch.numel()
+        b = batch.detach().cpu().numpy().astype(np.int64)
+        ng = None if isinstance(data_or_batch, torch.Tensor) else getattr(data_or_batch, 'num_graphs', None)
+        n_graphs = int(ng) if ng is not None else (int(b[-1]) + 1 if n else 0)
+        try:
+            p = (pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs))
+        except (TypeError, ValueError):
+            raise ValueError('`pairs` is an int64 tensor [C, 2] of atom rows; got %r' % (type(pairs),)) from None
+        if p.dtype.kind not in 'iu' or p.ndim != 2 or p.shape[1] != 2:
+            if not (p.size == 0 and p.ndim <= 2):
+                raise ValueError('`pairs` is an int64 tensor [C, 2] of atom rows; got %s %s' % (p.dtype, tuple(p.shape)))
+        p = p.astype(np.int64).reshape(-1, 2)
+        C = len(p)
+        if C and (p.min() < 0 or p.max() >= n):
+            raise ValueError('`pairs` holds atom rows in [0, N) = [0, %d); got %d .. %d' % (n, p.min(), p.max()))
+        if (p[:, 0] == p[:, 1]).any():
+            raise ValueError('a constraint joins two different atoms; `pairs`[%d] joins an atom to itself'
+                             % int(np.nonzero(p[:, 0] == p[:, 1])[0][0]))
+        graph = b[p[:, 0]] if C else np.zeros(0, np.int64)
+        if C and (graph != b[p[:, 1]]).any():
+            raise ValueError('both atoms of a constraint are in one graph; `pairs`[%d] joins two graphs'
+                             % int(np.nonzero(graph != b[p[:, 1]])[0][0]))
+        if C and (graph.min() < 0 or graph.max() >= n_graphs):
+            raise ValueError('`batch` holds graph ids outside [0, num_graphs) = [0, %d)' % n_graphs)
+        key = np.sort(p, axis=1)
+        if len(np.unique(key[:, 0] * max(n, 1) + key[:, 1])) != C:
+            raise ValueError('`pairs` holds a pair twice (the order of its two atoms does not matter)')
+        if lengths is None:
+            if pos is None:
+                raise ValueError('`lengths` is None: the current distances need `data.pos`, and only a `batch` tensor was given')
+            x = pos.detach().cpu().numpy().astype(np.float64)
+            d = np.sqrt(((x[p[:, 0]] - x[p[:, 1]]) ** 2).sum(1)) if C else np.zeros(0)
+        else:
+            try:
+                d = (lengths.detach().cpu().numpy() if isinstance(lengths, torch.Tensor) else np.asarray(lengths)).astype(np.float64)
+            except (TypeError, ValueError):
+                raise ValueError('`lengths` is a float64 tensor [C]; got %r' % (type(lengths),)) from None
+            if d.shape != (C,):
+                raise ValueError('`lengths` is a float64 tensor [C] = [%d], one per pair; got %s' % (C, tuple(d.shape)))
+        if not (np.isfinite(d) & (d > 0)).all():
+            raise ValueError('the lengths of the constraints must be positive and finite%s'
+                             % (' (two constrained atoms of `data.pos` coincide)' if lengths is None else ''))
+        colour, order = colour_constraints(p, graph)
+        self.order = order
+        self.pairs, self.colour, self.graph, self.lengths = p[order], colour[order], graph[order], d[order]
+        n_col = np.zeros(n_graphs, dtype=np.int64)                 # colours of a graph: its largest colour + 1
+        if C:
+            np.maximum.at(n_col, self.graph, self.colour + 1)
+        gcol = np.concatenate([[0], np.cumsum(n_col)])
+        slot = gcol[self.graph] + self.colour if C else np.zeros(0, np.int64)   # (ascending: the constraints are sorted by it)
+        colptr = np.concatenate([[0], np.cumsum(np.bincount(slot, minlength=int(gcol[-1])))])
+        if max(C, int(gcol[-1]), n) > 0x7fffffff:
+            raise ValueError('the constraint arrays are int32: N, C and the number of colours stay below 2^31')
+        to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a.astype(dt))).to(device)
+        self.n, self.n_atoms, self.n_graphs, self.device = C, n, n_graphs, device
+        self.i, self.j, self.d = to(self.pairs[:, 0], np.int32), to(self.pairs[:, 1], np.int32), to(self.lengths, np.float64)
+        self.gcol, self.colptr = to(gcol, np.int32), to(colptr, np.int32)
+        self.n_per_graph = to(np.bincount(self.graph, minlength=n_graphs), np.int64)
+        self._work = None
+
+    def work(self):
+        """The fp64 workspace [9 N] (x0, x, v) that constrained_step / project_constraints use where none is passed, made once.
+        Launches that share it must follow one another on one stream: concurrent launches (other streams) each need a `work` of
+        their own.  run() allocates one per run."""
+        if self._work is None:
+            self._work = torch.zeros(9 * self.n_atoms, dtype=torch.float64, device=self.device)
+        return self._work
+
+
+def bond_constraints(edge_index, mask):
+    """The unique pairs (i < j) of `edge_index` (int [2, E]; both directions of a bond count once) with at least one atom in
+    `mask` (bool [N]), e.g. data.z == 1 for the X-H bonds: int64 [C, 2] on the device of `edge_index`, sorted."""
+    a, b = edge_index[0].to(torch.int64), edge_index[1].to(torch.int64)
+    keep = (a != b) & (mask[a] | mask[b])
+    lo, hi = torch.minimum(a, b)[keep], torch.maximum(a, b)[keep]
+    n = mask.numel()
+    key = torch.unique(lo * n + hi)
+    return torch.stack([key // n, key % n], dim=1)
+
+
+def _cons_args(cons, work):
+    if cons.n and work is None:
+        work = cons.work()
+    elif cons.n and (work.dtype != torch.float64 or work.numel() < 9 * cons.n_atoms or work.device != cons.device):
+        raise ValueError('`work` is a float64 tensor of at least 9 N = %d entries on the device of the constraints; got %s [%d] on %s'
+                         % (9 * cons.n_atoms, work.dtype, work.numel(), work.device))
+    return (lib.ptr(cons.i), lib.ptr(cons.j), lib.ptr(cons.d), lib.ptr(cons.gcol), lib.ptr(cons.colptr), cons.n,
+            lib.ptr(work) if cons.n else None)
+
+
+def constrained_step(pos, vel, dpos, gptr, state, cons, dt, kT=0.0, gamma=0.0, mass=None, fixed=None, kick_in=1, advance=1,
+                     tol=1e-8, max_sweeps=500, work=None):
+    """One launch of pamnet_md_constrained_step_f32, in place on pos, vel and state (no synchronisation): md_step's arguments,
+    `cons` (a Constraints of this batch), and state['sweeps'] (int32 [n_graphs]) beside md_step's state.  work: fp64 [9 n]
+    workspace; None: the one `cons` keeps, which launches on one stream may share (Constraints.work)."""
+    (dt_g, dt), (kT_g, kT), (gamma_g, gamma) = _split(dt), _split(kT), _split(gamma)
+    lib.call('pamnet_md_constrained_step_f32', lib.ptr(pos), lib.ptr(vel), lib.ptr(dpos), lib.ptr(mass), lib.ptr(fixed),
+             lib.ptr(gptr), pos.size(0), gptr.numel() - 1, lib.ptr(state['seed']), lib.ptr(state['steps']),
+             lib.ptr(state['status']), lib.ptr(state['ke']), dt_g, kT_g, gamma_g, dt, kT, gamma, int(kick_in), int(advance),
+             *_cons_args(cons, work), lib.ptr(state['sweeps']), float(tol), int(max_sweeps), lib.stream_of(pos))
+
+
+def project_constraints(pos, vel, gptr, state, cons, dt=None, mass=None, fixed=None, do_pos=True, do_vel=True, tol=1e-8,
+                        max_sweeps=500, work=None):
+    """One launch of pamnet_md_project_constraints_f32, in place (no synchronisation): do_pos moves pos onto the lengths (SHAKE
+    along the current differences), do_vel removes the velocity along every constraint (RATTLE; needs dt, which scales its
+    convergence bound) and writes state['ke'].  vel may be None where do_vel is False.  state: status, ke, sweeps.  work: as for
+    constrained_step."""
+    dt_g, dt = _split(0.0 if dt is None else dt)
+    lib.call('pamnet_md_project_constraints_f32', lib.ptr(pos), lib.ptr(vel), lib.ptr(mass), lib.ptr(fixed), lib.ptr(gptr),
+             pos.size(0), gptr.numel() - 1, lib.ptr(state['status']), lib.ptr(state['ke']), dt_g, dt, *_cons_args(cons, work),
+             lib.ptr(state['sweeps']), float(tol), int(max_sweeps), int(bool(do_pos)), int(bool(do_vel)), lib.stream_of(pos))
 
 
 def _per_graph(name, v, n_graphs, device, positive):
@@ -138,7 +294,7 @@ def _per_graph(name, v, n_graphs, device, positive):
 
 
 def run(model, data, steps, dt, masses=None, kT=None, gamma=0.0, seed=0, fixed=None, velocities=None, remove_com=True,
-        record_every=0, check_every=0, trace=False):
+        record_every=0, check_every=0, trace=False, constraints=None, constraint_tol=1e-8, constraint_sweeps=500):
     """Move every graph of `data` for `steps` steps of length `dt`: velocity Verlet where gamma is 0, Langevin dynamics (BAOAB) at
     temperature kT and friction gamma elsewhere.  One model evaluation and one launch of the integrator per step.
 
@@ -161,6 +317,15 @@ def run(model, data, steps, dt, masses=None, kT=None, gamma=0.0, seed=0, fixed=N
     check_every: k > 0: the status vector is read every k steps, to stop once every graph has failed (a non-finite force or
             velocity).  0 (default): never -- everything is enqueued without a synchronisation of the driver's own.
     trace:  for tests and debugging: one dict per launch with clones of pos, dE/dpos, vel and the state before and after it.
+    constraints: a Constraints of this batch, or None.  With constraints the rule is g-BAOAB (Leimkuhler & Matthews 2016, one
+            geodesic sub-step per half drift; csrc/md_constraints.hip pamnet_md_constrained_step_f32 replaces the step launch):
+            the bond lengths are held by SHAKE / RATTLE, which lets `dt` be doubled where X-H vibrations capped it.  At set-up
+            the positions are projected onto the lengths and the starting velocities (Maxwell-Boltzmann or given) onto the
+            constraints.  A constraint between two fixed atoms is refused.  Positions are never wrapped, so a constrained pair
+            must sit in one image.  res.sweeps (int32 [G]) holds the most sweeps a solve of the last launch took,
+            res.unconverged (bool [G]) the graphs a solve failed for (status 3): they stop as a failed graph does.  The state of
+            a trace record gains `sweeps`.  A temperature counts dof = 3 N - 3 - C: temperature(..., n_constraints=C).
+    constraint_tol, constraint_sweeps: the relative bound of both solves and the sweeps one may take.
 
     The first launch opens step 0 (kick_in = 0), every later one closes the step before and opens the next, and one more
     evaluation and a closing launch (advance = 0) end the run: res.vel, res.kinetic, res.energy and res.forces all belong to
@@ -194,20 +359,43 @@ def run(model, data, steps, dt, masses=None, kT=None, gamma=0.0, seed=0, fixed=N
         raise ValueError('`velocities` is a float32 tensor [N, 3] = [%d, 3] on the device of `pos`; got %s'
                          % (n, '%s %s on %s' % (velocities.dtype, tuple(velocities.shape), velocities.device)
                             if isinstance(velocities, torch.Tensor) else type(velocities)))
+    cons = constraints
+    if cons is not None:
+        if not isinstance(cons, Constraints) or (cons.n_atoms, cons.n_graphs, cons.device) != (n, n_graphs, device):
+            raise ValueError('`constraints` is a md.Constraints of this batch (N = %d, num_graphs = %d, on %s); got %s'
+                             % (n, n_graphs, device, '%d atoms, %d graphs on %s' % (cons.n_atoms, cons.n_graphs, cons.device)
+                                if isinstance(cons, Constraints) else type(cons)))
+        constraint_tol, constraint_sweeps = float(constraint_tol), int(constraint_sweeps)
+        if not (constraint_tol > 0.0 and constraint_tol != float('inf')) or constraint_sweeps < 1:
+            raise ValueError('`constraint_tol` is positive and finite and `constraint_sweeps` at least 1; got %r, %r'
+                             % (constraint_tol, constraint_sweeps))
+        if fixed8 is not None and cons.n:
+            checks['constraints'] = ~(fixed8[cons.i.long()] & fixed8[cons.j.long()]).bool().any()
     vel, state = new_state(n, n_graphs, device, seed)
     names = [k for k, v in checks.items() if v is not None]
     if names:                                     # (as num_graphs: one read at set-up, for every tensor of values at once)
         ok = torch.stack([checks[k] for k in names]).tolist()
         bad = [k for k, good in zip(names, ok) if not good]
+        if 'constraints' in bad:
+            raise ValueError('`constraints` holds a pair whose two atoms are both `fixed`: its length cannot change, so there is '
+                             'nothing to constrain; drop the pair')
         if bad:
             raise ValueError('%s must be finite and positive (kT, gamma: non-negative) in every entry'
                              % ' and '.join('`%s`' % k for k in bad))
     cur = pos.detach().to(torch.float32).clone().contiguous()
     gptr, _ = G.csr_from_keys(batch.to(torch.int32).contiguous(), n_graphs)
+    if cons is not None:                          # the positions onto the lengths, before anything is evaluated
+        state['sweeps'] = torch.zeros(n_graphs, dtype=torch.int32, device=device)
+        solver = dict(tol=constraint_tol, max_sweeps=constraint_sweeps,     # (a workspace of this run's own: runs of one
+                      work=torch.empty(9 * n, dtype=torch.float64, device=device))   # Constraints on other streams share nothing)
+        project_constraints(cur, None, gptr, state, cons, None, masses, fixed8, do_pos=True, do_vel=False, **solver)
     if velocities is not None:
         vel = velocities.detach().clone().contiguous()
     elif kT is not None:
         init_velocities(vel, gptr, state['seed'], kT_k, state['ke'], masses, fixed8, remove_com=remove_com)
+    if cons is not None and (velocities is not None or kT is not None):
+        project_constraints(cur, vel, gptr, state, cons, dt, masses, fixed8, do_pos=False, do_vel=True, **solver)
+    keys = STATE if cons is None else CONSTRAINED_STATE
     frames = epot = ekin = None
     if record_every:
         n_rec = steps // record_every + 1
@@ -225,12 +413,15 @@ def run(model, data, steps, dt, masses=None, kT=None, gamma=0.0, seed=0, fixed=N
             epot[it // record_every].copy_(e.reshape(-1))
         if trace:
             t = dict(pos=cur.clone(), dE=de.clone(), v_before=vel.clone(), kick_in=kick_in, advance=advance,
-                     state_before={k: state[k].clone() for k in STATE})
-        md_step(cur, vel, de, gptr, state, dt, kT_k, gamma, masses, fixed8, kick_in, advance)
+                     state_before={k: state[k].clone() for k in keys})
+        if cons is None:
+            md_step(cur, vel, de, gptr, state, dt, kT_k, gamma, masses, fixed8, kick_in, advance)
+        else:
+            constrained_step(cur, vel, de, gptr, state, cons, dt, kT_k, gamma, masses, fixed8, kick_in, advance, **solver)
         if rec:
             ekin[it // record_every].copy_(state['ke'])
         if trace:
-            t.update(pos_after=cur.clone(), v_after=vel.clone(), state_after={k: state[k].clone() for k in STATE})
+            t.update(pos_after=cur.clone(), v_after=vel.clone(), state_after={k: state[k].clone() for k in keys})
             log.append(t)
         return e, de
 
@@ -241,8 +432,11 @@ def run(model, data, steps, dt, masses=None, kT=None, gamma=0.0, seed=0, fixed=N
         if check_every and done % check_every == 0 and not bool((state['status'] == RUNNING).any()):
             break
     energy, de = launch(done, 1 if done else 0, 0)  # one more evaluation: energy, forces, vel and ke belong to the final geometry
-    return MDResult(pos=cur, vel=vel, energy=energy, kinetic=state['ke'], forces=-de, steps=state['steps'],
-                    failed=state['status'] == FAILED, frames=frames, epot=epot, ekin=ekin, trace=log)
+    res = MDResult(pos=cur, vel=vel, energy=energy, kinetic=state['ke'], forces=-de, steps=state['steps'],
+                   failed=state['status'] == FAILED, frames=frames, epot=epot, ekin=ekin, trace=log)
+    if cons is not None:
+        res.unconverged, res.sweeps = state['status'] == UNCONVERGED, state['sweeps']
+    return res
 
 
 def run_npt(model, data, steps, dt, kT, pressure, tau_p, compressibility, masses=None, gamma=0.0, seed=0, fixed=None,
