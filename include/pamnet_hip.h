@@ -983,6 +983,57 @@ int pamnet_md_project_constraints_f32(float* pos, float* vel, const float* mass,
                                       int32_t max_sweeps, int32_t do_pos, int32_t do_vel, pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Replica-exchange molecular dynamics (parallel tempering; Sugita & Okamoto, Chem. Phys. Lett. 314, 141, 1999): one exchange
+ * attempt of every temperature ladder of a batch in one launch (csrc/remd.hip; the reference has no integrator).  A ladder is a
+ * run of consecutive graphs that hold the same atoms, one graph per temperature.  An exchange swaps the TEMPERATURES two graphs
+ * hold, not their configurations: no position, graph or neighbour structure moves; kT_g -- the array pamnet_md_step_f32 reads --
+ * the two rung tables and a scale of the velocities change.
+ *   energy [n_graphs] fp64, read only: the potential energy of every graph at its current positions;
+ *   vel [n, 3] fp32, in place;  fixed [n] uint8 or NULL;  gptr [n_graphs + 1] int32: as for pamnet_md_step_f32;
+ *   lptr [n_ladders + 1] int32: ladder l is the graphs lptr[l] .. lptr[l + 1] - 1 (kept inside [0, n_graphs]); it starts at 0,
+ *   does not decrease and ends at n_graphs.  A ladder of one graph (or of none) is legal and never exchanges;
+ *   kT_ladder [n_graphs] fp64, read only: entry lptr[l] + r is the temperature of rung r of ladder l (positive);
+ *   kT_g [n_graphs] fp64, in place: entry g is the temperature graph g holds;
+ *   rung [n_graphs] int32, in place: the rung graph g holds;  slot [n_graphs] int32, in place: entry lptr[l] + r is the graph
+ *   that holds rung r of ladder l -- the inverse of rung (slot[lptr[l] + rung[g]] == g);
+ *   status [n_graphs] int32, read only: the status of the step launch;  ke [n_graphs] fp64, in place;
+ *   seed [n_ladders] int64;  attempts [n_ladders] int32, in place: the exchange launches the ladder has seen;
+ *   tried, accepted [n_graphs] int32, in place: entry lptr[l] + r counts the pair (r, r + 1); the last entry of a ladder is
+ *   never written.
+ * The rule of ladder l, with lo = lptr[l], R its number of rungs, a = attempts[l] and parity p = a & 1:
+ *   1. For every r with r = p (mod 2) and r + 1 < R: i = slot[lo + r], j = slot[lo + r + 1].  status[i] != 0, status[j] != 0, or
+ *      energy[i] or energy[j] not finite: the pair is skipped -- not counted in tried, nothing of it is written.
+ *   2. D = (1 / kT_r - 1 / kT_{r+1}) (E_i - E_j) with kT from kT_ladder;  tried[lo + r] += 1.  Accept if D >= 0, or if
+ *      u < exp(D) with u = (x0 + 0.5) 2^-32 in fp64, x0 the first output of THE GENERATOR of the molecular-dynamics section
+ *      (Philox4x32-10) under the key (low 32 bits, high 32 bits) of seed[l] at the counter (r, a, 3, 0): stream 3 is the
+ *      exchange's (0: the thermostat, 1: the initial velocities, 2: the barostat).  Nothing else feeds the decision: it depends
+ *      on the ladder's seed, its attempt count, the rung and the two energies only.
+ *   3. On acceptance: slot[lo + r] = j, slot[lo + r + 1] = i;  rung[i] = r + 1, rung[j] = r;  kT_g[i] = kT_{r+1}, kT_g[j] = kT_r;
+ *      accepted[lo + r] += 1;  the velocities of the free atoms of i are multiplied by sqrt(kT_{r+1} / kT_r), those of j by
+ *      sqrt(kT_r / kT_{r+1}) -- fp64 arithmetic on the fp32 value, one rounding at the store; rows of fixed atoms are neither
+ *      read nor written --;  ke[i] *= kT_{r+1} / kT_r, ke[j] *= kT_r / kT_{r+1}.
+ *   4. attempts[l] += 1, also where no pair was tried.
+ * With the canonical weights exp(-E / kT) the acceptance min(1, exp(D)) keeps every rung's ensemble; the scale hands each
+ * graph velocities at its new temperature.  It is uniform over a graph, so velocities that satisfy distance constraints still do.
+ * The decision needs the ensemble of a thermostat at kT_g: call it between a closing step launch (kick_in 1, advance 0), which
+ * leaves vel and ke belonging to pos, and an opening one (kick_in 0, advance 1) on the same forces.
+ * One workgroup per ladder: one thread per pair decides, LDS carries (graph, scale) per rung behind a barrier, then the whole
+ * workgroup strides over the atoms of the graphs whose temperature changed.  No atomics and no floating-point sums: a ladder
+ * reads and writes its own entries only, so its outputs are bitwise repeatable and the same alone or inside any batch.
+ * A ladder has at most 256 rungs.
+ * Returns PAMNET_EINVAL for a negative count, n_graphs or n_ladders above 2^31 - 1, and n_graphs > 256 n_ladders (some ladder
+ * would have more than 256 rungs); PAMNET_ENULL for a null pointer: only fixed may be NULL.  n_ladders == 0 launches nothing.
+ * lptr lives on the device and the entry point does not read it: that it starts at 0, does not decrease, ends at n_graphs and
+ * holds no ladder above 256 rungs is the caller's to check (pamnet_amd.remd does, on the host); the kernel keeps every ladder
+ * inside [0, n_graphs], leaves a ladder of more than 256 rungs wholly alone (attempts included) and skips a pair whose slot
+ * entries do not name two graphs of its ladder.  (Part of ABI 18: nothing existing changed.)
+ * ------------------------------------------------------------------------------------------------------------------ */
+int pamnet_remd_exchange_f64(const double* energy, float* vel, const uint8_t* fixed, const int32_t* gptr, const int32_t* lptr,
+                             const double* kT_ladder, double* kT_g, int32_t* rung, int32_t* slot, const int32_t* status,
+                             double* ke, const int64_t* seed, int32_t* attempts, int32_t* tried, int32_t* accepted, int64_t n,
+                             int64_t n_graphs, int64_t n_ladders, pamnet_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Attention fusion + per-graph pooling  (models.py:206-224)
  * outs/atts: [2L, n] rows ordered (global_0, local_0, global_1, local_1, ...).
  *   node_out[n] = sign[n] * sum_l sum_c outs[l,c,n] * softmax_c(leaky_relu(atts[l,c,n], 0.2))
