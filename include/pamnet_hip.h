@@ -209,7 +209,10 @@ int pamnet_cell_images_axes_i32(const double* cell_table, const uint8_t* pbc, in
 
 /* knn: for every query node its k nearest nodes of the same graph (itself included, as torch_cluster.knn does),
  * ordered by (distance, index); then the self entry is dropped and entries with dist > cutoff are masked out:
- * nbr[i*k + s] = neighbour index or -1, dist[i*k + s] = distance.  (models.py:143-150) */
+ * nbr[i*k + s] = neighbour index or -1, dist[i*k + s] = distance.  (models.py:143-150)
+ * Ties in distance go to the lower index: the order is by (fp32 squared distance, index), exactly.  A masked entry (the
+ * self entry, dist > cutoff) keeps its slot and its dist.  A graph with fewer than k nodes fills the slots it has; the
+ * slots behind them are padding: nbr = -1, dist = +inf.  1 <= k <= 64 (PAMNET_EINVAL otherwise, nothing launched). */
 int pamnet_knn_i32(const float* pos, const int32_t* node_graph, const int32_t* gptr, int64_t n, int32_t k,
                    float cutoff, int32_t* nbr, float* dist, pamnet_stream_t stream);
 /* The kNN table (no cutoff: every entry but the self entry kept) together with what its two cuts keep per query -- cnt_a[i] /

@@ -943,7 +943,9 @@ __global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ pos,
     int bj;
     if (end - beg <= 64 * KNN_CACHE) knn_select(pos, xi, yi, zi, beg, end, K, lane, sd[w], sj[w], vd[w], vj[w], bd, bj);
     else knn_stream(pos, xi, yi, zi, beg, end, K, lane, bd, bj);
-    const float d = __fsqrt_rn(bd);
+    // sqrtf: the correctly rounded fp32 root (what a host computes from the same squared distance, bit for bit).  __fsqrt_rn is
+    // NOT that in this toolchain: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers map it to the native root, within one ulp.
+    const float d = sqrtf(bd);
     const bool keep = lane < K && (bj != 0x7fffffff) && (bj != (int)i) && (d <= cutoff);
     if (lane < K) {
         nbr[i * K + lane] = keep ? bj : -1;
