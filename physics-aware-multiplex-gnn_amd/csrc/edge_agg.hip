@@ -308,6 +308,10 @@ __global__ __launch_bounds__(WG8, 1) void global_edge_agg_fwd_kernel(GAggFwd a) 
                     if (RPP * i < 16 * mt) stage_e(rr + RPP * i, c4, pre[i]);
                 // (no branch around the requests: behind the workgroup's last row the guarded load reads that row again and
                 // zeroes it, and the requests in flight stay countable -- vector loads and stores retire in order on one counter)
+                // (What the compiler makes of the select on the value is a branch per row around each request; they stay in
+                // flight across the barrier and the GEMMs all the same, and rows behind the workgroup's last are not requested
+                // at all: the select-free ldg4cl_nt form, which requests them, measured 25.1 against 24.0 us per launch at the
+                // QM9 batch -- 128 rows per workgroup against 112-row chunks -- profiles/prefetch_in_flight_ab.txt.)
 #pragma unroll
                 for (int i = 0; i < NI; ++i) pre[i] = ldg4zl_nt(e, r1 + rr + RPP * i, re, DIM, c4);
             } else {
@@ -793,7 +797,9 @@ __global__ __launch_bounds__(WG8, 1) void global_edge_agg_bwd_kernel(GAggBwd a) 
     float4 pdm[AHEAD ? NI : 1];
     auto next_indices = [&](int64_t rbeg, int64_t rend) __attribute__((always_inline)) {
         if constexpr (AHEAD) {
-            const int64_t last = rend > rbeg ? rend - 1 : rbeg;      // (a chunk of edgeless nodes: any valid row, never used)
+            // (a chunk of edgeless nodes, or none behind the workgroup's last: any valid row, never used -- re >= 1 here)
+            int64_t last = rend > rbeg ? rend - 1 : rbeg;
+            last = last < re ? last : re - 1;
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
                 const int64_t g = rbeg + rr + RPP * i;
@@ -807,11 +813,20 @@ __global__ __launch_bounds__(WG8, 1) void global_edge_agg_bwd_kernel(GAggBwd a) 
             for (int i = 0; i < NI; ++i) pdm[i] = ldg4(d_agg, pgi[i], DIM, c4);
         }
     };
-    if (PRE && cur.r0 < re) {
+    if (PRE && cur.r0 >= re) {
+        // A workgroup without rows leaves here: its nodes get the zeros reduce_nodes writes for a node without rows.  The chunk
+        // loop is then entered only behind the requests below, whose index wait proves the weight pieces arrived -- reached
+        // around them too, the compiler re-waited for the pieces at every MFMA of every chunk (vmcnt counts along every path),
+        // and with them for the z / ea rows in flight.
+        float4* __restrict__ o = reinterpret_cast<float4*>(a.dPi);
+        for (int64_t k = (int64_t)nb * 32 + threadIdx.x; k < (int64_t)ne * 32; k += WG8) o[k] = f4zero();
+        return;
+    }
+    if (PRE) {
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            pz[i] = ldg4z(zs, cur.r0 + rr + RPP * i, re, DIM, c4);
-            pe[i] = ldg4z(eas, cur.r0 + rr + RPP * i, re, DIM, c4);
+            pz[i] = ldg4c(zs, cur.r0 + rr + RPP * i, re, DIM, c4);
+            pe[i] = ldg4c(eas, cur.r0 + rr + RPP * i, re, DIM, c4);
         }
         next_indices(cur.r0, cur.r1);
         next_gather();
@@ -827,7 +842,7 @@ __global__ __launch_bounds__(WG8, 1) void global_edge_agg_bwd_kernel(GAggBwd a) 
         if ((int)threadIdx.x <= nn) sptr[threadIdx.x] = mypraw - (int)r0;
         mypraw = load_node_ptr(ptr, nxt.c0, a.n);
         APROBE(1);
-        if (rows > 0) {
+        if (AHEAD || rows > 0) {
             // (Restructuring this sweep -- operands a row / a group of rows ahead, stores last -- changed nothing: all
             // workgroups run it at the same time and it moves 85 MB through L2 / Infinity Cache in ~8 us: bandwidth, not
             // latency, tools/agg_probe.py.)
@@ -850,11 +865,24 @@ __global__ __launch_bounds__(WG8, 1) void global_edge_agg_bwd_kernel(GAggBwd a) 
             }
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
-                if (RPP * i >= 16 * mt) continue;
+                if (!AHEAD && RPP * i >= 16 * mt) continue;   // (AHEAD: every tile, zeros behind the chunk's rows)
                 const int r = rr + RPP * i;
                 const int64_t g = r0 + r;
                 float4 x = f4zero(), y = f4zero();
-                if (g < r1) {
+                if constexpr (AHEAD) {
+                    // (all three operands are in registers: the products for every row, kept for the valid ones -- a register
+                    // read only under the row test counts as a request possibly still in flight where it is written next, and
+                    // the requests for the next chunk below waited there for this sweep's stores)
+                    const float4 dm = dmv[i], zz = pz[i], ee = pe[i];
+                    const float4 xv = f4mul(f4mul(dm, ee), f4dsilu(zz)), yv = f4mul(dm, f4silu(zz));
+                    const bool ok = g < r1;                     // (selects, not a branch around the products)
+                    x = make_float4(ok ? xv.x : 0.f, ok ? xv.y : 0.f, ok ? xv.z : 0.f, ok ? xv.w : 0.f);
+                    y = make_float4(ok ? yv.x : 0.f, ok ? yv.y : 0.f, ok ? yv.z : 0.f, ok ? yv.w : 0.f);
+                    if (ok) {
+                        stg4(dz, g, DIM, c4, x);
+                        stg4(dea, g, DIM, c4, y);
+                    }
+                } else if (g < r1) {
                     const float4 dm = GATHER_FIRST ? dmv[GATHER_FIRST ? i : 0] : ldg4(d_agg, row_of[g], DIM, c4);
                     const float4 zz = PRE ? pz[PRE ? i : 0] : ldg4(zs, g, DIM, c4);   // (non-temporal reads of the saves
                     const float4 ee = PRE ? pe[PRE ? i : 0] : ldg4(eas, g, DIM, c4);  //  measured slower: 793 vs 766 us)
@@ -872,11 +900,15 @@ __global__ __launch_bounds__(WG8, 1) void global_edge_agg_bwd_kernel(GAggBwd a) 
                 }
             }
         }
-        if (PRE && r1 < re) {                                  // the next chunk starts at r1: its rows travel during the GEMMs
+        if constexpr (PRE) {                                   // the next chunk starts at r1: its rows travel during the GEMMs
+            // No select on the loaded value (ldg4cl: the sweep above reads a row only under g < r1) and no branch around the
+            // requests (behind the workgroup's last row they read that row again): the compiler counts vmcnt along every path
+            // through the loop, and with either it waited for these rows before the barrier below, or behind it where a
+            // register of an older conditional request is written next.
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
-                pz[i] = ldg4z(zs, r1 + rr + RPP * i, re, DIM, c4);
-                pe[i] = ldg4z(eas, r1 + rr + RPP * i, re, DIM, c4);
+                pz[i] = ldg4cl(zs, r1 + rr + RPP * i, re, DIM, c4);
+                pe[i] = ldg4cl(eas, r1 + rr + RPP * i, re, DIM, c4);
             }
             next_indices(r1, nxt.r1);
         }
@@ -886,20 +918,20 @@ __global__ __launch_bounds__(WG8, 1) void global_edge_agg_bwd_kernel(GAggBwd a) 
         reduce_nodes<16>(c0, nn, rows, S0, sptr, carry[par], carry[par ^ 1], nullptr, a.dPi);   // reads S0 only
         par ^= 1;
         APROBE(4);
-        if (rows > 0) {
-            constexpr bool PREACC = MTX <= 5;                  // (the 8 / 9-tile instantiations have no registers to spare)
-            constexpr bool EARLY = PRE && MTX <= 3;            // ahead of the GEMMs where the registers allow
-            float4 dacc[PREACC ? NI : 1];                      // accumulate operand of the final sweep
-            auto fetch_acc = [&]() {
+        constexpr bool PREACC = MTX <= 5;                      // (the 8 / 9-tile instantiations have no registers to spare)
+        constexpr bool EARLY = PRE && MTX <= 3;                // ahead of the GEMMs where the registers allow
+        float4 dacc[PREACC ? NI : 1];                          // accumulate operand of the final sweep
+        auto fetch_acc = [&]() {
 #pragma unroll
-                for (int i = 0; i < NI; ++i) {
-                    int64_t g = r0 + rr + RPP * i;
-                    g = g < r1 ? g : r1 - 1;
-                    dacc[PREACC ? i : 0] = ldg4(d_e, g, DIM, c4);
-                }
-            };
+            for (int i = 0; i < NI; ++i) {
+                int64_t g = r0 + rr + RPP * i;
+                g = g < r1 ? g : r1 - 1;
+                dacc[PREACC ? i : 0] = ldg4(d_e, g, DIM, c4);
+            }
+        };
+        AccSet<MTX, 1> acc;
+        if (rows > 0) {
             if (EARLY && accumulate) fetch_acc();
-            AccSet<MTX, 1> acc;
             acc.zero();
             if constexpr (PL) {
                 mma_p16<MTX, true, BG>(P0, f1, acc.a[0], f1, acc.a[0], mt);
@@ -909,7 +941,12 @@ __global__ __launch_bounds__(WG8, 1) void global_edge_agg_bwd_kernel(GAggBwd a) 
                 mma_b16<MTX, true, BG>(S1, f2, acc.a[0], f2, acc.a[0], mt);
             }
             APROBE(5);
-            if (AHEAD && r1 < re) next_gather();               // (the indices arrived during the GEMMs)
+        }
+        // (the indices arrived during the GEMMs.)  ONE request site for chunks with rows and chunks of edgeless nodes, behind
+        // the join: as a second site in an else arm, its loads counted as possibly pending at the GEMMs' first LDS reads
+        // (the compiler counts vmcnt along every path) and the z / ea rows in flight were waited for there
+        next_gather();
+        if (rows > 0) {
             // otherwise requested here (the A fragments' registers are free again): the two barriers and the accumulator
             // stores cover the latency
             if (PREACC && !EARLY && accumulate) fetch_acc();
@@ -927,8 +964,6 @@ __global__ __launch_bounds__(WG8, 1) void global_edge_agg_bwd_kernel(GAggBwd a) 
                     stg4(d_e, g, DIM, c4, v);
                 }
             }
-        } else if (AHEAD && r1 < re) {
-            next_gather();                                     // (a chunk of edgeless nodes ran no GEMMs to issue it behind)
         }
         APROBE(7);
         __syncthreads();

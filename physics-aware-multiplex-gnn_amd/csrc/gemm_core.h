@@ -368,6 +368,17 @@ __device__ __forceinline__ float4 ldg4z(const float* p, int64_t row, int64_t nro
     if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
     return v;
 }
+// Prefetch form: the same clamped address, the loaded value returned as it is.  For registers that are held across a barrier
+// or a GEMM phase and whose every consumer substitutes zero for an out-of-range row itself: the select of ldg4z needs the
+// loaded value, so ahead of a join (a conditional request, a loop back edge) the compiler waits for the load right where it
+// was issued and nothing is left in flight.  An out-of-range row holds row 0's data: never use it unguarded.
+__device__ __forceinline__ float4 ldg4c(const float* p, int64_t row, int64_t nrows, int ld, int c4) {
+    return *reinterpret_cast<const float4*>(p + (row < nrows ? row : 0) * ld + 4 * c4);
+}
+// the same, out-of-range rows reading the LAST valid row (nrows >= 1): for requests every workgroup issues behind its own range
+__device__ __forceinline__ float4 ldg4cl(const float* p, int64_t row, int64_t nrows, int ld, int c4) {
+    return *reinterpret_cast<const float4*>(p + (row < nrows ? row : nrows - 1) * ld + 4 * c4);
+}
 __device__ __forceinline__ void stg4(float* p, int64_t row, int ld, int c4, float4 v) {
     *reinterpret_cast<float4*>(p + row * ld + 4 * c4) = v;
 }
