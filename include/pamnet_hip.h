@@ -1037,6 +1037,78 @@ int pamnet_remd_exchange_f64(const double* energy, float* vel, const uint8_t* fi
                              int64_t n_graphs, int64_t n_ladders, pamnet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Biased dynamics over collective variables: harmonic restraints (umbrella windows, walls) and well-tempered metadynamics
+ * (Barducci, Bussi & Parrinello, Phys. Rev. Lett. 100, 020603, 2008) with multiple walkers (Raiteri et al., J. Phys. Chem. B
+ * 110, 3533, 2006); csrc/bias.hip, the reference has no integrator.  pamnet_bias_apply_f64 is one launch per step, between
+ * the model evaluation and pamnet_md_step_f32 / pamnet_md_constrained_step_f32: it adds the gradient of the bias to dpos.
+ * A bias GROUP is a run of consecutive graphs that share one hill table: one graph is an ordinary simulation, W graphs are W
+ * walkers on one table.
+ *   pos [n, 3] fp32, read only;  dpos [n, 3] fp32, in place;  status [n_graphs] int32, in place: the status of the step launch;
+ *   gptr [n_graphs + 1] int32: as for pamnet_md_step_f32;
+ *   bptr [n_groups + 1] int32: group t is the graphs bptr[t] .. bptr[t + 1] - 1 (kept inside [0, n_graphs]), as lptr of
+ *   pamnet_remd_exchange_f64;
+ *   cvptr [n_graphs + 1] int32: graph g owns the collective variables (CVs) cvptr[g] .. cvptr[g + 1] - 1, at most 16;
+ *   kind [n_cvs] int32: 0 distance (2 atoms), 1 angle (3 atoms, radians, at the middle atom), 2 dihedral (4 atoms);
+ *   atoms [n_cvs, 4] int32: atom rows, all inside the graph of the CV; the entries beyond the kind's count are not read;
+ *   kappa, centre, halfwidth [n_cvs] fp64: the restraint of every CV;
+ *   ndim [n_groups] int32 in {0, 1, 2}: the first ndim CVs of every graph of the group carry the hills;
+ *   sigma [n_groups, 2] fp64 (positive where used), height0 [n_groups] fp64, inv_dT [n_groups] fp64: 1 / (kT (gamma - 1)) of
+ *   the bias factor gamma, 0 for plain metadynamics;
+ *   hill_c [n_groups, h_cap, 2] fp64, hill_w [n_groups, h_cap] fp64, n_hills [n_groups] int32, dropped [n_groups] int32: the
+ *   hill tables, in place;  deposit: 0 or 1;
+ *   cv [n_cvs] fp64, ebias [n_graphs] fp64: written.
+ * The CVs, in fp64 from the fp32 positions as they are (never wrapped: the atoms of a CV must sit in one image):
+ *   distance  d = |x_j - x_i|;  dd/dx_j = (x_j - x_i) / d = -dd/dx_i;
+ *   angle     theta = atan2(|a x b|, a . b), a = x_i - x_j, b = x_k - x_j, nn = a x b;
+ *             dtheta/dx_i = a x nn / (|a|^2 |nn|), dtheta/dx_k = nn x b / (|b|^2 |nn|), dtheta/dx_j = -(the two);
+ *   dihedral  phi = atan2(|b2| b1 . (b2 x b3), (b1 x b2) . (b2 x b3)), b1 = x_j - x_i, b2 = x_k - x_j, b3 = x_l - x_k; with
+ *             m = b1 x b2, nn = b2 x b3 (Blondel & Karplus, J. Comput. Chem. 17, 1132, 1996):
+ *             dphi/dx_i = -|b2| m / |m|^2, dphi/dx_l = |b2| nn / |nn|^2,
+ *             dphi/dx_j = (|b2| / |m|^2 + p) m + q nn, dphi/dx_k = -p m - (q + |b2| / |nn|^2) nn,
+ *             p = b1 . b2 / (|m|^2 |b2|), q = b3 . b2 / (|nn|^2 |b2|).
+ *   A dihedral is periodic: every difference s - c it enters (hill and restraint) is d - 2 pi rint(d / (2 pi)).
+ * The rule of graph g of group t, with n0 = n_hills[t] read once at the start of the launch (kept inside [0, h_cap]):
+ *   1. status[g] != 0 (or more than 16 CVs): the graph is skipped -- its dpos rows stay bitwise, its cv entries and ebias[g]
+ *      are NaN, it deposits nothing.
+ *   2. Every CV s_k and its gradient are formed.  If one of these numbers is not finite (collinear atoms of an angle or a
+ *      dihedral, coincident atoms, a non-finite position), the kind is unknown or an atom lies outside the graph:
+ *      status[g] = 2, dpos stays untouched, cv and ebias[g] are NaN, nothing is deposited.
+ *   3. V = sum_{h < n0} w_h exp(-1/2 sum_{d < ndim} u_hd^2), u_hd = (s_d - c_hd) / sigma_d;  dV/ds_d = -sum_h e_h u_hd /
+ *      sigma_d.  The order of the sum is fixed: thread q of 256 adds the hills q, q + 256, ... in that order; the 64 lanes of a
+ *      wavefront are added by the butterfly v += v[lane ^ o], o = 32, 16, ..., 1; the four wavefront sums are added in order.
+ *   4. Restraint of CV k where kappa_k != 0: a = |s_k - centre_k| - halfwidth_k; where a > 0, E_k = 1/2 kappa_k a^2 and
+ *      dE_k/ds_k = kappa_k a sign(s_k - centre_k).  halfwidth 0: an umbrella window; > 0: a pair of walls.
+ *   5. ebias[g] = V + sum_k E_k in the order of k;  c_k = (k < ndim ? dV/ds_k : 0) + dE_k/ds_k.
+ *   6. For k in order, where c_k != 0, for the atoms of the CV in order, per component:
+ *      dpos = (float)((double)dpos + c_k ds_k/dx) -- one thread, one rounding per addition: atoms that two CVs share (phi / psi)
+ *      are handled by this order, not by atomics.
+ *   7. deposit == 1, ndim > 0, after every graph of the group: the graphs that passed 2, in graph order, append the centre
+ *      (s_0, s_1) (s_1 = 0 where ndim is 1) and the height height0 exp(-V inv_dT), with the V of step 3 -- against the n0 old
+ *      hills, so the walkers of one launch do not see each other -- at n_hills[t], which rises by one each.  Where the table is
+ *      full nothing is written and dropped[t] counts it.
+ * One workgroup of 256 threads per group takes its walkers one after another; every loop count is read by all threads alike.
+ * No atomics: a group reads and writes its own entries only, so its outputs are bitwise repeatable and the same alone or
+ * inside any batch.  A group has at most 256 graphs.
+ * Returns PAMNET_EINVAL for a negative count, a count above 2^31 - 1, deposit outside {0, 1}, n_graphs > 256 n_groups and
+ * n_cvs > 16 n_graphs; PAMNET_ENULL for a null pointer (none may be NULL).  n_groups == 0 launches nothing.  bptr and cvptr
+ * live on the device and are not read by the entry point: the kernel leaves a group of more than 256 graphs wholly alone.
+ *
+ * pamnet_bias_grid_f64: out[i] = V of table `table` at points[i, 0 .. ndim) (fp64 [n_points, ndim], ndim 1 or 2), summed over
+ * the hills [0, n_hills[table]) in hill order by one thread per point; periodic [n_groups, 2] int32 says which dimensions wrap.
+ * It serves the free-energy estimate.  PAMNET_EINVAL for a negative count, table outside [0, n_groups), ndim outside {1, 2};
+ * PAMNET_ENULL for a null pointer; n_points == 0 launches nothing.  (Both are part of ABI 18: nothing existing changed.)
+ * ------------------------------------------------------------------------------------------------------------------ */
+int pamnet_bias_apply_f64(const float* pos, float* dpos, int32_t* status, const int32_t* gptr, const int32_t* bptr,
+                          const int32_t* cvptr, const int32_t* kind, const int32_t* atoms, const double* kappa,
+                          const double* centre, const double* halfwidth, const int32_t* ndim, const double* sigma,
+                          const double* height0, const double* inv_dT, double* hill_c, double* hill_w, int32_t* n_hills,
+                          int32_t* dropped, double* cv, double* ebias, int64_t n, int64_t n_graphs, int64_t n_groups,
+                          int64_t n_cvs, int64_t h_cap, int32_t deposit, pamnet_stream_t stream);
+int pamnet_bias_grid_f64(const double* hill_c, const double* hill_w, const int32_t* n_hills, const double* sigma,
+                         const int32_t* periodic, const double* points, double* out, int64_t table, int64_t n_groups,
+                         int64_t h_cap, int64_t n_points, int32_t ndim, pamnet_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Attention fusion + per-graph pooling  (models.py:206-224)
  * outs/atts: [2L, n] rows ordered (global_0, local_0, global_1, local_1, ...).
  *   node_out[n] = sign[n] * sum_l sum_c outs[l,c,n] * softmax_c(leaky_relu(atts[l,c,n], 0.2))

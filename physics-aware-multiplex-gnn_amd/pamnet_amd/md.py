@@ -22,6 +22,13 @@ Phys. 153, 114107, 2020) fused into the step launch (csrc/md_npt.hip pamnet_md_n
 holds bond lengths fixed (g-BAOAB: SHAKE / RATTLE sweeps over constraints coloured once on the host, inside the step launch:
 csrc/md_constraints.hip pamnet_md_constrained_step_f32), which lets dt be doubled where X-H vibrations capped it.
 
+    from pamnet_amd import bias
+    b = bias.Bias(data, [bias.dihedral(4, 6, 8, 14)], metadynamics=dict(ndim=1, sigma=0.35, height=0.012, bias_factor=8, kT=0.025, pace=50))
+    res = md.run(model, data, steps=20000, dt=0.1, masses=m, kT=0.025, gamma=0.1, seed=seeds, bias=b)
+
+biases the run along collective variables (restraints and well-tempered metadynamics: one more launch per step before the
+step launch, csrc/bias.hip pamnet_bias_apply_f64; pamnet_amd/bias.py).
+
 Units are the caller's: with energies in eV, lengths in Angstrom and masses in amu the time unit is 10.1805 fs (dt = 0.1 is about
 1 fs), kT is in eV and a pressure in eV / A^3 (160.2177 GPa; 1 bar = 6.2415e-7)."""
 import torch
@@ -42,6 +49,7 @@ class MDResult(object):
     steps int32 [G] (the steps a graph moved), failed bool [G], frames [F, N, 3] fp32 / epot, ekin [F, G] fp64 (record_every > 0,
     else None), trace (trace=True: one dict per launch, else None).  All on the device.
     run with constraints adds: unconverged bool [G] (a constraint solve of the graph failed: status 3), sweeps int32 [G].
+    run with bias adds: cv [F, K] and ebias [F, G] fp64 (record_every > 0, else None); forces include the bias, energy does not.
     run_npt adds: cell [G, 3, 3] fp32 (a new tensor), eps [G] fp64 (ln of the volume over the starting volume), volume and pressure
     [G] fp64 (the kernel's V and P_int = (2 KE - tr W) / (3 V) of `pos`, `vel` and `cell`; a graph without a barostat keeps
     |det cell| and NaN), virial [G, 3, 3] fp32 (W = dE/d strain) and stress = W / volume of the same evaluation; with record_every
@@ -294,7 +302,7 @@ def _per_graph(name, v, n_graphs, device, positive):
 
 
 def run(model, data, steps, dt, masses=None, kT=None, gamma=0.0, seed=0, fixed=None, velocities=None, remove_com=True,
-        record_every=0, check_every=0, trace=False, constraints=None, constraint_tol=1e-8, constraint_sweeps=500):
+        record_every=0, check_every=0, trace=False, constraints=None, constraint_tol=1e-8, constraint_sweeps=500, bias=None):
     """Move every graph of `data` for `steps` steps of length `dt`: velocity Verlet where gamma is 0, Langevin dynamics (BAOAB) at
     temperature kT and friction gamma elsewhere.  One model evaluation and one launch of the integrator per step.
 
@@ -326,10 +334,28 @@ def run(model, data, steps, dt, masses=None, kT=None, gamma=0.0, seed=0, fixed=N
             res.unconverged (bool [G]) the graphs a solve failed for (status 3): they stop as a failed graph does.  The state of
             a trace record gains `sweeps`.  A temperature counts dof = 3 N - 3 - C: temperature(..., n_constraints=C).
     constraint_tol, constraint_sweeps: the relative bound of both solves and the sweeps one may take.
+    bias:   a bias.Bias of this batch, or None: restraints and well-tempered metadynamics over collective variables (CVs).  After
+            every evaluation one more launch (csrc/bias.hip pamnet_bias_apply_f64) adds the gradient of the bias to dE/dpos,
+            before the step launch -- plain or constrained, unchanged -- reads it; on the steps `it` with it % pace == 0 it also
+            deposits one hill per walker (never in the closing launch).  That depends on the loop index only: no decision on the
+            host.  Where the Bias was given no `capacity`, its tables grow here by what the run can deposit.  res.forces INCLUDE
+            the bias, res.energy and res.epot do NOT (the model alone).  With record_every, res.cv [F, K] (the CVs, in the sorted
+            order of the Bias) and res.ebias [F, G] (the bias energies), fp64, are recorded beside epot; without, both are None
+            (bias.cv and bias.ebias hold those of res.pos).  NaN marks a graph that was not running.  A graph whose CV or CV
+            gradient is not finite fails (status 2) like one with a non-finite force.  A trace record gains dE_model (dE before the bias; dE is what the step launch read), status_before_bias, cv,
+            ebias, deposit and n_hills_before / n_hills_after; hills_before / hills_after (centres, heights) where it deposits.
+            With None the launches are exactly those without this argument.  run_npt and remd.run take no bias: the virial
+            of a bias and its part in the exchange energy are not implemented.
 
     The first launch opens step 0 (kick_in = 0), every later one closes the step before and opens the next, and one more
     evaluation and a closing launch (advance = 0) end the run: res.vel, res.kinetic, res.energy and res.forces all belong to
     res.pos.  A failed graph stops moving but is still evaluated."""
+    if bias is not None:                          # (a refusal that needs no device comes first)
+        from .bias import Bias
+        p = getattr(data, 'pos', None)
+        if not isinstance(bias, Bias) or (isinstance(p, torch.Tensor) and (bias.n_atoms, bias.device) != (p.size(0), p.device)):
+            raise ValueError('`bias` is a bias.Bias of this batch (N atoms, on the device of `pos`); got %s'
+                             % ('%d atoms on %s' % (bias.n_atoms, bias.device) if isinstance(bias, Bias) else type(bias)))
     try:
         pos, batch, n_graphs, _, fixed8 = _checked(model, data, 0.0, fixed)
     except ValueError as e:
@@ -371,6 +397,11 @@ def run(model, data, steps, dt, masses=None, kT=None, gamma=0.0, seed=0, fixed=N
                              % (constraint_tol, constraint_sweeps))
         if fixed8 is not None and cons.n:
             checks['constraints'] = ~(fixed8[cons.i.long()] & fixed8[cons.j.long()]).bool().any()
+    if bias is not None:
+        if (bias.n_atoms, bias.n_graphs, bias.device) != (n, n_graphs, device):
+            raise ValueError('`bias` is a bias.Bias of this batch (N = %d, num_graphs = %d, on %s); got %d atoms, %d graphs on %s'
+                             % (n, n_graphs, device, bias.n_atoms, bias.n_graphs, bias.device))
+        bias.reserve(steps)
     vel, state = new_state(n, n_graphs, device, seed)
     names = [k for k, v in checks.items() if v is not None]
     if names:                                     # (as num_graphs: one read at set-up, for every tensor of values at once)
@@ -396,21 +427,40 @@ def run(model, data, steps, dt, masses=None, kT=None, gamma=0.0, seed=0, fixed=N
     if cons is not None and (velocities is not None or kT is not None):
         project_constraints(cur, vel, gptr, state, cons, dt, masses, fixed8, do_pos=False, do_vel=True, **solver)
     keys = STATE if cons is None else CONSTRAINED_STATE
-    frames = epot = ekin = None
+    frames = epot = ekin = cvs = ebiases = None
     if record_every:
         n_rec = steps // record_every + 1
         frames = torch.zeros(n_rec, n, 3, dtype=torch.float32, device=device)
         epot = torch.zeros(n_rec, n_graphs, dtype=torch.float64, device=device)
         ekin = torch.zeros(n_rec, n_graphs, dtype=torch.float64, device=device)
+        if bias is not None:
+            cvs = torch.zeros(n_rec, bias.n_cvs, dtype=torch.float64, device=device)
+            ebiases = torch.zeros(n_rec, n_graphs, dtype=torch.float64, device=device)
     log = [] if trace else None
 
     def launch(it, kick_in, advance):
-        """Evaluate at cur, then one launch; step `it` is recorded at its full step: cur before the launch, ke after it."""
+        """Evaluate at cur, then the bias launch if there is one, then one launch; step `it` is recorded at its full step: cur
+        before the launch, ke after it."""
         e, de = _evaluate(model, data, cur)
         rec = record_every and it % record_every == 0
         if rec:
             frames[it // record_every].copy_(cur)
             epot[it // record_every].copy_(e.reshape(-1))
+        if bias is not None:
+            deposit = 1 if advance and bias.pace and it % bias.pace == 0 else 0
+            if trace:
+                tb = dict(dE_model=de.clone(), status_before_bias=state['status'].clone(), deposit=deposit,
+                          n_hills_before=bias.tab['n_hills'].clone())
+                if deposit:
+                    tb['hills_before'] = (bias.tab['hill_c'].clone(), bias.tab['hill_w'].clone())
+            bias.apply(cur, de, state['status'], deposit)
+            if rec:
+                cvs[it // record_every].copy_(bias.cv)
+                ebiases[it // record_every].copy_(bias.ebias)
+            if trace:
+                tb.update(cv=bias.cv.clone(), ebias=bias.ebias.clone(), n_hills_after=bias.tab['n_hills'].clone())
+                if deposit:
+                    tb['hills_after'] = (bias.tab['hill_c'].clone(), bias.tab['hill_w'].clone())
         if trace:
             t = dict(pos=cur.clone(), dE=de.clone(), v_before=vel.clone(), kick_in=kick_in, advance=advance,
                      state_before={k: state[k].clone() for k in keys})
@@ -422,6 +472,8 @@ def run(model, data, steps, dt, masses=None, kT=None, gamma=0.0, seed=0, fixed=N
             ekin[it // record_every].copy_(state['ke'])
         if trace:
             t.update(pos_after=cur.clone(), v_after=vel.clone(), state_after={k: state[k].clone() for k in keys})
+            if bias is not None:
+                t.update(tb)
             log.append(t)
         return e, de
 
@@ -436,6 +488,8 @@ def run(model, data, steps, dt, masses=None, kT=None, gamma=0.0, seed=0, fixed=N
                    failed=state['status'] == FAILED, frames=frames, epot=epot, ekin=ekin, trace=log)
     if cons is not None:
         res.unconverged, res.sweeps = state['status'] == UNCONVERGED, state['sweeps']
+    if bias is not None:
+        res.cv, res.ebias = cvs, ebiases
     return res
 
 
